@@ -23,6 +23,14 @@ BASELINE.json metric: "FP8 decode-attn us & fused-MoE TFLOPS (fixed shapes); AR+
   (benchmark/fuse_allreduce_rmsorm/benchmark_fuse_allreduce_rmsnorm.py:305,514; README.md:31-48).
 
 Contract: python bench.py --gpus N --steps K --warmup W prints ONE JSON line on rank 0.
+
+A plain run is lean: it builds the headline inputs, warms up, times exactly K steps and prints the line (`metric`,
+`value`, `unit`, `ms_per_step`, the headline's event timings and roofline fraction).  Everything else - the in-run
+parity check against the CPU oracle, the CPU baseline, the single-step-replay and scheduler timings, the committed
+profile figures, `second_metric`, `allreduce_summary`, the `extras` and the indented copy in bench_last.json - runs
+only with `--full` (where --no-cpu-baseline / --no-extras / --no-moe / --no-low-latency trim it as before).
+`--dump-outputs DIR` writes the timed path's output of the last timed step as DIR/<name>.npy (float32); the inputs
+are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -422,7 +430,7 @@ def moe_kernel_us():
             out["down"], out["down_calls"] = round(avg, 1), int(r.get("Calls") or 0)
     if "gate_up" not in out or "down" not in out:
         return None
-    out["source"] = f"profiles/{f.name} (rocprofv3 --kernel-trace --stats over `bench.py --no-extras --no-low-latency`: every launch of these rows is T = 4096)"
+    out["source"] = f"profiles/{f.name} (rocprofv3 --kernel-trace --stats over `bench.py --full --no-extras --no-low-latency`: every launch of these rows is T = 4096)"
     return out
 
 
@@ -1150,6 +1158,22 @@ def allreduce_summary(ar, world):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` (what a caller of the timed path receives) as <out_dir>/<name>.npy in
+    float32, at most DUMP_BUDGET_BYTES in all"""
+    import numpy as np
+
+    total = sum(t.numel() * 4 for t in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET_BYTES}"
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(d / f"{name}.npy", t.detach().float().cpu().numpy())
+
+
 # ================================================================================ main
 def cpu_selftest(args):
     """No-GPU path of the N > 1 plumbing (tests/test_bench_dist.py): gloo ranks, the same timed-region
@@ -1181,6 +1205,10 @@ def main():
     ap.add_argument("--no-low-latency", action="store_true",
                     help="second_metric at T = 4096 only (no T = 16 / 256 / 16384 launches): the rocprofv3 pass behind "
                          "profiles/round6_bench_kernel_stats.csv, whose grouped-GEMM rows then hold T = 4096 launches only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: in-run parity, CPU baseline, second metric, extras, bench_last.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's output of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -1223,7 +1251,7 @@ def main():
     step()
     torch.cuda.synchronize()
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ref, rows, cpu = c3_cpu_baseline(inp, w)
         got = out.reshape(w["batch"], w["num_seq_q"], w["num_head_q"], w["head_dim"])[rows].cpu()
         err = (got.float() - ref.float()).abs().max().item()
@@ -1242,6 +1270,9 @@ def main():
     if not args.no_graph:
         try:
             graph = capture(step, reps)
+            # captured in every run, before the timed region, although only --full replays it: without this capture the
+            # timed replays of `graph` ran 3-5 % slower (same-call A/B of fresh processes; extra eager steps instead of
+            # it did not close the gap; cause not pinned down)
             single = capture(step, 1) if reps > 1 else graph
         except Exception as e:  # noqa: BLE001
             print(f"[bench] graph capture failed ({e}); timing eager launches", file=sys.stderr)
@@ -1251,19 +1282,23 @@ def main():
     wall, per_replay_ms = timed_region(run, args.steps // reps, -(-args.warmup // reps), dist_on, dev, torch.cuda.synchronize)
     per_step_ms = sorted(t / reps for t in per_replay_ms)
     kern_ms_avg = sum(per_step_ms) / len(per_step_ms)
-    us_single = timed(single.replay, iters=50, warm=5) if single is not None else None
-    us_sched = timed(lambda: hpc.assign_attention_decode_task(inp["kv_lens"], task_map, w["num_head_kv"], w["num_seq_q"],
-                                                             True, w["min_process_len"]), iters=20, warm=3)
+    if args.dump_outputs and rank == 0:  # `out` still holds the last timed step's result
+        dump_outputs(args.dump_outputs, {"attention_decode_fp8_out": out})
+    us_single = us_sched = None
+    if args.full:
+        us_single = timed(single.replay, iters=50, warm=5) if single is not None else None
+        us_sched = timed(lambda: hpc.assign_attention_decode_task(inp["kv_lens"], task_map, w["num_head_kv"], w["num_seq_q"],
+                                                                 True, w["min_process_len"]), iters=20, warm=3)
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:  # every rank takes part (one child process per rank); rank 0 reports
             extras.update(extra_allreduce(rank, world, local_rank))
         except Exception as e:  # noqa: BLE001
             extras["fuse_allreduce_rmsnorm"] = {"error": repr(e)[:200]}
 
     second = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         kv_lens_cpu = inp["kv_lens"].cpu()
         graph_used = graph is not None
         del graph, single, run, inp
@@ -1299,7 +1334,7 @@ def main():
         # commit it was taken at so that a stale figure is visible
         traffic, traffic_src = None, None
         pmc = _latest_profile("decode_fp8_pmc_r6.json", "decode_fp8_pmc_r5.json", "decode_fp8_pmc_r4.json", "decode_fp8_pmc.json")
-        if pmc is not None:
+        if args.full and pmc is not None:
             pj = json.loads(pmc.read_text())
             traffic, traffic_src = pj.get("hbm_bytes_per_launch"), f"profiles/{pmc.name} ({pj.get('taken_at', 'round 2 kernel')})"
         ar_key = f"fuse_allreduce_rmsnorm_bf16_H8192_ws{world}"
@@ -1307,7 +1342,7 @@ def main():
             "metric": "attention_decode_fp8_kv_throughput", "value": round(value, 1), "unit": "GB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "fp8_e4m3", "data": "synthetic",
+            "vs_baseline": None, "dtype": "fp8_e4m3", "data": "synthetic", "full": args.full,
             "config": {
                 "workload": "FP8 decode attention, BASELINE configs[2]: batch 64, 8 KV / 64 Q heads, d 128, q per-token/per-head "
                             f"scales, K/V per-tensor, lengths log-uniform [128, 32768] seed 41 ({int(kv_lens_cpu.sum())} KV tokens), "
@@ -1335,14 +1370,15 @@ def main():
             "cpu_baseline": cpu,
             "second_metric": second,
             "allreduce_summary": allreduce_summary(extras.get(ar_key), world),
-            "scheduler_us": round(us_sched, 1),
+            "scheduler_us": None if us_sched is None else round(us_sched, 1),
             "us_per_call_median": round(per_step_ms[len(per_step_ms) // 2] * 1e3, 2),
             "extras": extras,
         }
-        try:  # the same record, indented, for profiles/ (the driver keeps only the head and tail of stdout)
-            (ROOT / "bench_last.json").write_text(json.dumps(line, indent=1))
-        except OSError:
-            pass
+        if args.full:
+            try:  # the same record, indented, for profiles/ (the driver keeps only the head and tail of stdout)
+                (ROOT / "bench_last.json").write_text(json.dumps(line, indent=1))
+            except OSError:
+                pass
         print(json.dumps(line))
     if dist_on:
         dist.destroy_process_group()

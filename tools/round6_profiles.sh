@@ -4,7 +4,7 @@
 # runs (--pmc with --kernel-trace only).  tools/round6_summarise.py condenses the outputs.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6prof; mkdir -p $O
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --steps 100 --warmup 20 --no-extras --no-cpu-baseline --no-low-latency > $O/bench.log 2>&1; echo "bench rc=$?"
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --steps 100 --warmup 20 --full --no-extras --no-cpu-baseline --no-low-latency > $O/bench.log 2>&1; echo "bench rc=$?"
 timeout 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python $R/tools/pmc_decode.py mixed > $O/pmc_fetch.log 2>&1; echo "fetch rc=$?"
 timeout 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python $R/tools/pmc_decode.py mixed > $O/pmc_write.log 2>&1; echo "write rc=$?"
 timeout 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_sq -- python $R/tools/pmc_decode.py mixed > $O/pmc_sq.log 2>&1; echo "sq rc=$?"

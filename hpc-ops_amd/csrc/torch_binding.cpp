@@ -197,6 +197,9 @@ at::Tensor attention_decode_fp8(const at::Tensor& q, at::Tensor& kcache, at::Ten
     TORCH_CHECK(kscale.dim() == 4 && kscale.stride(3) == 1 && kscale.element_size() == 1,
                 "per-token kscale must be the byte view of the K-cache tail rows");
     ks[0] = kscale.stride(0), ks[1] = kscale.stride(1), ks[2] = kscale.stride(2);
+    // both kernel generations read the scales as dwords (page, tail row and head offsets added to the base)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(kscale.data_ptr()) % 4 == 0 && ks[0] % 4 == 0 && ks[1] % 4 == 0 && ks[2] % 4 == 0,
+                "per-token kscale: base address and block / row / head strides must be multiples of 4 bytes");
   } else {
     TORCH_CHECK(block_size == 16 || block_size == 32 || block_size == 64, "kvcache paged blocksize must be 16, 32 or 64.");
     TORCH_CHECK(kscale.scalar_type() == at::kFloat && kscale.numel() >= 1, "kscale must be float32 [1]");

@@ -266,3 +266,60 @@ def ref_prefill_bf16(q, kcache, vcache, cu_seqlens_q, block_ids, seqlens_kv):
         scores = scores.masked_fill(~mask, float("-inf"))
         out[a0:a1] = torch.matmul(F.softmax(scores, dim=-1), BV).transpose(0, 1).to(torch.bfloat16)
     return out
+
+
+def ref_attn_by_kv_head(q, kvcache, block_ids, num_seq_q, lens_total, rows=None, q_scale=None, k_scale=None, v_scale=None,
+                        k_per_token=False, literal_qscale_row=False):
+    """ref_attn_fp8 (q_scale given) or ref_attn_with_paged_kvcache (q_scale None) for long requests: the same arithmetic,
+    one kv head at a time, so that a 128k-token request at 8 / 64 heads does not materialise `repeat_interleave(group)`
+    over the whole request (> 4 GB).  kvcache [nblk, 2, P, Hkv, D] (token rows only); k_scale for k_per_token is the byte
+    view of the K-cache tail rows, as in ref_attn_fp8; lens_total = tokens of each request INCLUDING its Sq new ones.
+    `rows` restricts the computation to a subset of requests.  Returns [len(rows), Sq, Hq, D] (bf16 for fp8, q's dtype
+    for bf16); bit-equal to the pinned oracles (tests/test_attn_bar.py)."""
+    num_batch = lens_total.shape[0]
+    num_head_q, head_dim = q.shape[1], q.shape[2]
+    P, num_head_kv = kvcache.shape[2], kvcache.shape[3]
+    group = num_head_q // num_head_kv
+    fp8 = q_scale is not None
+    sq = num_seq_q
+    qb = q.reshape(num_batch, sq, num_head_q, head_dim)
+    qs = q_scale.reshape(num_batch, sq, num_head_q) if fp8 else None
+    rows = range(num_batch) if rows is None else rows
+    out = torch.empty(len(rows), sq, num_head_q, kvcache.shape[4], dtype=torch.bfloat16 if fp8 else q.dtype)
+    for oi, bi in enumerate(rows):
+        seqlen = int(lens_total[bi])
+        blk = block_ids[bi, : (seqlen + P - 1) // P].long()
+        causal = torch.cat(
+            [torch.ones(sq, seqlen - sq, dtype=torch.bool),
+             torch.tril(torch.ones(sq, sq, dtype=torch.bool))], dim=-1).unsqueeze(0)
+        for g in range(num_head_kv):
+            hs = slice(g * group, (g + 1) * group)
+            q_batch = qb[bi, :, hs].transpose(0, 1).float()
+            k_batch = kvcache[blk, 0, :, g].reshape(-1, head_dim)[:seqlen].float().unsqueeze(0).expand(group, -1, -1)
+            v_batch = kvcache[blk, 1, :, g].reshape(-1, head_dim)[:seqlen].float().unsqueeze(0).expand(group, -1, -1)
+            p = q_batch @ k_batch.transpose(-1, -2) / math.sqrt(head_dim)
+            if not fp8:
+                p = p.masked_fill(~causal, float("-inf"))
+                y = torch.matmul(F.softmax(p, dim=-1), v_batch)
+                out[oi, :, hs] = y.transpose(0, 1).to(out.dtype)
+                continue
+            if literal_qscale_row:
+                p = p * q_scale[bi][hs, None, None]
+            else:
+                p = p * qs[bi][:, hs].transpose(0, 1)[:, :, None]
+            if k_per_token:
+                ksb = (k_scale[blk].contiguous().view(torch.float32)[:, :, g].reshape(-1)[:seqlen]).float()
+                p = p * ksb[None, None, :]
+            else:
+                p = p * k_scale
+            p = p.masked_fill(~causal, float("-inf"))
+            w = torch.exp(p - p.max(dim=-1)[0][:, :, None])
+            gsum = w.sum(dim=-1)[:, :, None]
+            w = (w * 256.0).to(torch.float8_e4m3fn).float()
+            y = torch.matmul(w, v_batch) / gsum
+            if k_per_token:
+                y = y * v_scale[g] / 256.0
+            else:
+                y = y * (v_scale / 256.0)
+            out[oi, :, hs] = y.transpose(0, 1).to(torch.bfloat16)
+    return out

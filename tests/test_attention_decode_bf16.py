@@ -7,7 +7,8 @@ import math
 import pytest
 import torch
 
-from utils import allclose, dev_set
+from decode_needles import TAU_UNIFORM_BF16
+from utils import allclose, attn_close, dev_set
 
 
 def _build_case(num_batch, num_seq_q, lens_before, block_size, kv_head_q_head, kvcache_shape, seed=41):
@@ -70,6 +71,7 @@ def _run(num_batch, num_seq_q, lens_before, block_size, kv_head_q_head, new_kv_i
     if use_output:
         assert my.data_ptr() == out.data_ptr()
     assert allclose(gt, my.cpu(), atol=0.016)
+    assert attn_close(gt, my.cpu(), TAU_UNIFORM_BF16, num_seq_q)
 
 
 @pytest.mark.gpu

@@ -7,7 +7,8 @@ import math
 import pytest
 import torch
 
-from utils import allclose, dev_set
+from decode_needles import TAU_UNIFORM_FP8, TAU_UNIFORM_FP8_KTOK
+from utils import allclose, attn_close, dev_set
 
 
 def _case(num_batch, num_seq_q, lens_before, block_size, kv_head_q_head, k_per_token, seed=41):
@@ -83,6 +84,7 @@ def _run(num_batch, num_seq_q, lens_before, block_size, kv_head_q_head, k_per_to
     torch.cuda.synchronize()
     assert my.dtype == torch.bfloat16
     assert allclose(gt, my.cpu(), atol=atol)
+    assert attn_close(gt, my.cpu(), TAU_UNIFORM_FP8_KTOK if k_per_token else TAU_UNIFORM_FP8, num_seq_q)
 
 
 @pytest.mark.gpu

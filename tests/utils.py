@@ -25,6 +25,40 @@ def allclose(ref_tensor, real_tensor, atol=1e-8, rtol=1e-5):
     return ok
 
 
+# Floor of the per-row scale in attn_close: a row whose largest |ref| is below it is measured against the floor, so
+# all-zero reference rows cannot divide by zero.  Far below the smallest row scale of any decode generator here
+# (near-uniform attention over 64k tokens of randn V: max |y| ~ 1e-3) and above bf16's subnormals.
+ATTN_FLOOR = 1e-5
+
+
+def attn_rel_err(ref, real, num_seq_q=1, floor=ATTN_FLOOR):
+    """Per (request, q row, q head): max_d |real - ref| / max(max_d |ref|, floor), as float32 [B, Sq, Hq].  NaN and inf
+    in `real` count as an infinite error."""
+    assert ref.shape == real.shape, (ref.shape, real.shape)
+    hq, d = ref.shape[-2], ref.shape[-1]
+    a = ref.float().reshape(-1, num_seq_q, hq, d)
+    b = real.float().reshape(-1, num_seq_q, hq, d).to(a.device)
+    err = (b - a).abs().amax(-1).nan_to_num(nan=float("inf"))
+    return err / a.abs().amax(-1).clamp_min(floor)
+
+
+def attn_close(ref, real, tau, num_seq_q=1, floor=ATTN_FLOOR, label=""):
+    """Scale-aware decode-attention bar: every (request, q row, q head) of `real` must sit within tau of its own row's
+    scale (attn_rel_err).  An absolute atol on outputs of |y| ~ 0.01 accepts an all-zero answer; this one does not.
+    On failure the worst rows are printed: request, row, head, relative error, max |ref|."""
+    rel = attn_rel_err(ref, real, num_seq_q, floor)
+    ok = bool((rel <= tau).all())
+    if not ok:
+        scale = ref.float().reshape(rel.shape + (-1,)).abs().amax(-1)
+        bad = int((rel > tau).sum())
+        print(f"\nattn_close FAILED {label}: {bad}/{rel.numel()} (request, row, head) out of tau={tau:.4g}; "
+              f"worst {float(rel.max()):.4g}")
+        for i in torch.topk(rel.reshape(-1), min(10, rel.numel())).indices.tolist():
+            b, s, h = (int(v) for v in torch.unravel_index(torch.tensor(i), rel.shape))
+            print(f"  request {b} row {s} head {h}: err {float(rel[b, s, h]):.4g} x scale, max|ref| {float(scale[b, s, h]):.4g}")
+    return ok
+
+
 def to_cpu(*ts):
     return [t.cpu() if t is not None else None for t in ts]
 

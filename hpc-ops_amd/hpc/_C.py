@@ -93,6 +93,11 @@ _sig("hpc_attention_prefill_bf16_async", I, P, P, P, P, P, I, I, I, I, I, I, I, 
 _sig("hpc_masked_act_mul_and_quant_async", I, P, P, P, P, I, I, I, P)
 _sig("hpc_masked_act_mul_and_blockwise_quant_async", I, P, P, P, P, I, I, I, P)
 _sig("hpc_reformat_x_scale_async", I, P, P, P, P, I, I, I, I, P)
+_sig("hpc_stem_oam_prep_paged_kv_async", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, L, L, L, L, L, L,
+     L, L, L, P)
+_sig("hpc_stem_oam_prep_varlen_q_async", I, P, P, P, P, P, I, I, I, I, I, I, L, L, L, P)
+_sig("hpc_stem_oam_gemm_async", I, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P)
+_sig("hpc_stem_tpd_async", I, P, P, P, P, P, I, I, I, I, I, F, I, I, F, I, F, I, P)
 _sig("hpc_sampler_segments", I, I)
 _sig("hpc_fused_sampler_workspace_bytes", L, I, I, I)
 _sig("hpc_fused_sampler_async", I, P, P, P, I, P, L, P, P, F, P, F, I, P, I, I, P, F, P, I, I, L, I, ctypes.c_uint64, P)

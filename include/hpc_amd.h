@@ -382,6 +382,54 @@ int hpc_attention_with_kvcache_prefill_fp8_async(
     int64_t kscale_block_stride_bytes, int64_t kscale_row_stride_bytes, int64_t kscale_head_stride_bytes,
     hpc_stream_t stream);
 
+/* ---- Stem block-sparse mask generation (feeds hpc_attention_with_kvcache_blocksparse_prefill_fp8) ----------------
+ * Stem block S = 128 tokens, stride R = 16 (16 groups of 8 tokens g, g+16, ..., g+112 per block), head dim 128; only
+ * these are supported (-1 otherwise).  Kb_r / Qb_r = ceil(len_r / 128); every output element is written, padding
+ * blocks as zeros (kflat, qflat, vbias, mask) or -inf (logits).
+ *
+ * hpc_stem_oam_prep_paged_kv_async
+ *   reference: stem_oam_prep_paged_kv_qpertoken_perhead_kvpertensor_dim128_async (quant_type 1) and
+ *   stem_oam_prep_paged_kv_qkpertoken_perhead_vperhead_dim128_async (quant_type 0),
+ *   src/stem/stem_oam_prep_paged_kv_dim128.h (entry src/stem/entry.cc:19-110).
+ *   kcache / vcache e4m3 [pages, block_size = 32 | 64, Hkv, 128] (strides in elements), kv_indices int32
+ *   [B, num_seq_max_blocks], kv_seq_lens int32 [B].  kflat bf16 [B, Hkv, max_num_stem_blocks, 2048]: group g of block
+ *   b = sum of kscale_t * K[t] at columns (15 - g) * 128 (reversed group order); v_norm f32 scratch
+ *   [B, Hkv, max_num_stem_blocks * 8]: max row norm of vscale * V per 16-token window; vbias f32
+ *   [B, Hkv, max_num_stem_blocks] from the per-(request, head) mean / sample std of log(v_norm + 1e-6).
+ *   quant_type 1: kscale / vscale f32 [1]; 0: kscale f32 per token at [page, row / 32, head, row % 32] (strides in
+ *   f32 elements), vscale f32 [Hkv]. */
+int hpc_stem_oam_prep_paged_kv_async(
+    void* kflat, void* vbias, void* v_norm, const void* kcache, const void* vcache, const void* kscale,
+    const void* vscale, const void* kv_indices, const void* kv_seq_lens, int quant_type, int num_batch, int num_dim_qk,
+    int num_dim_v, int num_head_kv, int block_size, int num_seq_max_blocks, int stem_block_size, int stem_stride,
+    int max_num_stem_blocks, float lambda_mag, int64_t kcache_block_stride, int64_t kcache_token_stride,
+    int64_t kcache_head_stride, int64_t vcache_block_stride, int64_t vcache_token_stride, int64_t vcache_head_stride,
+    int64_t kscale_block_stride, int64_t kscale_row_stride, int64_t kscale_head_stride, hpc_stream_t stream);
+/* reference: stem_oam_prep_varlen_q_dim128_async, src/stem/stem_oam_prep_varlen_q_dim128.h (entry :114-155).
+ * q_fp8 e4m3 [total_q, Hq, 128] (row stride ldQ bytes), qscale f32 [B, Hq, >= max q_len] (strides in elements),
+ * cu_seqlens_q int32 [B + 1].  qflat bf16 [B, Hq, max_num_q_blocks, 2048], group g at columns g * 128. */
+int hpc_stem_oam_prep_varlen_q_async(void* qflat, const void* q_fp8, const void* qscale, const void* q_seq_lens,
+                                     const void* cu_seqlens_q, int num_batch, int num_head_q, int num_dim_qk,
+                                     int stem_block_size, int stem_stride, int max_num_q_blocks, int64_t ldQ,
+                                     int64_t qscale_batch_stride, int64_t qscale_head_stride, hpc_stream_t stream);
+/* reference: stem_oam_gemm_dim128_async, src/stem/stem_oam_gemm_dim128.h (entry :157-222).
+ * qflat / kflat / vbias contiguous as produced above; block_logits bf16 [B, Hq, max_num_qb, max_num_kb] =
+ * qflat . kflat^T / 64 + vbias[h_q / (Hq / Hkv)], -inf where qb >= Qb_r, kb >= Kb_r or (causal) qb + off < kb with
+ * off = (kv_len - q_len + 127) / 128. */
+int hpc_stem_oam_gemm_async(void* block_logits, const void* qflat, const void* kflat, const void* vbias,
+                            const void* q_seq_lens, const void* kv_seq_lens, int num_batch, int num_head_q,
+                            int num_head_kv, int max_num_qb, int max_num_kb, int stem_block_size, int stem_stride,
+                            int causal, hpc_stream_t stream);
+/* reference: stem_tpd_async, src/stem/stem_tpd.h (entry :224-266).  block_logits bf16 contiguous
+ * [B, H, max_Qb, max_Kb <= 32768]; mask uint8 of the same shape: per row < Qb_r the columns < Kb_r whose order key is
+ * at or above the exact top-`budget` threshold, plus the first initial_blocks, the window_size blocks ending at the
+ * diagonal min(row + off, Kb_r - 1) and the diagonal; 0 elsewhere. */
+int hpc_stem_tpd_async(void* mask, const void* block_logits, const void* q_seq_lens, const void* kv_seq_lens,
+                       const void* num_prompt_tokens, int num_batch, int num_heads, int max_Qb, int max_Kb,
+                       int block_size, float alpha, int initial_blocks, int window_size, float k_block_num_rate_medium,
+                       int k_block_num_bias_medium, float k_block_num_rate_large, int k_block_num_bias_large,
+                       hpc_stream_t stream);
+
 /* ---- fused sampler (end of the decode step) ----
  * reference: fused_sampler_async / fused_sampler_temperature_async, src/sampler/sampler.h:17-45
  *            (kernels src/sampler/fused_sampler.cu, fused_sampler_temperature.cu; entry src/sampler/entry.cc).

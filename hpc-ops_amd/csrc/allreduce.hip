@@ -63,14 +63,6 @@ __device__ __forceinline__ bool arrived(u32x4 v) {
   return v[0] != kSentinel && v[1] != kSentinel && v[2] != kSentinel && v[3] != kSentinel;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 // r = bf16(sum + residual) -> residual_out; y = bf16(float(r) * rsqrt(mean(r^2) + eps) * w)
 // acc[i][0..7] hold the all-reduced row (fp32, already rounded to bf16 precision by the caller if
 // the mode requires it); returns the normalised row packed in `out`.
@@ -132,7 +124,7 @@ struct HtArgs {
   long spin_limit;
   float eps;
   int rows, hidden, rank, ws;
-  int cas_barrier;  // development key 47 = 1: signal barriers with compare-and-swap (rounds 1-5)
+  int cas_barrier;  // development key kDevArCasBarrier = 1: signal barriers with compare-and-swap (rounds 1-5)
   int sig_stride;   // words between the flag groups of consecutive blocks (hpc_..._signal_stride: spread over the whole pad)
 };
 
@@ -152,7 +144,7 @@ __device__ __forceinline__ void signal_barrier(const HtArgs& a, int bid, bool cl
   //    system-scope accesses.  The rows this rank keeps to itself (out_residual: ordinary write-back stores) are nobody
   //    else's business and reach memory at the end of the kernel like any other output.
   const int t = threadIdx.x;
-  if (kHpcDevBuild && a.cas_barrier) {  // development key 47 = 1: the form of rounds 1-5 (CAS loops, release / acquire fences) - A/B
+  if (kHpcDevBuild && a.cas_barrier) {  // development key kDevArCasBarrier = 1: the form of rounds 1-5 (CAS loops, release / acquire fences) - A/B
     if (closing) __threadfence_system();
     __syncthreads();
     if (t < a.ws) {
@@ -554,9 +546,9 @@ __global__ __launch_bounds__(kThreads) void ll_fused_loopback_kernel(const LlArg
 using namespace hpc::ar;
 
 namespace {
-// development key 10 = n: bounded spins give up after 2^n rounds (tests of the lost-peer path)
+// development key kDevArSpinLog2 = n: bounded spins give up after 2^n rounds (tests of the lost-peer path)
 long spin_limit() {
-  const int n = hpc_dev_tuning_get(10);
+  const int n = hpc_dev_tuning_get(kDevArSpinLog2);
   return n > 0 && n < 40 ? 1L << n : kSpinLimit;
 }
 // one word of pinned, device-mapped host memory shared by every device of the process
@@ -593,7 +585,7 @@ extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_grid(int world_size, i
   // only (num_max_blocks, world size, pad capacity) - never of this rank's row count (the reference
   // launches num_max_blocks blocks for the same reason, high_throughput.cu:135-150).  One row is
   // only 2 * hidden bytes per peer, so the reference's SM-count-sized default leaves most of an
-  // MI355X idle: at least two workgroups per CU (development key 11 = n replaces the floor of 512 -
+  // MI355X idle: at least two workgroups per CU (development key kDevArMinGrid = n replaces the floor of 512 -
   // the tests that run two ranks on ONE GPU need both ranks' grids co-resident).  Block b posts into
   // words [b * ws, (b + 1) * ws) of a pad.
   // Round 6: TWO workgroups per CU (512).  The kernels hold <= 256 registers and a few bytes of LDS, so two 4-wave workgroups
@@ -602,7 +594,7 @@ extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_grid(int world_size, i
   // 72.9 / 49.9 / 45.3, T = 16384 376 / 218 / 196.  (With the system-scope fences of rounds 1-5 in the barriers every
   // workgroup cost 85 ns of serialised L2 write-back / invalidate and 256 beat 512: 79 against 103 us at T = 4096.)
   // A constant, not the device's CU count: the value must be the same on every rank.
-  const int floor_dev = hpc_dev_tuning_get(11);
+  const int floor_dev = hpc_dev_tuning_get(kDevArMinGrid);
   const int floor_blocks = floor_dev > 0 ? floor_dev : 512;
   int grid = num_max_blocks > floor_blocks ? num_max_blocks : floor_blocks;
   if (grid > signal_pad_words / world_size) grid = signal_pad_words / world_size;
@@ -615,10 +607,10 @@ extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_grid(int world_size, i
 // floor(pad_words / grid) rounded down to a multiple of 16 words, never below ws.  Rank-invariant like the grid.  Measured
 // at ws = 1 it is worth little (T = 512: 31.4 -> 29.7 us per call with the old fences in place; the fixed cost was the
 // fences, see signal_barrier) - kept because with eight ranks every word is polled across a link and eight times as many
-// words share a line; development key 48 = 1 restores the packed layout.
+// words share a line; development key kDevArPackedFlags = 1 restores the packed layout.
 extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_signal_stride(int world_size, int grid, int signal_pad_words) {
   if (world_size < 1 || world_size > kMaxWs || grid <= 0 || signal_pad_words < grid * world_size) return HPC_ERR_INVALID;
-  if (hpc_dev_tuning_get(48) == 1) return world_size;  // development key 48 = 1: the packed layout of rounds 1-5 (A/B)
+  if (hpc_dev_tuning_get(kDevArPackedFlags) == 1) return world_size;  // development key kDevArPackedFlags = 1: the packed layout of rounds 1-5 (A/B)
   const int spread = (signal_pad_words / grid) & ~15;
   return spread > world_size ? spread : world_size;
 }
@@ -654,7 +646,7 @@ extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_async(
   a.hidden = hidden_size;
   a.rank = rank;
   a.ws = world_size;
-  a.cas_barrier = hpc_dev_tuning_get(47) == 1;
+  a.cas_barrier = hpc_dev_tuning_get(kDevArCasBarrier) == 1;
   a.sig_stride = hpc_fuse_allreduce_rmsnorm_high_throughput_signal_stride(world_size, grid, signal_pad_words);
   if (a.sig_stride < world_size) return HPC_ERR_INVALID;
 #define HPC_HT_LAUNCH(WS)                                          \
@@ -662,7 +654,7 @@ extern "C" int hpc_fuse_allreduce_rmsnorm_high_throughput_async(
     ht_kernel<WS, 4><<<grid, kThreads, 0, stream>>>(a);             \
   else                                                              \
     ht_kernel<WS, 8><<<grid, kThreads, 0, stream>>>(a)
-  switch (hpc_dev_tuning_get(9) == 1 ? 0 : world_size) {  // key 9 = 1: runtime-world-size kernel
+  switch (hpc_dev_tuning_get(kDevArRuntimeWorld) == 1 ? 0 : world_size) {  // key kDevArRuntimeWorld = 1: runtime-world-size kernel
     case 1: HPC_HT_LAUNCH(1); break;
     case 2: HPC_HT_LAUNCH(2); break;
     case 4: HPC_HT_LAUNCH(4); break;
@@ -743,7 +735,7 @@ extern "C" int hpc_allreduce_low_latency_async(
   const bool wide = hidden_size > 4 * kThreads * 8;
   // one launch up to one workgroup per CU (measured at ws = 1, H 8192: T 8 / 128 9.0 / 11.5 us against 10.0 / 12.5 with two
   // launches, T 512 25.6 against 23.1 - with two workgroups per CU the second's scatter waits behind the first's poll)
-  const int key35 = hpc_dev_tuning_get(35);  // development: 1 = always two launches, 2 = one launch whenever resident
+  const int key35 = hpc_dev_tuning_get(kDevArLlLaunches);  // development: 1 = always two launches, 2 = one launch whenever resident
   if (key35 != 1 && grid <= ll_fused_capacity(wide, key35 == 2)) {
     if (!wide)
       ll_fused_kernel<4><<<grid, kThreads, 0, stream>>>(a);
@@ -804,7 +796,7 @@ extern "C" int hpc_dev_allreduce_loopback_ht(const void* const* peer_x, void* co
     a.hidden = hidden;
     a.rank = r;
     a.ws = world_size;
-    a.cas_barrier = hpc_dev_tuning_get(47) == 1;
+    a.cas_barrier = hpc_dev_tuning_get(kDevArCasBarrier) == 1;
     a.sig_stride = hpc_fuse_allreduce_rmsnorm_high_throughput_signal_stride(world_size, grid, pad_words);
     if (a.sig_stride < world_size) return HPC_ERR_INVALID;
   }
@@ -816,7 +808,7 @@ extern "C" int hpc_dev_allreduce_loopback_ht(const void* const* peer_x, void* co
     ht_loopback_kernel<WS, 4><<<g, kThreads, 0, stream>>>(dev);          \
   else                                                                   \
     ht_loopback_kernel<WS, 8><<<g, kThreads, 0, stream>>>(dev)
-  switch (hpc_dev_tuning_get(9) == 1 ? 0 : world_size) {
+  switch (hpc_dev_tuning_get(kDevArRuntimeWorld) == 1 ? 0 : world_size) {
     case 1: HPC_HT_LOOP(1); break;
     case 2: HPC_HT_LOOP(2); break;
     case 4: HPC_HT_LOOP(4); break;
@@ -857,14 +849,14 @@ extern "C" int hpc_dev_allreduce_loopback_ll(void* const* output, void* const* r
     a.hidden = hidden;
     a.rank = r;
     a.ws = world_size;
-    a.one_shot = hpc_dev_tuning_get(52) == 1;   // development key 52 = 1: the one-shot form in the loopback grid
-    a.fuse_norm = hpc_dev_tuning_get(53) != 1;  // development key 53 = 1: the all-reduce alone (rmsnorm_fusion = false)
+    a.one_shot = hpc_dev_tuning_get(kDevArLlOneShot) == 1;   // development key kDevArLlOneShot = 1: the one-shot form in the loopback grid
+    a.fuse_norm = hpc_dev_tuning_get(kDevArLlNoNorm) != 1;  // development key kDevArLlNoNorm = 1: the all-reduce alone (rmsnorm_fusion = false)
     if (a.one_shot && workspace_bytes < 3l * num_tokens * world_size * hidden * 2) return HPC_ERR_INVALID;
   }
   const LlArgs* dev = loopback_args_on_device(host, world_size, stream);
   if (!dev) return HPC_ERR_LAUNCH;
   const dim3 g(num_tokens < 2048 ? num_tokens : 2048, world_size);
-  if (static_cast<int>(g.x * g.y) <= ll_fused_capacity(hidden > 4 * kThreads * 8, true) && hpc_dev_tuning_get(35) != 1) {
+  if (static_cast<int>(g.x * g.y) <= ll_fused_capacity(hidden > 4 * kThreads * 8, true) && hpc_dev_tuning_get(kDevArLlLaunches) != 1) {
     if (hidden <= 4 * kThreads * 8)
       ll_fused_loopback_kernel<4><<<g, kThreads, 0, stream>>>(dev);
     else

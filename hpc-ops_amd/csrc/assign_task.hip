@@ -247,7 +247,7 @@ extern "C" int hpc_attention_decode_num_bins(int num_seq_q, int device_id) {
   if (num_seq_q < 1 || num_seq_q > kMaxSeqQ) return HPC_ERR_INVALID;
   const int cus = hpc_get_cu_count(device_id);
   if (cus <= 0) return HPC_ERR_LAUNCH;
-  const int dev_bins = hpc_dev_tuning_get(34);  // development: bin count override (A/B of the bin size on small problems)
+  const int dev_bins = hpc_dev_tuning_get(kDevSchedBins);  // development: bin count override (A/B of the bin size on small problems)
   if (dev_bins > 0 && dev_bins <= 4 * cus) return dev_bins;
   return cus * cta_per_cu(num_seq_q);
 }

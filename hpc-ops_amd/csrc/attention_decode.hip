@@ -62,7 +62,7 @@ struct Args {
   const float* vscale;  // fp8: [1] or [Hkv]
   int num_batch, num_seq_q, num_head_kv, g_shift, page_shift, max_blocks;
   int ldq, ldy, qscale_stride;
-  int solo_ok;  // bins full of short tasks may run one task per wave (tuning key 5 = 1 turns it off)
+  int solo_ok;  // bins full of short tasks may run one task per wave (tuning key kDevDecodeNoWaveSolo = 1 turns it off)
   long k_block_stride, k_token_stride, k_head_stride;  // elements
   long v_block_stride, v_token_stride, v_head_stride;
   long ks_block_stride, ks_row_stride, ks_head_stride;  // bytes, per-token K scales
@@ -77,10 +77,6 @@ union Frag16 {
   u32x4 u;
   bf16x8 b;
 };
-
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
 
 // kQuant (fp8 only): 1 = q per-token/per-head, k/v per tensor; 0 = k per-token/per-head (scales in
 // the page tail rows), v per head.
@@ -703,7 +699,7 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(const Args a, 
 
 template <bool kFp8, int kQuant>
 int launch(const Args& a, int num_bins, int num_nb, hipStream_t stream) {
-  const bool temporal = hpc_dev_tuning_get(0) == 1;
+  const bool temporal = hpc_dev_tuning_get(kDevDecodeKvTemporal) == 1;
 #define HPC_DECODE_LAUNCH(NB)                                                                   \
   if (temporal)                                                                                 \
     decode_kernel<kFp8, kQuant, NB, 0><<<num_bins, kThreads, 0, stream>>>(a);                   \
@@ -774,8 +770,8 @@ inline Common fill_common(Args& a, void* y_ptr, void* workspace, const int* task
   a.task_map = task_map_ptr;
   a.y = static_cast<uint16_t*>(y_ptr);
   // the workspace starts with the arrival counters of split requests (zero-once region, shared with the second
-  // generation: one of the two runs per call); development key 33 = 1: the round-1 form (combine kernel)
-  a.arrive = static_cast<int64_t>(num_batch) * num_head_kv * 4 <= hpc::decode2::kCounterBytes && hpc_dev_tuning_get(33) != 1
+  // generation: one of the two runs per call); development key kDevDecodeCombineKernel = 1: the round-1 form (combine kernel)
+  a.arrive = static_cast<int64_t>(num_batch) * num_head_kv * 4 <= hpc::decode2::kCounterBytes && hpc_dev_tuning_get(kDevDecodeCombineKernel) != 1
                  ? static_cast<int*>(workspace) : nullptr;
   char* ws = static_cast<char*>(workspace) + hpc::decode2::kCounterBytes;
   a.part_o = reinterpret_cast<float*>(ws);
@@ -790,7 +786,7 @@ inline Common fill_common(Args& a, void* y_ptr, void* workspace, const int* task
   a.g_shift = group == 8 ? 3 : 2;
   a.page_shift = block_size == 64 ? 6 : (block_size == 32 ? 5 : 4);
   a.max_blocks = num_seq_max_blocks;
-  a.solo_ok = hpc_dev_tuning_get(5) != 1;
+  a.solo_ok = hpc_dev_tuning_get(kDevDecodeNoWaveSolo) != 1;
   a.ldq = ldQ;
   a.ldy = ldY;
   a.qscale_stride = 0;
@@ -863,16 +859,16 @@ static int try_second_generation(hpc::decode2::Args& b, void* workspace, int num
                                  int64_t v_head_stride_bytes, hipStream_t stream) {
   b.part_o = b.part_lse = nullptr;
   b.arrive = nullptr;
-  b.dev_nomem = hpc_dev_tuning_get(15);
-  b.min_range_cost = hpc_dev_tuning_get(20) > 0 ? hpc_dev_tuning_get(20) : 8;  // development key 20 overrides (15 x 64 + 1 x 16k tokens: 87 us without a floor, 47 / 49 / 61 / 105 us at 8 / 16 / 32 / 64)
+  b.dev_nomem = hpc_dev_tuning_get(kDevDecodeNoKvLoads);
+  b.min_range_cost = hpc_dev_tuning_get(kDevDecodeMinRangeCost) > 0 ? hpc_dev_tuning_get(kDevDecodeMinRangeCost) : 8;  // development key kDevDecodeMinRangeCost overrides (15 x 64 + 1 x 16k tokens: 87 us without a floor, 47 / 49 / 61 / 105 us at 8 / 16 / 32 / 64)
   b.prof = g_decode_prof;
-  if (hpc_dev_tuning_get(12) == 1) return 1;  // development key 12 = 1: first generation only
+  if (hpc_dev_tuning_get(kDevDecodeFp8NoPair) == 1) return 1;  // development key kDevDecodeFp8NoPair = 1: first generation only
   const int mode = hpc::decode2::mode_of(b, num_head_q, block_size, k_head_stride_bytes, v_head_stride_bytes);
   int dev = 0;
   if (mode == 0 || hipGetDevice(&dev) != hipSuccess) return 1;
   const int unit = mode == 3 ? num_head_kv : num_head_kv / (mode == 2 ? 4 : 2);  // workgroup = (token range, head pair, quad or head)
   int num_wg = 2 * hpc_get_cu_count(dev);  // two 4-wave workgroups per CU (<= 256 registers, 65 KB of LDS each)
-  const int wg_dev = hpc_dev_tuning_get(14);
+  const int wg_dev = hpc_dev_tuning_get(kDevDecodeGrid);
   if (wg_dev > 0) num_wg = wg_dev;
   if (num_wg > num_bins) num_wg = num_bins;  // the scratch is sized for num_bins workgroups
   num_wg -= num_wg % unit;
@@ -899,7 +895,7 @@ extern "C" int hpc_attention_decode_bf16_async(
                                kcache_head_stride, vcache_block_stride, vcache_token_stride,
                                vcache_head_stride, 8);
   if (c.code != HPC_OK) return c.code;
-  if (num_seq_kvcache_ptr && hpc_dev_tuning_get(28) != 1) {  // development key 28 = 1: bf16 on the first generation only
+  if (num_seq_kvcache_ptr && hpc_dev_tuning_get(kDevDecodeBf16NoPair) != 1) {  // development key kDevDecodeBf16NoPair = 1: bf16 on the first generation only
     hpc::decode2::Args b;
     b.q = q_ptr;
     b.kcache = kcache_ptr;
@@ -994,9 +990,9 @@ extern "C" int hpc_attention_decode_fp8_async(
     b.ks_row_stride = kscale_row_stride;
     b.ks_head_stride = kscale_head_stride;
     b.scale_log2 = a.scale_log2;
-    // quant_type 0 (per-token K scales, per-head V scales) runs there too since round 6 (development key 54 = 1: first generation)
+    // quant_type 0 (per-token K scales, per-head V scales) runs there too since round 6 (development key kDevDecodeQt0FirstGen = 1: first generation)
     b.ktok = quant_type == 0 ? 1 : 0;
-    if (quant_type == 1 || hpc_dev_tuning_get(54) != 1) {
+    if (quant_type == 1 || hpc_dev_tuning_get(kDevDecodeQt0FirstGen) != 1) {
       const int rc = try_second_generation(b, workspace, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, block_size,
                                            kcache_head_stride, vcache_head_stride, stream);
       if (rc <= 0) return rc;

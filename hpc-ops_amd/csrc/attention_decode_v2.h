@@ -28,14 +28,14 @@ struct Args {
   int ktok = 0;   // fp8: 1 = per-token K scales in the pages' tail rows (kscale + ks_* strides) and per-head V scales (quant_type 0)
   int pair_wgs[4];  // fp8, 4 head pairs: workgroups (= ranges) per pair, [0] = 0: equal shares
   int big_pct;      // > 100: ranges of the first half of the grid are this many percent of the others' length
-  int dev_nomem;  // development key 15 = 1: K / V loads fetch nothing (compute-only timing; results are wrong)
+  int dev_nomem;  // development key kDevDecodeNoKvLoads = 1: K / V loads fetch nothing (compute-only timing; results are wrong)
   int pair_xor;   // workgroups from mate_from on (the SECOND workgroup of every CU) serve head pair p ^ pair_xor: a CU's two
   int mate_from;  // workgroups stream slices of the token rows that differ in byte-address bit 9 (see the kernel); 0 = off
-  int xcd_map;    // development key 38: eight 3-bit entries, workgroup 8 j + x serves pair (e & 3) of range 2 j + (e >> 2), e = entry x
-  int dev_sleep;  // development key 39: workgroups of even head pairs sleep this many x 64 clocks per wave-iteration
-  int dev_merge_dup = 0;  // development key 58 = 1: the last arriver loads (and folds with weight zero) a duplicate for a missing second chunk
-  int dev_nosnap = 0;     // development key 61 = 1: short requests of an underloaded launch may be split (rounds 2-5)
-  int dev_slice;  // development key 37 = s + 1: every workgroup streams slice s of the token rows (timing only; results are wrong)
+  int xcd_map;    // development key kDevDecodeXcdMap: eight 3-bit entries, workgroup 8 j + x serves pair (e & 3) of range 2 j + (e >> 2), e = entry x
+  int dev_sleep;  // development key kDevDecodeSleep: workgroups of even head pairs sleep this many x 64 clocks per wave-iteration
+  int dev_merge_dup = 0;  // development key kDevDecodeMergeDup = 1: the last arriver loads (and folds with weight zero) a duplicate for a missing second chunk
+  int dev_nosnap = 0;     // development key kDevDecodeNoSnap = 1: short requests of an underloaded launch may be split (rounds 2-5)
+  int dev_slice;  // development key kDevDecodeOneSlice = s + 1: every workgroup streams slice s of the token rows (timing only; results are wrong)
   long k_block_stride, k_token_stride;  // bytes
   long v_block_stride, v_token_stride;
   long ks_block_stride, ks_row_stride, ks_head_stride;  // bytes
@@ -51,7 +51,7 @@ constexpr int64_t kCounterBytes = 64 * 1024;
 int64_t workspace_bytes(int num_wg);  // partial slots (2 per workgroup x 2 heads), after the first-generation region
 // 3: one kv head per workgroup (fp8, per-tensor scales, 17 ... 32 q rows per kv head, any page layout, pages of 32 / 64 tokens);
 // 0: not served here; 1: served (NHD pages with adjacent heads contiguous - 128 B apart for fp8, 256 B for bf16 -, or, fp8
-// with per-tensor scales and development key 55 = 1, HND pages with a head's tokens contiguous (a.hnd is set then); an even number of kv heads,
+// with per-tensor scales and development key kDevDecodeHndPair = 1, HND pages with a head's tokens contiguous (a.hnd is set then); an even number of kv heads,
 // <= 16 q rows per kv head, <= 1024 requests).
 int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int64_t v_head_stride);
 int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStream_t stream);

@@ -71,15 +71,6 @@ constexpr int kRow = 256;                             // LDS row: head 0 | head 
 constexpr int kRows = 32;                             // rows per wave-iteration
 constexpr int kVOff = kRows * kRow;                   // V half of a wave's stage
 constexpr int kWaveLds = 2 * kRows * kRow;            // 16 KB: K + V of one WI; the merge buffer s_o[2][16][128] aliases it
-typedef int v2i32 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) v2i32 lds_v2i32;
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // ---- loads the compiler does not see ---------------------------------------------------------------------------
 // hipcc's waitcnt insertion drained the whole queue once per wave-iteration in every compiler-visible form of this
@@ -89,17 +80,8 @@ __device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstla
 // vmcnt(number of loads issued after the ones it needs).  Stores and other compiler-visible memory operations in
 // the queue only make these waits conservative, never unsafe.  Destinations are "v" registers: the kernel stays
 // well below 256 registers, so hipcc has no reason to shuffle a not-yet-landed destination through an AGPR.
-__device__ __forceinline__ i32x4 srd(uint32_t lo, uint32_t hi, int num_records) {
-  return i32x4{sgpr(static_cast<int>(lo)), sgpr(static_cast<int>(hi)), sgpr(num_records), 0x00020000};
-}
-__device__ __forceinline__ i32x4 srd_of(const void* base, unsigned num_records) {
-  const uint64_t v = reinterpret_cast<uint64_t>(base);
-  return srd(static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32), static_cast<int>(num_records));
-}
 // every statement opens with s_nop 4: its SGPR operands may have been written by v_readfirstlane just before
-// (the descriptor is re-pinned word by word: an "s" operand must be provably wave-uniform or hipcc hands the
-// assembler a VGPR tuple)
-__device__ __forceinline__ i32x4 pin(i32x4 r) { return i32x4{sgpr(r[0]), sgpr(r[1]), sgpr(r[2]), sgpr(r[3])}; }
+// (the descriptor is re-pinned word by word, hpc_common.h::pin)
 template <int kAux>
 __device__ __forceinline__ void ld_x4x4(u32x4 (&k)[4], int voff, i32x4 rs_in, int s1, int s2, int s3) {
   const i32x4 rs = pin(rs_in);
@@ -159,25 +141,6 @@ __device__ __forceinline__ void wait_q(u32x4 (&q0)[2], u32x4 (&q1)[2], uint32_t&
   asm volatile("s_waitcnt vmcnt(%6)" : "+v"(q0[0]), "+v"(q0[1]), "+v"(q1[0]), "+v"(q1[1]), "+v"(s0), "+v"(s1) : "n"(N < 63 ? N : 63));
 }
 
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-// max over the 4 lanes that share a q row (lane, lane ^ 16, lane ^ 32, lane ^ 48) with the gfx950 row-swap
-// instructions instead of ds_bpermute (an LDS round trip on the critical path of every WI):
-// permlane16_swap(x, x) = {[x0 x0 x2 x2], [x1 x1 x3 x3]} by 16-lane rows, permlane32_swap(y, y) = {[y0 y1 y0 y1], [y2 y3 y2 y3]}
-__device__ __forceinline__ float row4_max(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float row4_sum(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-typedef const float __attribute__((address_space(4))) * cfloat_ptr;
-__device__ __forceinline__ cfloat_ptr as_constf(const float* p) { return (cfloat_ptr)(reinterpret_cast<uintptr_t>(p)); }
 
 // flag bits of a wave-iteration
 constexpr int kFValid = 1;    // inside this workgroup's range
@@ -209,7 +172,7 @@ constexpr int kFMasked = 32;  // some token of the WI is invisible to some q row
 //        buffer_load_dword per wave-iteration (lane = head * 32 + token), issued between the K and the V loads, staged
 //        through 256 bytes of LDS per wave, read back as the four tokens of a lane's score rows.  Scores are scaled
 //        (s * qscale / sqrt(d) * log2 e) * kscale[token] - the first-generation kernel's order.
-// kHnd:  fp8 head pairs on HND pages [page][head][token][128 B] (round 6, development key 55 = 1; the product keeps the first-generation kernel there).  A kv head's
+// kHnd:  fp8 head pairs on HND pages [page][head][token][128 B] (round 6, development key kDevDecodeHndPair = 1; the product keeps the first-generation kernel there).  A kv head's
 //        tokens are contiguous there, so a load instruction fetches 8 tokens x 128 B of ONE head (1 KB contiguous - the widest
 //        piece the probe knows, and no workgroup fixes byte-address bits 8-9) and a 16-row block is two instructions per head.
 //        Only the lane -> (row, chunk) map of the loads and of the stage writes differs: the LDS image, and with it everything
@@ -314,10 +277,10 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
   // byte offset differs in address bit 9 from the first one's, the whole launch runs 4-6 % faster (C3 mix 141 -> 133-137 us,
   // uniform 8k 180 -> 175 us, every box); mates on the same slice (today's kernel until round 5), slices that differ in bit 8, or
   // an XCD that serves all four slices are all slower.  Every workgroup that streams alone on a slice runs as fast as any
-  // other (development key 37), so this is not a property of the memory channels behind a slice.  Two more facts of the same
+  // other (development key kDevDecodeOneSlice), so this is not a property of the memory channels behind a slice.  Two more facts of the same
   // sweep that this mapping relies on: pair index bit 0 (= slice address bit 8 for fp8 pairs) is the PARITY of the XCD a
   // workgroup runs on (workgroups go round the 8 XCDs in index order) - every other assignment of slice bits to XCD index bits
-  // is 3 % slower (development key 38) -, and the even XCDs stream bit-8 = 0 addresses faster than anything else streams (call 28).
+  // is 3 % slower (development key kDevDecodeXcdMap) -, and the even XCDs stream bit-8 = 0 addresses faster than anything else streams (call 28).
   if (a.xcd_map != 0 && npair == 4 && (nwg & 7) == 0) {  // development: which XCD (= wg % 8) streams which slice
     const int e = (a.xcd_map >> (3 * (wg & 7))) & 7;
     pr = e & 3;
@@ -514,12 +477,12 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
   const uint64_t kbase_h = reinterpret_cast<uint64_t>(a.kcache) + static_cast<uint64_t>(mem_slice) * (kSolo ? static_cast<uint64_t>(a.k_head_stride) : kHnd ? 2 * static_cast<uint64_t>(a.k_head_stride) : kRowB);
   const uint64_t vbase_h = reinterpret_cast<uint64_t>(a.vcache) + static_cast<uint64_t>(mem_slice) * (kSolo ? static_cast<uint64_t>(a.v_head_stride) : kHnd ? 2 * static_cast<uint64_t>(a.v_head_stride) : kRowB);
   const uint32_t kbs = static_cast<uint32_t>(a.k_block_stride), vbs = static_cast<uint32_t>(a.v_block_stride);  // < 4 GB (eligible())
-  const bool mem = a.dev_nomem == 0;  // development key 15 = 1: K / V loads fetch nothing (compute-only timing)
+  const bool mem = a.dev_nomem == 0;  // development key kDevDecodeNoKvLoads = 1: K / V loads fetch nothing (compute-only timing)
   i32x4 dk0, dk1, dv0, dv1;  // descriptors of the WI being issued
   uint32_t ksr = 0;           // kKtok: the WI's 64 K scales in flight (lane = head * 32 + token)
   uint32_t ksr1 = 0;          // kKtok + kSolo: tokens 32 ... 63 of the one head (ksr: tokens 0 ... 31; lanes l and l + 32 hold the same)
-  i32x4 dks = i32x4{0, 0, 0, 0x00020000};
-  i32x4 dks1 = i32x4{0, 0, 0, 0x00020000};
+  i32x4 dks = i32x4{0, 0, 0, kSrdWord3};
+  i32x4 dks1 = i32x4{0, 0, 0, kSrdWord3};
   // K-scale tail row of the wave's WIs: they start at multiples of 32 tokens, so one row (tok / 32 within the page) and
   // one page hold a WI's scales (pages of 32 / 64 tokens: eligible()); the pair's two heads are 2 x 128 contiguous bytes
   // (one head per workgroup: the 64 tokens of a wave-iteration are two 128-byte pieces - tail rows in0 / 32 and in0 / 32 + 1 of the
@@ -536,8 +499,8 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
     dk0 = srd(static_cast<uint32_t>(ka), static_cast<uint32_t>(ka >> 32), nrec0);
     dv0 = srd(static_cast<uint32_t>(va), static_cast<uint32_t>(va >> 32), nrec0);
     if (blk1_same_page) {
-      dk1 = i32x4{dk0[0], dk0[1], sgpr(nrec1), 0x00020000};
-      dv1 = i32x4{dv0[0], dv0[1], sgpr(nrec1), 0x00020000};
+      dk1 = i32x4{dk0[0], dk0[1], sgpr(nrec1), kSrdWord3};
+      dv1 = i32x4{dv0[0], dv0[1], sgpr(nrec1), kSrdWord3};
     } else {
       const uint64_t kb = kbase_h + static_cast<uint64_t>(static_cast<uint32_t>(pid1)) * kbs;
       const uint64_t vb = vbase_h + static_cast<uint64_t>(static_cast<uint32_t>(pid1)) * vbs;
@@ -768,7 +731,7 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
         for (int u = 0; u < 2; ++u) {
           // (round 6: a second chunk that does not exist is neither loaded nor folded - rounds 3-5 loaded the first one again
           // and gave it weight zero; most split requests have two or three chunks, and a duplicate of a written-through partial
-          // is one more trip past L2 at the very end of the launch.  Development key 58 = 1: the duplicate loads.)
+          // is one more trip past L2 at the very end of the launch.  Development key kDevDecodeMergeDup = 1: the duplicate loads.)
           const int c = c0 + u * kWaves < nchunks ? c0 + u * kWaves : c0;
           if (u > 0 && c0 + u * kWaves >= nchunks && !(kHpcDevBuild && a.dev_merge_dup)) continue;  // wave-uniform
 #pragma unroll
@@ -1039,7 +1002,7 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
     // (round 5: s_setprio 2 around this load issue, around the whole memory phase of a wave-iteration, or s_setprio 1
     //  around its compute phase change nothing - C3 mix 140.1-141.0 us against 140.3-141.9 us, uniform 8k 185.3-185.6
     //  against 180.2-185.5 us, profiles/round5_decode_ab.txt: the waves wait for the memory pipeline, not for issue slots)
-    if constexpr (kHpcDevBuild) {  // development key 39: (in front of the load issue) throttle the workgroups of the even head pairs (the fast slices)
+    if constexpr (kHpcDevBuild) {  // development key kDevDecodeSleep: (in front of the load issue) throttle the workgroups of the even head pairs (the fast slices)
       if (a.dev_sleep > 0 && !(pr & 1))
         for (int i = 0; i < a.dev_sleep; ++i) __builtin_amdgcn_s_sleep(1);
     }
@@ -1519,7 +1482,7 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
   if (a.num_head_kv <= 0 || num_head_q % a.num_head_kv) return 0;
   const int group = num_head_q / a.num_head_kv;
   const int head_bytes = a.bf16 ? 256 : 128;  // strides in BYTES: adjacent kv heads of a token must be contiguous (NHD pages)
-  // ... or (fp8, per-tensor scales) a head's tokens: HND pages - development key 55 = 1 only.  Measured (profiles/round6_decode_ab.txt,
+  // ... or (fp8, per-tensor scales) a head's tokens: HND pages - development key kDevDecodeHndPair = 1 only.  Measured (profiles/round6_decode_ab.txt,
   // call 3): against the first-generation kernel the HND form wins on length mixes (C3 mix 137.3 vs 141.2 us, 32 x 128 + 32 x 4k
   // 57.8 vs 60.6) and loses where the task map gives every workgroup one whole (request, head) and this kernel's plan cuts every
   // request in two (uniform 8k: 181.7 us = 0.74 against 164-178 us = 0.75-0.82) - and 1 KB contiguous pieces stream no faster
@@ -1532,11 +1495,11 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
   // Any head / token strides (NHD and HND pages), any head count, pages of 32 / 64 tokens.  Measured against the first generation's
   // two-block form (profiles/round6_decode_ab.txt, call 8; C3 lengths, us): num_seq_q 3, 8 / 64 heads NHD mix 195.6 -> 163.8,
   // uniform 8k 220 -> 196; HND 193 -> 150 / 218 -> 180; num_seq_q 4: 4 / 32 heads 112 -> 87.5 / 112 -> 95, 1 / 8 heads 49.5 -> 41.4.
-  // Development key 60: 1 = never (rounds 1-5), 2 = also every other fp8 call with per-tensor scales that the pair form does not
+  // Development key kDevDecodeSoloForm: 1 = never (rounds 1-5), 2 = also every other fp8 call with per-tensor scales that the pair form does not
   // take (<= 16 q rows on HND pages or with an odd head count) - there the first generation stays ahead (one kv head, 8 q rows:
   // 31 against 38-40 us; HND mix 138 / 139, 32 x 128 + 32 x 4k 63 against 71 us).
   {
-    const int rows = a.num_seq_q * group, k60 = hpc_dev_tuning_get(60);
+    const int rows = a.num_seq_q * group, k60 = hpc_dev_tuning_get(kDevDecodeSoloForm);
     const bool pair_case = (a.num_head_kv % 2) == 0 && rows <= 16 && k_head_stride == head_bytes && v_head_stride == head_bytes &&
                            (!a.ktok || a.ks_head_stride == 128);
     const bool ks_ok = !a.ktok || (a.ks_block_stride > 0 && a.ks_block_stride < (1ll << 32) && (a.ks_row_stride % 4) == 0 &&
@@ -1552,7 +1515,7 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
   }
   const bool hnd = !a.bf16 && !a.ktok && a.k_token_stride == 128 && a.v_token_stride == 128 && k_head_stride >= 128 * block_size &&
                    v_head_stride >= 128 * block_size && (k_head_stride % 16) == 0 && (v_head_stride % 16) == 0 &&
-                   k_head_stride < (1ll << 28) && v_head_stride < (1ll << 28) && a.num_head_kv > 1 && hpc_dev_tuning_get(55) == 1;
+                   k_head_stride < (1ll << 28) && v_head_stride < (1ll << 28) && a.num_head_kv > 1 && hpc_dev_tuning_get(kDevDecodeHndPair) == 1;
   if (hnd) {
     a.hnd = 1;
     k_head_stride = v_head_stride = head_bytes;  // the checks below are the NHD form's
@@ -1577,8 +1540,8 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
   // 3-5 % SLOWER than head pairs on the graded shapes (uniform 8k 188.8 vs 183.0 us, C3 mix 145.4 vs 138.6 us, same box,
   // profiles/round3_decode_fp8_forms_ab.txt): the wider rows do not pay in the kernel although they do in a pure streaming
   // probe - the waves sit in the load issue either way (tools/prof_decode.py: 52-57 % of a wave's cycles).  So head
-  // pairs stay the default and development key 29 = 2 selects the four-head form (kept: tested, half the softmax work).
-  const bool quad = !a.bf16 && !a.hnd && (a.num_head_kv % 4) == 0 && a.num_seq_q * group <= 8 && hpc_dev_tuning_get(29) == 2;
+  // pairs stay the default and development key kDevDecodeQuadForm = 2 selects the four-head form (kept: tested, half the softmax work).
+  const bool quad = !a.bf16 && !a.hnd && (a.num_head_kv % 4) == 0 && a.num_seq_q * group <= 8 && hpc_dev_tuning_get(kDevDecodeQuadForm) == 2;
   return quad ? 2 : 1;
 }
 
@@ -1592,23 +1555,35 @@ int ticket_overruns(bool reset) {
 }
 #endif
 
+namespace {
+// After the kernel launch of launch().  The contract of the counter region is "zero on entry, zero on exit": a launch that
+// was refused leaves it as it found it, but the caller cannot tell a refused launch from one that died half way - restore
+// the invariant in stream order before reporting (best effort: the stream may be beyond repair).
+int launch_status(void* counters, hipStream_t stream) {
+  if (hipGetLastError() == hipSuccess) return HPC_OK;
+  (void)hipMemsetAsync(counters, 0, kCounterBytes, stream);
+  (void)hipGetLastError();
+  return HPC_ERR_LAUNCH;
+}
+}  // namespace
+
 int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStream_t stream) {
+  int dev = 0;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
   char* ws = static_cast<char*>(partials);
   a.part_o = reinterpret_cast<float*>(ws);
   ws += static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 128 * 4;
   a.part_lse = reinterpret_cast<float*>(ws);
   a.arrive = static_cast<int*>(counters);
-  const bool temporal = hpc_dev_tuning_get(0) == 1;
+  const bool temporal = hpc_dev_tuning_get(kDevDecodeKvTemporal) == 1;
   if (mode == 3) {  // one kv head per workgroup
     a.dev_slice = a.xcd_map = a.dev_sleep = 0;
     a.pair_xor = a.mate_from = 0;
     a.pair_wgs[0] = a.pair_wgs[1] = a.pair_wgs[2] = a.pair_wgs[3] = 0;
     a.big_pct = 100;
     {  // the pair form's CU-mate rule (a CU's two workgroups on slices across an address bit) makes no difference here - masks 1, 2,
-       // 4, 6 on 8 heads: C3 mix 160.6-164.3 us with and without, call 8 - so it is off; development key 36 = mask + 1 switches it on
-      int dev = 0;
-      const int cus = hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-      const int k36 = hpc_dev_tuning_get(36);
+       // 4, 6 on 8 heads: C3 mix 160.6-164.3 us with and without, call 8 - so it is off; development key kDevDecodePairSwizzle = mask + 1 switches it on
+      const int k36 = hpc_dev_tuning_get(kDevDecodePairSwizzle);
       const int mask = k36 > 0 ? k36 - 1 : 0;
       const int np = a.num_head_kv;
       if (cus > 0 && num_wg > cus && (np & (np - 1)) == 0 && mask > 0 && mask < np && cus % np == 0) {
@@ -1624,29 +1599,22 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
       decode2_kernel<2, false, true, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
     else
       decode2_kernel<2, false, false, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    if (hipGetLastError() != hipSuccess) {
-      (void)hipMemsetAsync(counters, 0, kCounterBytes, stream);
-      (void)hipGetLastError();
-      return HPC_ERR_LAUNCH;
-    }
-    return HPC_OK;
+    return launch_status(counters, stream);
   }
-  a.dev_slice = hpc_dev_tuning_get(37);
-  a.xcd_map = hpc_dev_tuning_get(38);
-  a.dev_sleep = hpc_dev_tuning_get(39);
-  a.dev_merge_dup = hpc_dev_tuning_get(58) == 1;
-  a.dev_nosnap = hpc_dev_tuning_get(61) == 1;
+  a.dev_slice = hpc_dev_tuning_get(kDevDecodeOneSlice);
+  a.xcd_map = hpc_dev_tuning_get(kDevDecodeXcdMap);
+  a.dev_sleep = hpc_dev_tuning_get(kDevDecodeSleep);
+  a.dev_merge_dup = hpc_dev_tuning_get(kDevDecodeMergeDup) == 1;
+  a.dev_nosnap = hpc_dev_tuning_get(kDevDecodeNoSnap) == 1;
   // the second workgroup of every CU on the slice across address bit 9 (see the kernel): slices of 256 B (fp8 pairs) -> pair
   // index bit 1, of 512 B (bf16 pairs, fp8 quads) -> bit 0.  Measured per shape (profiles/round5_decode_pair_map_ab.txt):
   // fp8 8 / 64 heads +4-6 %, 16 / 128 heads +4 % (bit 8: +2 %, bit 10: 0), bf16 8 / 64 +1-2.5 % (bit 10: 0); with two pairs
   // (4 kv heads, fp8) only bit 8 exists: +2 % on the length mix, +-1 % on uniform lengths - taken.  Needs a power-of-two pair
   // count that holds the bit, more than one workgroup per CU, whole rows of pairs in front of the second workgroups, equal
-  // shares.  Development key 36 = mask + 1 overrides the mask (1 = off: both workgroups of a CU on the same slice).
+  // shares.  Development key kDevDecodePairSwizzle = mask + 1 overrides the mask (1 = off: both workgroups of a CU on the same slice).
   {
-    int dev = 0;
     const int npair = a.num_head_kv / (mode == 2 ? 4 : 2);
-    const int cus = hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-    const int k36 = hpc_dev_tuning_get(36);
+    const int k36 = hpc_dev_tuning_get(kDevDecodePairSwizzle);
     int mask = (a.bf16 || mode == 2 || npair == 2) ? 1 : 2;
     if (k36 > 0) mask = k36 - 1;
     // (HND pages: a workgroup walks whole 1 KB pieces of a head - no slice fixes address bits 8-9, the rule has nothing to separate)
@@ -1658,10 +1626,10 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
   // Unequal shares for the four 256-byte slices of an 8-kv-head fp8 row (see the kernel): slice 1 gets d1 more
   // workgroups than the even share, slice 3 d3, slices 0 and 2 give them up.  Off by default: measured +3 % on the C3 mix
   // at d1 = 12 of 128 and nothing on uniform 8k (where the even split puts exactly one request half on every
-  // workgroup); development keys 30 / 31 set the deltas (value - 100, per 128 workgroups of a slice).
+  // workgroup); development keys kDevDecodeExtraWg256 / kDevDecodeExtraWg768 set the deltas (value - 100, per 128 workgroups of a slice).
   a.pair_wgs[0] = a.pair_wgs[1] = a.pair_wgs[2] = a.pair_wgs[3] = 0;
   if (!a.bf16 && mode == 1 && a.num_head_kv == 8 && num_wg >= 256 && num_wg % 4 == 0) {
-    const int k30 = hpc_dev_tuning_get(30), k31 = hpc_dev_tuning_get(31);
+    const int k30 = hpc_dev_tuning_get(kDevDecodeExtraWg256), k31 = hpc_dev_tuning_get(kDevDecodeExtraWg768);
     const int even = num_wg / 4;
     int d1 = (k30 != 0 ? k30 - 100 : 0) * even / 128, d3 = (k31 != 0 ? k31 - 100 : 0) * even / 128;
     if (d1 != 0 || d3 != 0) {
@@ -1671,15 +1639,14 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
   }
   if (a.pair_wgs[0] > 0) a.pair_xor = a.mate_from = 0;  // unequal shares (development) re-map the tail of the grid themselves (both together: measured worse)
   // longer ranges for the first workgroup of every CU (see the kernel): only when the grid is exactly two workgroups
-  // per CU, so that "first half of the grid" means "first on its CU".  Development key 32: percentage (0 = off).
+  // per CU, so that "first half of the grid" means "first on its CU".  Development key kDevDecodeFirstHalfPct: percentage (0 = off).
   // Measured: no gain at 108 / 115 / 122 % (C3 mix 139.7 / 139.0 / 138.4 us vs 139.3 us) - when a CU's first workgroup
   // ends early its second one speeds up, and the chip's aggregate rate does not change: the spread of finish times
   // (first halves 119-143 us, second halves 142-169 us on uniform 8k) is not where the time goes.  Off.
   {
-    int dev = 0;
-    const int k32 = hpc_dev_tuning_get(32);
+    const int k32 = hpc_dev_tuning_get(kDevDecodeFirstHalfPct);
     a.big_pct = 100;
-    if (k32 > 100 && k32 <= 200 && hipGetDevice(&dev) == hipSuccess && num_wg == 2 * hpc_get_cu_count(dev) &&
+    if (k32 > 100 && k32 <= 200 && cus > 0 && num_wg == 2 * cus &&
         (num_wg / 2) % (a.num_head_kv / (mode == 2 ? 4 : 2)) == 0)
       a.big_pct = k32;
   }
@@ -1709,15 +1676,7 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
   } else {
     decode2_kernel<2><<<num_wg, kThreads, 0, stream>>>(a);
   }
-  if (hipGetLastError() != hipSuccess) {
-    // the contract of the counter region is "zero on entry, zero on exit": a launch that was refused leaves it as it
-    // found it, but the caller cannot tell a refused launch from one that died half way - restore the invariant in
-    // stream order before reporting (best effort: the stream may be beyond repair)
-    (void)hipMemsetAsync(counters, 0, kCounterBytes, stream);
-    (void)hipGetLastError();
-    return HPC_ERR_LAUNCH;
-  }
-  return HPC_OK;
+  return launch_status(counters, stream);
 }
 
 }  // namespace decode2

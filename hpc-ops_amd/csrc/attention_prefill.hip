@@ -51,11 +51,6 @@ constexpr int kKRow = 128 + 16;  // padded LDS row of the K transpose tile
 constexpr int kMaskCols = 512;    // block-sparse: mask columns (128-token tiles) cached per head
 
 // ---- loads the compiler does not see (hand-counted vmcnt, as in attention_decode_v2.hip) ---------------------------
-__device__ __forceinline__ i32x4 srd_of(const void* base) {  // every word pinned: an "s" operand must be provably uniform
-  const uint64_t v = reinterpret_cast<uint64_t>(base);
-  return i32x4{__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(v))),
-               __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(v >> 32))), -1, 0x00020000};
-}
 __device__ __forceinline__ void ld_pair(u32x4& x0, u32x4& x1, int voff, i32x4 rs, int soff1) {
   const int s1 = __builtin_amdgcn_readfirstlane(soff1);
   asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %2, %3, 0 offen\n\tbuffer_load_dwordx4 %1, %2, %3, %4 offen"
@@ -69,32 +64,6 @@ __device__ __forceinline__ void ld_one(float& x, int voff, i32x4 rs) {
 template <int kLeft>
 __device__ __forceinline__ void wait_set(u32x4 (&k)[2], u32x4 (&v)[2], float& ks) {
   asm volatile("s_waitcnt vmcnt(%5)" : "+v"(k[0]), "+v"(k[1]), "+v"(v[0]), "+v"(v[1]), "+v"(ks) : "n"(kLeft));
-}
-
-template <int kN>
-struct IntC {
-  static constexpr int value = kN;
-};
-typedef int v2i32 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) v2i32 lds_v2i32;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-// max / sum over the 4 lanes that share a q row (lane, lane ^ 16, lane ^ 32, lane ^ 48): gfx950 row swaps,
-// permlane16_swap(x, x) = {[x0 x0 x2 x2], [x1 x1 x3 x3]} by 16-lane rows, permlane32_swap(y, y) = {[y0 y1 y0 y1], [y2 y3 y2 y3]}
-__device__ __forceinline__ float row4_max(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float row4_sum(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
 }
 
 // kQuant 1: q per token / per head, k and v per tensor.  kQuant 0: k per token / per head (scales in
@@ -552,8 +521,8 @@ static int prefill_fp8_launch(const void* block_mask_ptr, int mask_tiles_m, int 
   a.vscale = static_cast<const float*>(vscale_ptr);
   a.block_mask = static_cast<const uint8_t*>(block_mask_ptr);
   // head-major 16-row blocks let a block skip masked-out tiles (block-sparse); dense attention measured ~8 %
-  // faster with every wave holding all G heads of a few positions (key 7 overrides: 1 = by head, 2 = by position)
-  a.by_head = group <= 8 && (hpc_dev_tuning_get(7) ? hpc_dev_tuning_get(7) == 1 : block_mask_ptr != nullptr);
+  // faster with every wave holding all G heads of a few positions (key kDevPrefillRowMap overrides: 1 = by head, 2 = by position)
+  a.by_head = group <= 8 && (hpc_dev_tuning_get(kDevPrefillRowMap) ? hpc_dev_tuning_get(kDevPrefillRowMap) == 1 : block_mask_ptr != nullptr);
   a.mask_tiles_m = mask_tiles_m;
   a.mask_tiles_kv = mask_tiles_kv;
   if (block_mask_ptr && (mask_tiles_m <= 0 || mask_tiles_kv <= 0)) return HPC_ERR_INVALID;

@@ -47,35 +47,12 @@ constexpr int kVTileBytes = 64 * 256;       // one V tile: unpadded 256-byte row
 constexpr int kStageBytes = 4 * kTileBytes;  // K, V x 2 buffers (the padded V form of rounds 3-4 is the larger one)
 constexpr int kEpiBytes = kWaves * 16 * (128 + 4) * 4 + kWaves * 16 * 4;
 
-// max / sum over the 4 lanes that share a q row (lane, lane ^ 16, lane ^ 32, lane ^ 48) with the gfx950 row swaps
-// (no LDS round trip): permlane16_swap(x, x) = {[x0 x0 x2 x2], [x1 x1 x3 x3]}, permlane32_swap(y, y) = {[y0 y1 y0 y1], [y2 y3 y2 y3]}
-__device__ __forceinline__ float row4_max(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float row4_sum(float x) {
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  const float y = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-template <int kN>
-struct IntC {
-  static constexpr int value = kN;
-};
-
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-
 union Frag16 {
   u32x4 u;
   bf16x8 b;
 };
 
-// kTr: V^T operands through the transposing LDS read (round 5); false: the v_perm_b32 form of rounds 3-4 (development key 46 = 1)
+// kTr: V^T operands through the transposing LDS read (round 5); false: the v_perm_b32 form of rounds 3-4 (development key kDevPrefillBf16Perm = 1)
 template <bool kTr>
 __global__ __launch_bounds__(kThreads, 2) void prefill_bf16_kernel(const Args a) {
   constexpr int kVStride = kTr ? 256 : kKRow, kVBuf = kTr ? kVTileBytes : kTileBytes;
@@ -404,7 +381,7 @@ int launch_prefill_bf16(hpc::prefill16::Args& a, int max_seqlens_q, int num_head
   const long rows = static_cast<long>(max_seqlens_q) * group;
   dim3 grid(static_cast<unsigned>((rows + kWaves * kRowsPerWave - 1) / (kWaves * kRowsPerWave)), num_head_kv, num_batch);
   if (grid.z > 65535 || grid.y > 65535) return HPC_ERR_UNSUPPORTED;
-  if (kHpcDevBuild && hpc_dev_tuning_get(46) == 1)  // development key 46 = 1: V^T operands built with v_perm_b32 (rounds 3-4)
+  if (kHpcDevBuild && hpc_dev_tuning_get(kDevPrefillBf16Perm) == 1)  // development key kDevPrefillBf16Perm = 1: V^T operands built with v_perm_b32 (rounds 3-4)
     prefill_bf16_kernel<false><<<grid, kThreads, 0, stream>>>(a);
   else
     prefill_bf16_kernel<true><<<grid, kThreads, 0, stream>>>(a);

@@ -48,16 +48,6 @@ namespace moe {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ int block_sum(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 // Four consecutive routed ids starting at i (all inside the array).  kVec = the id array is 16-byte aligned: one
 // 16-byte load; otherwise four 4-byte loads.  No branch on the data path: the loops below keep several of these in flight.
 template <bool kVec>
@@ -746,8 +736,8 @@ extern "C" int hpc_fuse_moe_blockwise_async(
   if (rc) return rc;
   // gate_up: rows come straight from x through row_index, scales from x_scale[token][kb].  With the 256 x 256 tile
   // kernel the activation + quantisation runs in the GEMM's epilogue (a tile = 128 gate rows + the 128 up rows of
-  // the same columns) and the bf16 gate-up matrix is never written (development key 19 = 1: keep them apart)
-  if ((inter & 127) == 0 && hpc_dev_tuning_get(19) != 1 &&
+  // the same columns) and the bf16 gate-up matrix is never written (development key kDevMoeSplitAct = 1: keep them apart)
+  if ((inter & 127) == 0 && hpc_dev_tuning_get(kDevMoeSplitAct) != 1 &&
       hpc_ggemm_p8_selected(num_expert, m, intermediate_size2, hidden_size, ws + w.cu_tiles)) {
     rc = hpc_group_gemm_blockwise_fp8_act(ws + w.down_in, ws + w.down_in_scale, x_ptr, gate_up_weight_ptr,
                                           ws + w.seqlens, ws + w.cu_seqlens, x_scale_ptr, gate_up_weight_scale_ptr,
@@ -803,7 +793,7 @@ extern "C" int hpc_fuse_moe_pertensor_async(
   // With the 256 x 256 tile kernel the activation + quantisation runs in the gate-up GEMM's epilogue (a tile = 128
   // gate rows + the 128 up rows of the same columns): the bf16 gate-up matrix is never written (development key
   // 19 = 1 keeps the two kernels apart)
-  if ((inter & 127) == 0 && (hidden_size & 127) == 0 && hpc_dev_tuning_get(19) != 1 &&
+  if ((inter & 127) == 0 && (hidden_size & 127) == 0 && hpc_dev_tuning_get(kDevMoeSplitAct) != 1 &&
       hpc_ggemm_p8_selected(num_expert, m, intermediate_size2, hidden_size, ws + w.cu_tiles)) {
     rc = hpc_group_gemm_pertensor_fp8_act(ws + w.down_in, x_ptr, gate_up_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens,
                                           gate_up_scale_ptr, ws + w.row_index, act_and_mul_scale_ptr, use_bf16_mul,

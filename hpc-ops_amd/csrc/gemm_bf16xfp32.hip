@@ -11,7 +11,7 @@
 // the activations fetched straight into MFMA operand layout (v_mfma_f32_16x16x32_bf16: lane (r, g) holds 8
 // consecutive k of row r), 64 k per step, register double-buffered; larger m runs on the LDS-staged tile kernel
 // (64 weight rows x 128 tokens, every operand read once per workgroup as full lines; round 5 - the 64 x 64
-// direct-load kernel of rounds 1-4 stays behind development key 40 as the A/B partner).  Split-K partials
+// direct-load kernel of rounds 1-4 stays behind development key kDevRouterGemm64 as the A/B partner).  Split-K partials
 // go to an fp32 workspace; the last workgroup to arrive at a tile (device-scope counter) sums the
 // splits in fixed order - deterministic - writes y and leaves the counter at zero for the next call
 // (same contract as the reference's split_flag).
@@ -32,7 +32,7 @@ struct Args {
   float* split_y;  // [S, m, n] fp32 (S > 1)
   int* flag;       // per-tile arrival counters, row stride flag_ld (S > 1)
   int m, n, k, splits, flag_ld, fp32_out;
-  int dev_skip;  // development key 41: bit 0 = no weight loads, bit 1 = no activation loads in the tile kernel (timing only)
+  int dev_skip;  // development key kDevRouterGemmSkipLoads: bit 0 = no weight loads, bit 1 = no activation loads in the tile kernel (timing only)
   float scale;
 };
 
@@ -245,9 +245,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bf16xfp32_tile_kernel(const 
   auto load = [&](int rb, int c) {
     const bool on = c < c_end;
     const int koff = on ? c * 128 : 0;
-    const bool mem_w = on && !(a.dev_skip & 1);  // development key 41 bit 0: no weight loads (timing only)
+    const bool mem_w = on && !(a.dev_skip & 1);  // development key kDevRouterGemmSkipLoads bit 0: no weight loads (timing only)
     const auto rh_ = make_rsrc(a.wh, mem_w ? w_bytes : 0u), rl_ = make_rsrc(a.wl, mem_w ? w_bytes : 0u);
-    const auto rx_ = make_rsrc(a.x, on && !(a.dev_skip & 2) ? x_bytes : 0u);  // development key 41 bit 1: no activation loads
+    const auto rx_ = make_rsrc(a.x, on && !(a.dev_skip & 2) ? x_bytes : 0u);  // development key kDevRouterGemmSkipLoads bit 1: no activation loads
 #pragma unroll
     for (int q = 0; q < 4; ++q) xr[rb][q] = buf_ld16<0>(rx_, xg_off[q], koff);
 #pragma unroll
@@ -527,8 +527,8 @@ extern "C" int hpc_gemm_bf16xfp32_splits(int m, int n, int k, int use_splitk) {
   // m = 1024 29.2 us with 16 splits, 19.9 with 8 - profiles/round5_router_tile_ab.txt); a launch that has between one and two
   // workgroups per CU without splitting is split once more (two resident workgroups per CU overlap each other's load phases).
   const long tiles = static_cast<long>((m + 127) / 128) * (n / 64);
-  // development key 45: cap on the split count above m = 256 (never above the 16 planes the reduce sums)
-  const int cap = hpc_dev_tuning_get(45) > 0 ? (hpc_dev_tuning_get(45) < 16 ? hpc_dev_tuning_get(45) : 16) : 8;
+  // development key kDevRouterGemmSplitCap: cap on the split count above m = 256 (never above the 16 planes the reduce sums)
+  const int cap = hpc_dev_tuning_get(kDevRouterGemmSplitCap) > 0 ? (hpc_dev_tuning_get(kDevRouterGemmSplitCap) < 16 ? hpc_dev_tuning_get(kDevRouterGemmSplitCap) : 16) : 8;
   while (s < cap && tiles * s < cus && k / (s * 2) >= 256) s *= 2;
   if (tiles >= cus && tiles < 2 * cus && s == 1 && k >= 512) s = 2;
   return s;
@@ -564,7 +564,7 @@ extern "C" int hpc_gemm_bf16xfp32_async(void* y_ptr, void* splitk_y_ptr, void* s
   a.flag_ld = flag_ld;
   a.fp32_out = use_fp32_output;
   a.scale = scale;
-  a.dev_skip = hpc_dev_tuning_get(41);
+  a.dev_skip = hpc_dev_tuning_get(kDevRouterGemmSkipLoads);
   if (m <= kSkinnyMaxM) {
     const int tm = skinny_tm(m);
     dim3 grid(n / 16, (m + tm - 1) / tm, splits);
@@ -581,10 +581,10 @@ extern "C" int hpc_gemm_bf16xfp32_async(void* y_ptr, void* splitk_y_ptr, void* s
   if (splits > 1 && flag_ld < n / 64) return HPC_ERR_INVALID;
   // Measured (profiles/round5_router_tile_ab.txt; n = 256, k = 4096 unless said, old -> new): m = 4096 94.7 -> 29.0 us, m = 1024
   // 32.5 -> 20.1, m = 304 23.6 -> 18.2, m = 8192 x k = 7168 304 -> 77.5 us (0.78 PFLOP/s), m = 16384 x n = 128 180 -> 51.5 us.  What is
-  // left (timing-only variants, development key 41): the loop with no loads at all takes 62 of the 77.5 us (eight 16-byte LDS
+  // left (timing-only variants, development key kDevRouterGemmSkipLoads): the loop with no loads at all takes 62 of the 77.5 us (eight 16-byte LDS
   // stores + sixteen operand reads per wave for 32 MFMAs, one barrier per step), and below m ~ 1024 the call is its fixed
   // cost (launch, eight steps, split hand-off: 18-19 us).
-  if (hpc_dev_tuning_get(40) == 1) {  // development key 40 = 1: the 64 x 64 kernel of rounds 1-4 (operands straight from memory)
+  if (hpc_dev_tuning_get(kDevRouterGemm64) == 1) {  // development key kDevRouterGemm64 = 1: the 64 x 64 kernel of rounds 1-4 (operands straight from memory)
     dim3 grid(n / 64, (m + 63) / 64, splits);
     if (grid.y > 65535) return HPC_ERR_UNSUPPORTED;
     gemm_bf16xfp32_kernel<4><<<grid, kThreads, 0, stream>>>(a);

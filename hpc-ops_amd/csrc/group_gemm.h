@@ -1,5 +1,6 @@
-// Shared argument block of the grouped FP8 GEMM kernels (streaming form: group_gemm_blockwise.hip,
-// tiled form: group_gemm_tiled.hip).
+// Shared argument block of the grouped FP8 GEMM kernels: the streaming form and the entry points that fill the block
+// (group_gemm_blockwise.hip), the 128 x 128 and 256 x 128 tiled forms (group_gemm_tiled.hip, group_gemm_tiled256.hip) and
+// the 256 x 256 tile kernel (group_gemm_p8.hip).
 #pragma once
 #include <stdint.h>
 
@@ -30,10 +31,10 @@ struct Args {
   // the bf16-rounded multiply of the reference when use_bf16_mul (reference src/activation/activation.cu:19-75)
   const float* act_mul_scale = nullptr;
   int use_bf16_mul = 0;
-  int no_half_tile = 0;  // development (key 21): 1 = the 256 x 256 kernel runs its full body only, 2 = no tail body (<= 64 rows)
+  int no_half_tile = 0;  // development (key kDevP8NoHalfTile): 1 = the 256 x 256 kernel runs its full body only, 2 = no tail body (<= 64 rows)
   int nt_single = 1;     // 256 x 256 kernel, tail body: non-temporal weight loads for a group's ONLY (<= 64-row) token tile
-  int tail_regs = 0;     // development (key 26): 1 = the register-streamed tail body instead of the LDS-ring one
-  int item_scan_old = 0; // development (key 43): 1 = the item lookup's scans / lane reads through ds_bpermute (rounds 2-5) instead of DPP + v_readlane
+  int tail_regs = 0;     // development (key kDevP8TailRegs): 1 = the register-streamed tail body instead of the LDS-ring one
+  int item_scan_old = 0; // development (key kDevP8ItemScanOld): 1 = the item lookup's scans / lane reads through ds_bpermute (rounds 2-5) instead of DPP + v_readlane
   int ext_rows = 0;      // 256 x 256 kernel: 1 = a group's short tail rides along with its full tiles (group_gemm_p8.hip::locate_item)
   int item_order = 0;    // 256 x 256 kernel: 0 = tail tiles in place, 1 = full tiles first, tail tiles last (group_gemm_p8.hip::locate_item)
   void* prof = nullptr;  // development: s_memtime log of the 256 x 256 kernel's section boundaries (hpc_dev_p8_prof_buffer)

@@ -30,10 +30,6 @@ constexpr int kThreads = 256;
 // stages in flight per wave (template kDepth, default 4); one stage = 2 k-blocks = 256 B per weight row
 constexpr int kXRow = 272;    // LDS bytes per staged activation row (256 + 16: conflict-free b128 reads)
 
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-
 // kMT = token blocks of 16 served per pass over the weights (1, 2 or 4); kR = 16-row weight blocks
 // per wave (1 or 2): the workgroup tile is 64*kR rows.
 //
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(64 * kWaves, (kWaves == 8 || kMT * kR >= 8) ? 1 : 2
 //    scales ride in the same LDS read batch as the B operands;
 //  * the token-scale load uses a wave-uniform descriptor (the lane-dependent one above cost a waterfall loop per stage);
 //  * the weight loads of the first kDepth stages are issued before the lane's activation roles are known (see above).
-// Same arithmetic in the same order: bit-identical to the kernel above.  Development key 56 = 1 keeps that one.
+// Same arithmetic in the same order: bit-identical to the kernel above.  Development key kDevStreamGemmLoop = 1 keeps that one.
 //  * (kK128) a k-block is ONE v_mfma_f32_16x16x128_f8f6f4 per token block - the 256 x 256 kernel's instruction, operand
 //    convention (lane (r16, g4): chunks g4 and g4 + 4 of its row on both sides) and arithmetic: results are bit-identical to
 //    that kernel's bodies - instead of a chain of four dependent K = 32 MFMAs (kK128 = false: bit-identical to the kernel above).
@@ -477,16 +473,16 @@ __global__ __launch_bounds__(256, 2) void gemm_blockwise_stream2_kernel(const Ar
 }  // namespace hpc
 
 bool hpc_ggemm_p8_selected(int num_group, int m, int n, int k, const void* cu_tiles128) {
-  const int tiled_mode = hpc_dev_tuning_get(3);
+  const int tiled_mode = hpc_dev_tuning_get(kDevGgemmTiledMode);
   // (up to 64 groups the kernel finds its work item from one round of lane-parallel loads, above that from one round
   // per 64 groups: tests/test_fuse_moe_blockwise.py::test_group_gemm_blockwise_many_groups, 65 ... 256 groups)
   // From 16 rows per group on (round 5; rounds 2-4: from 192): with the carried tails, the tail body for <= 64 rows and the
   // half-tile body the 256 x 256 kernel overtakes the 256 x 128 ring kernel everywhere and the streaming kernel from
   // ~16 rows per group (fused MoE, E64 / top-8 / H4096 / I11008, us: T = 128 1554-1561 against 1564-1676, T = 256
   // 1590-1596 against 1711-1836, T = 512 1753-1755 against 1876-1978, T = 1024 2069-2102 against 2432-2607; below
-  // it loses: T = 64 1552-1563 against 1396-1461 - profiles/round5_moe_kernel_choice.txt).  Development key 25 restores
+  // it loses: T = 64 1552-1563 against 1396-1461 - profiles/round5_moe_kernel_choice.txt).  Development key kDevGgemmP8From192 restores
   // the old threshold.
-  const int p8_from = hpc_dev_tuning_get(25) == 1 ? 192 : 16;
+  const int p8_from = hpc_dev_tuning_get(kDevGgemmP8From192) == 1 ? 192 : 16;
   return cu_tiles128 && n % 256 == 0 && k >= 128 &&
          (tiled_mode == 4 || (tiled_mode == 0 && m / num_group >= p8_from));
 }
@@ -499,9 +495,9 @@ int launch_stream_gemm(hpc::ggemm::Args& a, int num_group, int m, int n, const v
   // kernel when n allows (one pass over the weights for up to 128 tokens, 100 KB in flight per CU without
   // staging registers; measured on E64 / top-8: T = 128 (16 per group) 1.61 vs 1.50 ms for the streaming form,
   // T = 192 1.63 vs 1.79, T = 256 1.73 vs 1.85, T = 384 1.75 ms), else the 128 x 128 register-staged one
-  // development key 3: 0 auto, 1 never tiled, 2 always 256 x 128 (when possible), 3 always 128 x 128,
+  // development key kDevGgemmTiledMode: 0 auto, 1 never tiled, 2 always 256 x 128 (when possible), 3 always 128 x 128,
   // 4 always 256 x 256 (when possible)
-  const int tiled_mode = hpc_dev_tuning_get(3);
+  const int tiled_mode = hpc_dev_tuning_get(kDevGgemmTiledMode);
   // the 256 x 256 kernel from 16 rows per group on (hpc_ggemm_p8_selected: tail body for <= 64 rows, half-tile body for <= 128)
   if (tiled_mode != 1 && hpc_ggemm_p8_selected(num_group, m, n, a.K, cu_tiles128))
     return hpc_ggemm_launch_p8(a, static_cast<const int*>(cu_tiles128), num_group, m, n, stream);
@@ -513,7 +509,7 @@ int launch_stream_gemm(hpc::ggemm::Args& a, int num_group, int m, int n, const v
   // tokens served per pass over the weights, from the average group size (the reference picks its
   // tileM the same way, fuse_moe/entry.cc:525-543); larger groups take several passes
   const int avg = m / num_group;
-  const int forced = hpc_dev_tuning_get(1);
+  const int forced = hpc_dev_tuning_get(kDevStreamGemmForm);
   // forced: 1 / 2 / 3 / 4 = tokens-per-pass 16 / 32 / 48 / 64 with 16 rows per wave; 8 = 64 tokens, 32 rows per
   // wave; 16 / 32 = 64 / 32 tokens with 8 waves per workgroup
   // measured on E64 / top-8: 16 tokens per pass up to ~10 per group, 32 up to ~22, then 48 (one pass still
@@ -530,7 +526,7 @@ int launch_stream_gemm(hpc::ggemm::Args& a, int num_group, int m, int n, const v
     gemm_blockwise_stream_kernel<2, 1, 8><<<grid, 512, 0, stream>>>(a);
   } else {
     dim3 grid(n / 64, num_group);
-    const int k56 = hpc_dev_tuning_get(56);  // development key 56: 1 = the stage loop of rounds 1-5, 2 = the new loop on K = 32 MFMAs
+    const int k56 = hpc_dev_tuning_get(kDevStreamGemmLoop);  // development key kDevStreamGemmLoop: 1 = the stage loop of rounds 1-5, 2 = the new loop on K = 32 MFMAs
     if (mt == 1 && k56 == 0)
       gemm_blockwise_stream2_kernel<1, 4><<<grid, kThreads, 0, stream>>>(a);
     else if (mt == 2 && k56 == 0)
@@ -551,6 +547,57 @@ int launch_stream_gemm(hpc::ggemm::Args& a, int num_group, int m, int n, const v
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
+
+// The argument block without y, tile_m, col_base and the epilogue fields, which the entry points set.
+// Blockwise scales: 128 x 128 weight blocks, activation scales per row and k-block.
+hpc::ggemm::Args blockwise_args(const void* x, const void* w, const void* xscale, const void* wscale, const void* seqlens,
+                                const void* cu_seqlens, const void* row_index, int n, int k, int num_block_k_pad4,
+                                int64_t xscale_row_stride, int64_t xscale_kb_stride) {
+  hpc::ggemm::Args a;
+  a.x = static_cast<const uint8_t*>(x);
+  a.w = static_cast<const uint8_t*>(w);
+  a.xs = static_cast<const float*>(xscale);
+  a.ws = static_cast<const float*>(wscale);
+  a.seqlens = static_cast<const int*>(seqlens);
+  a.cu_seqlens = static_cast<const int*>(cu_seqlens);
+  a.row_index = static_cast<const int*>(row_index);
+  a.N = n;
+  a.K = k;
+  a.KB = k / 128;
+  a.ws_group_stride = (n / 128) * num_block_k_pad4;
+  a.ws_ntile_stride = num_block_k_pad4;
+  a.ws_kb_stride = 1;
+  a.has_xs = 1;
+  a.x_bytes = 0xfffffe00u;  // x may be indexed through row_index: rows beyond m exist (< 4 GB checked)
+  a.xs_row_stride = xscale_row_stride;
+  a.xs_kb_stride = xscale_kb_stride;
+  return a;
+}
+// Per-tensor scales: one output scale per group, no activation scales; k_blocks = a.KB.
+hpc::ggemm::Args pertensor_args(const void* x, const void* w, const void* yscale, const void* seqlens,
+                                const void* cu_seqlens, const void* row_index, int x_rows, int n, int k, int k_blocks) {
+  hpc::ggemm::Args a;
+  a.x = static_cast<const uint8_t*>(x);
+  a.w = static_cast<const uint8_t*>(w);
+  a.xs = static_cast<const float*>(yscale);  // unused (has_xs = 0), any valid pointer
+  a.ws = static_cast<const float*>(yscale);
+  a.seqlens = static_cast<const int*>(seqlens);
+  a.cu_seqlens = static_cast<const int*>(cu_seqlens);
+  a.row_index = static_cast<const int*>(row_index);
+  a.col_base = nullptr;
+  a.N = n;
+  a.K = k;
+  a.KB = k_blocks;
+  a.tile_m = 16;
+  a.ws_group_stride = 1;
+  a.ws_ntile_stride = 0;
+  a.ws_kb_stride = 0;
+  a.has_xs = 0;
+  a.x_bytes = static_cast<unsigned>(static_cast<int64_t>(x_rows) * k);
+  a.xs_row_stride = 0;
+  a.xs_kb_stride = 0;
+  return a;
+}
 }  // namespace
 
 extern "C" int hpc_group_gemm_blockwise_fp8_async(
@@ -567,27 +614,11 @@ extern "C" int hpc_group_gemm_blockwise_fp8_async(
   if ((n & 127) || (k & 127)) return HPC_ERR_UNSUPPORTED;  // 128x128 weight scale blocks
   if (num_block_k_pad4 < k / 128) return HPC_ERR_INVALID;
   if (static_cast<int64_t>(m) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;  // 32-bit x offsets
-  Args a;
-  a.x = static_cast<const uint8_t*>(x_ptr);
-  a.w = static_cast<const uint8_t*>(w_ptr);
-  a.xs = static_cast<const float*>(xscale_ptr);
-  a.ws = static_cast<const float*>(wscale_ptr);
+  Args a = blockwise_args(x_ptr, w_ptr, xscale_ptr, wscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k,
+                          num_block_k_pad4, xscale_row_stride, xscale_kb_stride);
   a.y = static_cast<uint16_t*>(y_ptr);
-  a.seqlens = static_cast<const int*>(seqlens_ptr);
-  a.cu_seqlens = static_cast<const int*>(cu_seqlens_ptr);
-  a.row_index = static_cast<const int*>(row_index_ptr);
   a.col_base = static_cast<const int*>(col_base_ptr);
-  a.N = n;
-  a.K = k;
-  a.KB = k / 128;
   a.tile_m = tile_m;
-  a.ws_group_stride = (n / 128) * num_block_k_pad4;
-  a.ws_ntile_stride = num_block_k_pad4;
-  a.ws_kb_stride = 1;
-  a.has_xs = 1;
-  a.x_bytes = 0xfffffe00u;  // x may be indexed through row_index: rows beyond m exist (< 4 GB checked)
-  a.xs_row_stride = xscale_row_stride;
-  a.xs_kb_stride = xscale_kb_stride;
   return launch_stream_gemm(a, num_group, m, n, cu_tiles128_ptr, stream);
 }
 
@@ -606,27 +637,8 @@ extern "C" int hpc_group_gemm_pertensor_fp8_async(void* y_ptr, const void* x_ptr
   if (m <= 0) return HPC_OK;
   if ((n & 63) || (k & 63)) return HPC_ERR_UNSUPPORTED;
   if (static_cast<int64_t>(x_rows) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a;
-  a.x = static_cast<const uint8_t*>(x_ptr);
-  a.w = static_cast<const uint8_t*>(w_ptr);
-  a.xs = static_cast<const float*>(yscale_ptr);  // unused (has_xs = 0), any valid pointer
-  a.ws = static_cast<const float*>(yscale_ptr);
+  Args a = pertensor_args(x_ptr, w_ptr, yscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, x_rows, n, k, (k + 127) / 128);
   a.y = static_cast<uint16_t*>(y_ptr);
-  a.seqlens = static_cast<const int*>(seqlens_ptr);
-  a.cu_seqlens = static_cast<const int*>(cu_seqlens_ptr);
-  a.row_index = static_cast<const int*>(row_index_ptr);
-  a.col_base = nullptr;
-  a.N = n;
-  a.K = k;
-  a.KB = (k + 127) / 128;
-  a.tile_m = 16;
-  a.ws_group_stride = 1;
-  a.ws_ntile_stride = 0;
-  a.ws_kb_stride = 0;
-  a.has_xs = 0;
-  a.x_bytes = static_cast<unsigned>(static_cast<int64_t>(x_rows) * k);
-  a.xs_row_stride = 0;
-  a.xs_kb_stride = 0;
   return launch_stream_gemm(a, num_group, m, n, cu_tiles128_ptr, stream);
 }
 
@@ -639,27 +651,8 @@ int hpc_group_gemm_pertensor_fp8_act(void* act_out, const void* x_ptr, const voi
                                      int n, int k, const void* cu_tiles128_ptr, hipStream_t stream) {
   using namespace hpc::ggemm;
   if (static_cast<int64_t>(x_rows) * k > 0xfffffe00ll || static_cast<int64_t>(n) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a;
-  a.x = static_cast<const uint8_t*>(x_ptr);
-  a.w = static_cast<const uint8_t*>(w_ptr);
-  a.xs = static_cast<const float*>(yscale_ptr);
-  a.ws = static_cast<const float*>(yscale_ptr);
+  Args a = pertensor_args(x_ptr, w_ptr, yscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, x_rows, n, k, k / 128);
   a.y = nullptr;
-  a.seqlens = static_cast<const int*>(seqlens_ptr);
-  a.cu_seqlens = static_cast<const int*>(cu_seqlens_ptr);
-  a.row_index = static_cast<const int*>(row_index_ptr);
-  a.col_base = nullptr;
-  a.N = n;
-  a.K = k;
-  a.KB = k / 128;
-  a.tile_m = 16;
-  a.ws_group_stride = 1;
-  a.ws_ntile_stride = 0;
-  a.ws_kb_stride = 0;
-  a.has_xs = 0;
-  a.x_bytes = static_cast<unsigned>(static_cast<int64_t>(x_rows) * k);
-  a.xs_row_stride = 0;
-  a.xs_kb_stride = 0;
   a.act_out = static_cast<uint8_t*>(act_out);
   a.act_mul_scale = static_cast<const float*>(act_mul_scale_ptr);
   a.use_bf16_mul = use_bf16_mul;
@@ -676,27 +669,11 @@ int hpc_group_gemm_blockwise_fp8_act(void* act_out, void* act_scale, const void*
                                      const void* cu_tiles128_ptr, hipStream_t stream) {
   using namespace hpc::ggemm;
   if (static_cast<int64_t>(m) * k > 0xfffffe00ll || static_cast<int64_t>(n) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a;
-  a.x = static_cast<const uint8_t*>(x_ptr);
-  a.w = static_cast<const uint8_t*>(w_ptr);
-  a.xs = static_cast<const float*>(xscale_ptr);
-  a.ws = static_cast<const float*>(wscale_ptr);
+  Args a = blockwise_args(x_ptr, w_ptr, xscale_ptr, wscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k,
+                          num_block_k_pad4, xscale_row_stride, xscale_kb_stride);
   a.y = nullptr;
-  a.seqlens = static_cast<const int*>(seqlens_ptr);
-  a.cu_seqlens = static_cast<const int*>(cu_seqlens_ptr);
-  a.row_index = static_cast<const int*>(row_index_ptr);
   a.col_base = nullptr;
-  a.N = n;
-  a.K = k;
-  a.KB = k / 128;
   a.tile_m = 16;
-  a.ws_group_stride = (n / 128) * num_block_k_pad4;
-  a.ws_ntile_stride = num_block_k_pad4;
-  a.ws_kb_stride = 1;
-  a.has_xs = 1;
-  a.x_bytes = 0xfffffe00u;
-  a.xs_row_stride = xscale_row_stride;
-  a.xs_kb_stride = xscale_kb_stride;
   a.act_out = static_cast<uint8_t*>(act_out);
   a.act_scale = static_cast<float*>(act_scale);
   return hpc_ggemm_launch_p8(a, static_cast<const int*>(cu_tiles128_ptr), num_group, m, n, stream);

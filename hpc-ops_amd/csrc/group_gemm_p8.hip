@@ -80,13 +80,6 @@ static_assert(kRDummy + 256 <= kLdsTail, "the register-streamed tail body fits t
 constexpr int kLds = (kLdsTail > kLdsMain ? kLdsTail : kLdsMain) > kLdsHalf ? (kLdsTail > kLdsMain ? kLdsTail : kLdsMain) : kLdsHalf;
 static_assert(kLds <= 160 * 1024, "one workgroup per CU");
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int kN>
-struct IntC {
-  static constexpr int value = kN;
-};
-
 // The work item of this workgroup.  Items are dealt to the XCDs in contiguous eighths (workgroup `lin` -> XCD lin % 8,
 // position lin / 8 of that XCD's share), so that the token tiles sharing a weight tile meet in one L2.  The 256-token
 // tile counts come from the scan of ceil(len / 128) the callers already have (`cut`): c = cut[g + 1] - cut[g] 128-row
@@ -113,7 +106,7 @@ struct Item {
 // (row_shr 1, 2, 4, 8: lanes without a source add 0), then lane 15 of row 0 / 2 into row 1 / 3 (row_bcast:15, rows 0xA) and
 // lane 31 into rows 2 and 3 (row_bcast:31, rows 0xC).
 __device__ __forceinline__ int wave_incl_scan(int v, int lane, bool old_path = false) {
-  if (kHpcDevBuild && old_path) {  // development key 43 = 1: the ds_bpermute form of rounds 2-5
+  if (kHpcDevBuild && old_path) {  // development key kDevP8ItemScanOld = 1: the ds_bpermute form of rounds 2-5
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const int u = __shfl_up(v, o, 64);
@@ -222,7 +215,7 @@ __device__ __forceinline__ Item locate_item(cint_ptr cut, const int* seqlens, co
   return it;
 }
 
-// ---- variants of the k-loop (development key 22 selects one in the development build; the product is CfgProduct) -------
+// ---- variants of the k-loop (development key kDevP8LoopVariant selects one in the development build; the product is CfgProduct) -------
 // Where a wave issues its DMA pieces of a k-tile: slot 0 = in the load section, slot n + 1 = behind MFMA n of the MMA
 // section that follows it.  X half of k-tile T: U3(T+1) q0 q1 (free since the barrier that ended the other group's load
 // section Y of T-1).  Y half: U0(T+2) q0 q1, U1(T+2) q0 q1, U2(T+2) q0 q1 (full body only), scales(T+2) - their units are
@@ -256,7 +249,7 @@ struct CfgNoPrio : CfgProduct { static constexpr bool kPrio = false; };
 //  all within noise of or behind the product loop once the carried tails were in)
 #endif
 
-// kNoDma (development key 18 = 1, timing only - results are wrong): no DMA inside the k-loop
+// kNoDma (development key kDevP8NoDma = 1, timing only - results are wrong): no DMA inside the k-loop
 // kAct: the gate-up GEMM of the fused MoE - a tile is 128 gate rows (wave group 0) + the 128 up rows of the same
 // columns (group 1); the epilogue applies SiLU(gate) * up and the 128-block quantisation instead of storing y
 // Blockwise rescale (kHasXs): the ARITHMETIC OF THE REFERENCE KERNEL (src/group_gemm/kernels.cuh:808-834) - every MFMA
@@ -1149,7 +1142,7 @@ __device__ __forceinline__ void tail_finish(const Args& a, uint8_t* s_mem, f32x4
 //     other's LDS latency;
 //   * same operand conventions, swizzle and arithmetic as the full body (one FMA per k block, the last two blocks of a
 //     k-tile folded under the first MFMAs of the next): results are bit-identical to the half-tile body's
-//     (tests/test_fuse_moe_blockwise.py::test_group_gemm_tail_body_is_bit_identical, development key 21 = 2);
+//     (tests/test_fuse_moe_blockwise.py::test_group_gemm_tail_body_is_bit_identical, development key kDevP8NoHalfTile = 2);
 //   * VMEM order per k-tile T (q = T % 3): [W(T+2) x 4] and, behind the chunk barrier at q = 0, [X chunk T/3 + 1 x 3,
 //     scales x 1]; the wait in front of k-tile T leaves 4 (q = 0) or 8 + 3 + (scales) pieces in flight.
 template <bool kHasXs, bool kAct, bool kKTail, bool kNt>
@@ -1347,7 +1340,7 @@ __device__ __forceinline__ void p8_tail_body(const Args& a, uint8_t* s_mem, int 
   tail_finish<kHasXs, kAct>(a, s_mem, tot, ws_row, mt0, n0, m_cnt, m0);
 }
 
-// DEVELOPMENT VARIANT (key 26 = 1; not in the shipped library): the tail body with the weights streamed THROUGH REGISTERS.
+// DEVELOPMENT VARIANT (key kDevP8TailRegs = 1; not in the shipped library): the tail body with the weights streamed THROUGH REGISTERS.
 // Question it answers: is a tail tile - ~32 us for the 32 k-tiles of the MoE's gate-up GEMM, 3 times what its 8 MFMAs per
 // wave and k-tile need - slow because the LDS-ring body above keeps too little in flight (two k-tiles of weights, the next
 // three k-tiles of tokens)?  Nothing in a tail tile shares weights between waves, so here a lane loads exactly its MFMA A
@@ -1403,7 +1396,7 @@ __device__ __forceinline__ void p8_tail_body_r(const Args& a, uint8_t* s_mem, in
   auto ld_w = [&](int T, auto stage) {
     constexpr int kS = decltype(stage)::value;
     const int koff = T * kBK;
-    const i32x4 rs = i32x4{w_lo, w_hi, __builtin_amdgcn_readfirstlane(T < KB ? static_cast<int>(w_bytes) : 0), 0x00020000};
+    const i32x4 rs = i32x4{w_lo, w_hi, __builtin_amdgcn_readfirstlane(T < KB ? static_cast<int>(w_bytes) : 0), kSrdWord3};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       unsigned v1 = w_voff[i] + 64;
@@ -1599,9 +1592,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_p8_kernel(const Args a, 
   const int m0 = __builtin_amdgcn_readfirstlane(it.m0);
   const int mt0 = __builtin_amdgcn_readfirstlane(it.mt) * kBM;
   const int n0 = __builtin_amdgcn_readfirstlane(it.wt) * kBN;
-  // a group's last token tile: <= 64 rows the tail body, <= 128 rows the half-tile body (development key 21 = 1: neither,
+  // a group's last token tile: <= 64 rows the tail body, <= 128 rows the half-tile body (development key kDevP8NoHalfTile = 1: neither,
   // 2: no tail body)
-  // (development key 26 = 1: the register-streamed tail body instead of the LDS-ring one - development build only)
+  // (development key kDevP8TailRegs = 1: the register-streamed tail body instead of the LDS-ring one - development build only)
   const bool tail = m_cnt - mt0 <= 64 && a.no_half_tile == 0 && !kNoDma;
   const bool single = m_cnt <= 64 && a.nt_single;
   if (kHpcDevBuild && tail && a.tail_regs && single)
@@ -1627,7 +1620,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_p8_kernel(const Args a, 
 }
 
 #ifdef HPC_DEV
-// development key 22: variant of the k-loop for the blockwise kernels (A/B runs, tools/tune_ggemm.py; tools/prof_p8.py)
+// development key kDevP8LoopVariant: variant of the k-loop for the blockwise kernels (A/B runs, tools/tune_ggemm.py; tools/prof_p8.py)
 template <class Cfg>
 void launch_blockwise_variant(const Args& a, const int* cu_tiles, int num_group, dim3 grid, hipStream_t stream) {
   if (a.act_out)
@@ -1653,31 +1646,31 @@ int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a_in, const int* cu_tiles, int n
                         hipStream_t stream) {
   using namespace hpc::ggemm;
   Args a = a_in;
-  a.no_half_tile = hpc_dev_tuning_get(21);  // development: 1 = full body only, 2 = no tail body
-  // a group's ONLY (<= 64-row) token tile streams its weights non-temporally (development key 24 = 1: default policy).
+  a.no_half_tile = hpc_dev_tuning_get(kDevP8NoHalfTile);  // development: 1 = full body only, 2 = no tail body
+  // a group's ONLY (<= 64-row) token tile streams its weights non-temporally (development key kDevP8TailTemporal = 1: default policy).
   // (A four-stage form of the weight rings with a single-slab token ring - 96 instead of 64 KB of weights in flight per CU -
   // was built, bit-identical, and measured no faster: T = 256 1 515-1 563 against 1 505-1 512 us, profiles/
   // round5_moe_kernel_choice.txt; the stream is not bound by the bytes in flight at that point.  Removed.)
-  a.nt_single = hpc_dev_tuning_get(24) != 1;
-  a.tail_regs = hpc_dev_tuning_get(26) == 1;
-  a.item_scan_old = hpc_dev_tuning_get(43) == 1;
+  a.nt_single = hpc_dev_tuning_get(kDevP8TailTemporal) != 1;
+  a.tail_regs = hpc_dev_tuning_get(kDevP8TailRegs) == 1;
+  a.item_scan_old = hpc_dev_tuning_get(kDevP8ItemScanOld) == 1;
   // a group's short tail (<= 16 rows per full tile it has) rides along with its full tiles instead of running as a tail
-  // item (blockwise scales; development key 49 = 1: tail items for every tail, the dispatch of round 5)
-  a.ext_rows = hpc_dev_tuning_get(49) != 1;
+  // item (blockwise scales; development key kDevP8NoRideAlong = 1: tail items for every tail, the dispatch of round 5)
+  a.ext_rows = hpc_dev_tuning_get(kDevP8NoRideAlong) != 1;
   if (n % kBN || a.K < kBK) return HPC_ERR_UNSUPPORTED;
   const long max_tiles = m / kBM + num_group;  // upper bound of sum_g ceil(len_g / 256)
   const long items = max_tiles * (n / kBN) + 16;  // + 16: the per-XCD chunks of the full and of the tail tiles round up
   // tail tiles stay next to their full siblings (order 0).  Order 1 - all full tiles first, tail tiles last, which evens
   // out the end of a launch (the down GEMM of the MoE has ~9.4 items per CU) - measured SLOWER on the same box: gate-up /
   // down GEMM 3493 / 1624 us against 3225 / 1583 us: a tail tile that cannot meet its weight tile in L2 streams it from
-  // memory and its DMA pieces land late (development key 23 = 1 selects order 1; profiles/round5_moe_ggemm_ab.txt)
-  a.item_order = hpc_dev_tuning_get(23) == 1 ? 1 : 0;
+  // memory and its DMA pieces land late (development key kDevP8TailsLast = 1 selects order 1; profiles/round5_moe_ggemm_ab.txt)
+  a.item_order = hpc_dev_tuning_get(kDevP8TailsLast) == 1 ? 1 : 0;
   if (items > 0x7fffffffl) return HPC_ERR_UNSUPPORTED;
   dim3 grid(static_cast<unsigned>(items));
 #ifdef HPC_DEV
   a.prof = g_p8_prof;
-  if (a.has_xs && hpc_dev_tuning_get(22) > 0) {
-    switch (hpc_dev_tuning_get(22)) {
+  if (a.has_xs && hpc_dev_tuning_get(kDevP8LoopVariant) > 0) {
+    switch (hpc_dev_tuning_get(kDevP8LoopVariant)) {
       case 1: launch_blockwise_variant<CfgProf>(a, cu_tiles, num_group, grid, stream); break;
       case 2: launch_blockwise_variant<CfgRound4>(a, cu_tiles, num_group, grid, stream); break;
       case 3: launch_blockwise_variant<CfgRound4Prof>(a, cu_tiles, num_group, grid, stream); break;
@@ -1695,7 +1688,7 @@ int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a_in, const int* cu_tiles, int n
     gemm_fp8_p8_kernel<P, false, false, true, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
   else if (a.act_out)
     gemm_fp8_p8_kernel<P, false, false, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (kHpcDevBuild && a.has_xs && hpc_dev_tuning_get(18) == 1)
+  else if (kHpcDevBuild && a.has_xs && hpc_dev_tuning_get(kDevP8NoDma) == 1)
     gemm_fp8_p8_kernel<P, true, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
   else if (a.has_xs)
     gemm_fp8_p8_kernel<P, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);

@@ -19,10 +19,6 @@ constexpr int kThreads = 256;
 constexpr int kTile = 128;
 constexpr int kRow = 128 + 16;  // padded LDS row (bytes)
 
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-
 __global__ __launch_bounds__(kThreads, 2) void gemm_fp8_tiled_kernel(const Args a, const int* __restrict__ cu_tiles,
                                                                      int num_group) {
   __shared__ __attribute__((aligned(16))) uint8_t s_w[2][kTile * kRow];

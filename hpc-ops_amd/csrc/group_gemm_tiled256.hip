@@ -39,12 +39,6 @@ __device__ unsigned long long g_t256_prof[16];
 #define T256_ACC(i, v)
 #endif
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
-  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
-}
-
 // Per-token-tile-size constants (namespace scope on purpose: the kernel's lambdas use them, and hipcc's
 // host pass drops the kernel stub when a lambda in a templated __global__ refers to function-local
 // constexpr values derived from the template arguments).
@@ -372,10 +366,10 @@ int hpc_ggemm_launch_tiled256(const hpc::ggemm::Args& a, const int* cu_tiles, in
   // The 32-token-tile form (4-slab ring: three weight slabs in flight) was meant for 40-128 tokens per
   // group; measured it is SLOWER (E64: 3.6 ms vs 2.2 ms at T = 256 .. 768) - its extra token tiles re-read
   // the weight tile through L2 and do a quarter of the MFMA work per slab - so it only runs on request.
-  const bool narrow = hpc_dev_tuning_get(6) == 2;
+  const bool narrow = hpc_dev_tuning_get(kDevTiled256Form) == 2;
   // 64-token tiles (8 x 1 waves of 32 x 64, 42 KB per slab, three slabs in the ring) - also measured SLOWER than
   // the 128-token tile on groups of 24-64 rows (E64: T = 256 2.19 vs 1.73 ms, T = 384 2.25 vs 1.75 ms): on request only
-  const bool half = hpc_dev_tuning_get(6) == 3;
+  const bool half = hpc_dev_tuning_get(kDevTiled256Form) == 3;
   const long max_tiles = m / kBM + num_group;  // upper bound of sum_g ceil(len_g / 128)
   const long items = max_tiles * (n / kBN) * (narrow ? 4 : (half ? 2 : 1)) + 8;  // + 8: the per-XCD chunks round up
   if (items > 0x7fffffffl) return HPC_ERR_UNSUPPORTED;

@@ -23,6 +23,25 @@ typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+// operand types of the transposing LDS reads (ds_read_b64_tr_b8 / _b16) and LDS address-space pointees
+typedef int v2i32 __attribute__((ext_vector_type(2)));
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
+typedef __attribute__((address_space(3))) v2i32 lds_v2i32;
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+
+// compile-time integer as a value: the argument of a generic lambda that needs it constexpr
+template <int kN>
+struct IntC {
+  static constexpr int value = kN;
+};
+
+// two dwords as the 64-bit operand of an fp8 MFMA
+__device__ __forceinline__ long pack64(uint32_t lo, uint32_t hi) {
+  return static_cast<long>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
+}
 
 // ---- bf16 <-> f32 (bit tricks; RNE on the way down, NaN preserved) -------------------
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) {
@@ -100,6 +119,29 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// sum over a workgroup of four waves through four LDS floats
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();  // red is reused between calls
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+// max / sum over the 4 lanes that share a q row (lane, lane ^ 16, lane ^ 32, lane ^ 48) with the gfx950 row-swap
+// instructions instead of ds_bpermute (an LDS round trip on the critical path of every wave-iteration):
+// permlane16_swap(x, x) = {[x0 x0 x2 x2], [x1 x1 x3 x3]} by 16-lane rows, permlane32_swap(y, y) = {[y0 y1 y0 y1], [y2 y3 y2 y3]}
+__device__ __forceinline__ float row4_max(float x) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  const float y = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
+  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float row4_sum(float x) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  const float y = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(y), __float_as_uint(y), false, false);
+  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
 
 // ---- 16-byte global accesses -------------------------------------------------------------
 __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
@@ -116,14 +158,17 @@ typedef const int __attribute__((address_space(4))) * cint_ptr;
 __device__ __forceinline__ cint_ptr as_const(const int* p) {
   return (cint_ptr)(reinterpret_cast<uintptr_t>(p));
 }
+typedef const float __attribute__((address_space(4))) * cfloat_ptr;
+__device__ __forceinline__ cfloat_ptr as_constf(const float* p) { return (cfloat_ptr)(reinterpret_cast<uintptr_t>(p)); }
 
 // ---- buffer (SRD) loads: wave-uniform 64-bit base in SGPRs + 32-bit lane offset -------------------
 // The base must be provably wave-uniform (built from kernargs / readfirstlane values), otherwise
 // hipcc wraps every access in a waterfall loop.
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
+constexpr int kSrdWord3 = 0x00020000;  // last descriptor word of a raw buffer: DATA_FORMAT = 32 bits, nothing else (no swizzle, no thread-id add)
 // num_records = 0 makes every access out of range: loads return 0 and fetch nothing.
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned num_records = 0xffffffffu) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, num_records, 0x00020000);
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, num_records, kSrdWord3);
 }
 // Pin a pointer that IS wave-uniform (but that hipcc's divergence analysis cannot prove uniform) into
 // SGPRs; without it a descriptor built from the pointer costs a waterfall loop per access.
@@ -133,6 +178,17 @@ __device__ __forceinline__ const uint8_t* uniform_ptr(const void* p) {
   const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
   return reinterpret_cast<const uint8_t*>(static_cast<uint64_t>(lo) | (static_cast<uint64_t>(hi) << 32));
 }
+// The descriptor as four plain dwords, for inline-asm buffer loads (the loads the compiler does not see): every word
+// pinned into an SGPR, because an "s" operand must be provably wave-uniform or hipcc hands the assembler a VGPR tuple.
+__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ i32x4 srd(uint32_t lo, uint32_t hi, int num_records) {
+  return i32x4{sgpr(static_cast<int>(lo)), sgpr(static_cast<int>(hi)), sgpr(num_records), kSrdWord3};
+}
+__device__ __forceinline__ i32x4 srd_of(const void* base, unsigned num_records = 0xffffffffu) {
+  const uint64_t v = reinterpret_cast<uint64_t>(base);
+  return srd(static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32), static_cast<int>(num_records));
+}
+__device__ __forceinline__ i32x4 pin(i32x4 r) { return i32x4{sgpr(r[0]), sgpr(r[1]), sgpr(r[2]), sgpr(r[3])}; }
 // voff: per-lane byte offset (may carry a compile-time constant), soff: wave-uniform byte offset
 // kAux: cache policy bits of the buffer instruction (0 = default, 2 = nt "streaming, read once")
 template <int kAux = 0>

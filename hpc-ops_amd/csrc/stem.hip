@@ -144,14 +144,6 @@ __global__ __launch_bounds__(256) void stem_prep_kv_kernel(const PrepKvArgs a) {
 
 // grid (Hkv, B), 256 threads: mean / sample std of l = log(v_norm + 1e-6) over the request's Kb*8 windows, then
 // vbias[b] = lambda/8 * sum_s relu((l[8b+s] - mean) / (std + 1e-6)); zeros past the request's blocks.
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();  // red is reused between calls
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ __launch_bounds__(256) void stem_vbias_kernel(float* __restrict__ vbias, const float* __restrict__ v_norm,
                                                          const int* __restrict__ kv_seq_lens, int num_head_kv, int max_kb,
                                                          float lambda_mag) {
@@ -163,13 +155,13 @@ __global__ __launch_bounds__(256) void stem_vbias_kernel(float* __restrict__ vbi
   float* vb = vbias + row * max_kb;
   float s = 0.0f;
   for (int i = tid; i < n; i += 256) s += logf(vn[i] + 1e-6f);
-  const float mean = n > 0 ? block_sum256(s, red) / static_cast<float>(n) : 0.0f;
+  const float mean = n > 0 ? block_sum(s, red) / static_cast<float>(n) : 0.0f;
   float q = 0.0f;
   for (int i = tid; i < n; i += 256) {
     const float d = logf(vn[i] + 1e-6f) - mean;
     q += d * d;
   }
-  q = n > 0 ? block_sum256(q, red) : 0.0f;
+  q = n > 0 ? block_sum(q, red) : 0.0f;
   const float sd = n > 1 ? sqrtf(q / static_cast<float>(n - 1)) : 0.0f;
   const float inv = 1.0f / (sd + 1e-6f);
   for (int b = tid; b < max_kb; b += 256) {

@@ -1,5 +1,9 @@
-// Paged decode attention for gfx950: bf16 and fp8 (e4m3) KV, D=128, GQA group 4/8, dynamic
-// split-KV task map, plus the split-KV combine kernel.
+// Paged decode attention for gfx950: bf16 and fp8 (e4m3) KV, D=128, GQA group 1/2/4/8/16 (the groups the prefill
+// ops take), dynamic split-KV task map, plus the split-KV combine kernel.  The kernels address q rows as
+// row >> g_shift, row & (G - 1) with G read at run time; a call routes by its q rows per kv head (num_seq_q * G): <= 16
+// head pairs or this file's one-block form, 17 ... 32 one kv head per workgroup (attention_decode_v2.hip) or the two-block
+// form, 33 ... 48 bf16 three blocks; group 16 with more rows than a form holds is served as slices of a kv head's q
+// heads (decode_slices() below).
 //
 // Replaces reference src/attention/decode/sm90/{dynamic,static}/smallm_{bf16,fp8_*}_dim128_*.cu(h)
 // and src/attention/decode/splitk_combine_kernels.cuh (static split-K becomes "schedule on the
@@ -61,6 +65,8 @@ struct Args {
   const float* kscale;  // fp8: [1] (per tensor) or base of the K-scale rows of the cache (per token)
   const float* vscale;  // fp8: [1] or [Hkv]
   int num_batch, num_seq_q, num_head_kv, g_shift, page_shift, max_blocks;
+  int hq_shift;  // q heads per kv head in MEMORY, log2: kv head h's q heads (and q scales, y rows) start at h << hq_shift.  = g_shift
+                 // except in a pass over one slice of a group-16 kv head's q heads (launch_sliced: g_shift is the slice's group)
   int ldq, ldy, qscale_stride;
   int solo_ok;  // bins full of short tasks may run one task per wave (tuning key kDevDecodeNoWaveSolo = 1 turns it off)
   long k_block_stride, k_token_stride, k_head_stride;  // elements
@@ -171,7 +177,7 @@ __global__ __launch_bounds__(kThreads, kNB == 1 ? 2 : 1) void decode_kernel(cons
       const int row = nb * 16 + n;
       const bool ok = row < rows_valid;
       const int sq = row >> a.g_shift;
-      const int hq = (h << a.g_shift) + (row & (G - 1));
+      const int hq = (h << a.hq_shift) + (row & (G - 1));
       row_sq[nb] = sq;
       const long qoff = (static_cast<long>(b * a.num_seq_q + sq) * a.ldq + hq * 128) * kEB;
 #pragma unroll
@@ -439,7 +445,7 @@ __global__ __launch_bounds__(kThreads, kNB == 1 ? 2 : 1) void decode_kernel(cons
       if (nchunks == 1) {
         const int rs = row >> a.g_shift;
         uint16_t* dst = a.y + static_cast<long>(b * a.num_seq_q + rs) * a.ldy +
-                        ((h << a.g_shift) + (row & (G - 1))) * 128 + c8 * 8;
+                        ((h << a.hq_shift) + (row & (G - 1))) * 128 + c8 * 8;
         u32x4 pk;
 #pragma unroll
         for (int i = 0; i < 4; ++i) pk[i] = pack_bf16x2(acc[2 * i], acc[2 * i + 1]);
@@ -584,7 +590,7 @@ __global__ __launch_bounds__(kThreads, kNB == 1 ? 2 : 1) void decode_kernel(cons
           }
           const float inv = W > 0.f ? 1.0f / W : 0.f;
           const int rs = row >> a.g_shift;
-          uint16_t* dst = a.y + static_cast<long>(b * a.num_seq_q + rs) * a.ldy + ((h << a.g_shift) + (row & (G - 1))) * 128 + c8 * 8;
+          uint16_t* dst = a.y + static_cast<long>(b * a.num_seq_q + rs) * a.ldy + ((h << a.hq_shift) + (row & (G - 1))) * 128 + c8 * 8;
           u32x4 pk;
 #pragma unroll
           for (int i = 0; i < 4; ++i) pk[i] = pack_bf16x2(acc[2 * i] * inv, acc[2 * i + 1] * inv);
@@ -690,7 +696,7 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(const Args a, 
   const float inv = W > 0.f ? 1.0f / W : 0.f;
   const int rs = row >> a.g_shift;
   uint16_t* dst = a.y + static_cast<long>(b * a.num_seq_q + rs) * a.ldy +
-                  ((h << a.g_shift) + (row & (G - 1))) * 128 + c8 * 8;
+                  ((h << a.hq_shift) + (row & (G - 1))) * 128 + c8 * 8;
   u32x4 pk;
 #pragma unroll
   for (int i = 0; i < 4; ++i) pk[i] = pack_bf16x2(acc[2 * i] * inv, acc[2 * i + 1] * inv);
@@ -727,6 +733,29 @@ int launch(const Args& a, int num_bins, int num_nb, hipStream_t stream) {
   return HPC_OK;
 }
 
+// Group 16 with more q rows per kv head than a form holds, on the first generation: one pass per slice of 8 adjacent q heads
+// (24 / 32 rows: two blocks; bf16 40 rows: three), the slice's q heads, q scales and y rows reached through offset base pointers
+// and hq_shift; K / V, the task map and the scratch are the call's - the passes run one after the other in the stream and each
+// leaves the arrival counters zero.  Every pass streams the whole cache: 2 x the time of one.  Serves the sliced calls that the
+// one-head-per-workgroup form (attention_decode_v2.hip, virtual heads) cannot take: fp8 on pages of 16, lengths on the host, more
+// arrival counters than 64 KB.
+template <bool kFp8, int kQuant>
+int launch_sliced(const Args& a, int num_bins, hipStream_t stream) {
+  constexpr int kSliceShift = 3;  // 8 q heads
+  Args s = a;
+  s.g_shift = kSliceShift;
+  const int num_nb = ((a.num_seq_q << kSliceShift) + 15) / 16;
+  for (int sl = 0; sl < (1 << (a.g_shift - kSliceShift)); ++sl) {
+    const long heads = static_cast<long>(sl) << kSliceShift;
+    s.q = static_cast<const uint8_t*>(a.q) + heads * 128 * (kFp8 ? 1 : 2);
+    s.y = a.y + heads * 128;
+    s.qscale = a.qscale ? a.qscale + heads : nullptr;
+    const int rc = launch<kFp8, kQuant>(s, num_bins, num_nb, stream);
+    if (rc != HPC_OK) return rc;
+  }
+  return HPC_OK;
+}
+
 struct Common {
   int num_nb;
   int code;
@@ -753,7 +782,8 @@ inline Common fill_common(Args& a, void* y_ptr, void* workspace, const int* task
     return c;
   }
   const int group = num_head_q / num_head_kv;
-  if ((group != 4 && group != 8) || num_seq_q < 1 || num_seq_q > 5) {
+  // powers of two up to 16: q rows are addressed by shift and mask (the prefill ops take the same set)
+  if ((group != 1 && group != 2 && group != 4 && group != 8 && group != 16) || num_seq_q < 1 || num_seq_q > 5) {
     c.code = HPC_ERR_UNSUPPORTED;
     return c;
   }
@@ -783,7 +813,7 @@ inline Common fill_common(Args& a, void* y_ptr, void* workspace, const int* task
   a.num_batch = num_batch;
   a.num_seq_q = num_seq_q;
   a.num_head_kv = num_head_kv;
-  a.g_shift = group == 8 ? 3 : 2;
+  a.g_shift = a.hq_shift = __builtin_ctz(static_cast<unsigned>(group));
   a.page_shift = block_size == 64 ? 6 : (block_size == 32 ? 5 : 4);
   a.max_blocks = num_seq_max_blocks;
   a.solo_ok = hpc_dev_tuning_get(kDevDecodeNoWaveSolo) != 1;
@@ -851,12 +881,34 @@ extern "C" int hpc_dev_decode_prof_buffer(void* p) {
 static constexpr void* g_decode_prof = nullptr;  // production build: the profiling instantiations are not emitted
 #endif
 
+// Group 16 with more q rows per kv head than any form holds (`max_rows`: fp8 32; bf16 48 - the first generation's three-block form
+// runs 16 x 3 rows in one pass, 319 / 395 us against 365 / 503 us as two slices on the C3 mix / uniform 8k at 8 kv heads,
+// profiles/gqa_groups_decode.txt): the kv head's 16 q heads are served as two slices of 8 adjacent q heads.
+//  * num_seq_q 3, 4 (24 / 32 rows per slice): each slice is a virtual kv head of the one-head-per-workgroup form.  A slice's q
+//    heads, q scales and y rows are contiguous at (virtual head) << 3 - what that kernel computes for a real head of group 8;
+//    only K / V / K-scale / V-scale addresses use the real head (decode2::Args::share_shift = 1).  A kv head's K / V bytes are
+//    requested once per slice; sibling slices share an XCD's L2 where the kv head count allows (see the kernel): 1.40-1.58 x the
+//    time of one pass.  A call that form cannot take (fp8 on pages of 16, host lengths, more arrival counters than 64 KB,
+//    development keys that switch the second generation off) runs as one first-generation pass per slice (launch_sliced: 2 x).
+//  * bf16 num_seq_q 5 (40 rows per slice): two passes of the first generation's three-block form, 599 / 755 us - measured
+//    against four slices of 20 rows on the one-head form: 659 / 899 us.
+// Returns share_shift for the one-head form (0: not sliced, or sliced on the first generation only - see `sliced`).
+static int decode_slices(int num_seq_q, int group, int max_rows, bool* sliced) {
+  *sliced = group == 16 && num_seq_q * group > max_rows;
+  return *sliced && num_seq_q * 8 <= 32 ? 1 : 0;
+}
+
 // Second generation (attention_decode_v2.hip: head pairs per load, deep prefetch, in-kernel plan and merge) when the
 // layout allows it.  Returns HPC_OK when it launched, 1 when the call is not its case (the caller goes on to the
 // first generation), a negative code on a launch error.  Strides in `b` are BYTES.
+// `share_shift` > 0: the call is served as 1 << share_shift slices per kv head (decode_slices() above) - the kernel sees
+// num_head_kv << share_shift virtual heads of group (num_head_q / num_head_kv) >> share_shift, one per workgroup.
 static int try_second_generation(hpc::decode2::Args& b, void* workspace, int num_bins, int num_batch, int num_seq_q,
                                  int num_head_q, int num_head_kv, int block_size, int64_t k_head_stride_bytes,
-                                 int64_t v_head_stride_bytes, hipStream_t stream) {
+                                 int64_t v_head_stride_bytes, hipStream_t stream, int share_shift = 0) {
+  b.share_shift = share_shift;
+  b.num_head_kv = num_head_kv << share_shift;
+  b.g_shift = __builtin_ctz(static_cast<unsigned>(num_head_q / b.num_head_kv));
   b.part_o = b.part_lse = nullptr;
   b.arrive = nullptr;
   b.dev_nomem = hpc_dev_tuning_get(kDevDecodeNoKvLoads);
@@ -866,7 +918,8 @@ static int try_second_generation(hpc::decode2::Args& b, void* workspace, int num
   const int mode = hpc::decode2::mode_of(b, num_head_q, block_size, k_head_stride_bytes, v_head_stride_bytes);
   int dev = 0;
   if (mode == 0 || hipGetDevice(&dev) != hipSuccess) return 1;
-  const int unit = mode == 3 ? num_head_kv : num_head_kv / (mode == 2 ? 4 : 2);  // workgroup = (token range, head pair, quad or head)
+  if (share_shift > 0 && mode != 3) return 1;
+  const int unit = mode == 3 ? b.num_head_kv : num_head_kv / (mode == 2 ? 4 : 2);  // workgroup = (token range, head pair, quad or (virtual) head)
   int num_wg = 2 * hpc_get_cu_count(dev);  // two 4-wave workgroups per CU (<= 256 registers, 65 KB of LDS each)
   const int wg_dev = hpc_dev_tuning_get(kDevDecodeGrid);
   if (wg_dev > 0) num_wg = wg_dev;
@@ -895,7 +948,9 @@ extern "C" int hpc_attention_decode_bf16_async(
                                kcache_head_stride, vcache_block_stride, vcache_token_stride,
                                vcache_head_stride, 8);
   if (c.code != HPC_OK) return c.code;
-  if (num_seq_kvcache_ptr && hpc_dev_tuning_get(kDevDecodeBf16NoPair) != 1) {  // development key kDevDecodeBf16NoPair = 1: bf16 on the first generation only
+  bool sliced = false;
+  const int share_shift = decode_slices(num_seq_q, num_head_q / num_head_kv, 48, &sliced);
+  if (num_seq_kvcache_ptr && hpc_dev_tuning_get(kDevDecodeBf16NoPair) != 1 && sliced == (share_shift > 0)) {  // development key kDevDecodeBf16NoPair = 1: bf16 on the first generation only
     hpc::decode2::Args b;
     b.q = q_ptr;
     b.kcache = kcache_ptr;
@@ -923,9 +978,10 @@ extern "C" int hpc_attention_decode_bf16_async(
     b.ks_block_stride = b.ks_row_stride = b.ks_head_stride = 0;
     b.scale_log2 = a.scale_log2;
     const int rc = try_second_generation(b, workspace, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, block_size,
-                                         kcache_head_stride * 2, vcache_head_stride * 2, stream);
+                                         kcache_head_stride * 2, vcache_head_stride * 2, stream, share_shift);
     if (rc <= 0) return rc;
   }
+  if (sliced) return launch_sliced<false, 1>(a, num_bins, stream);
   return launch<false, 1>(a, num_bins, c.num_nb, stream);
 }
 
@@ -958,6 +1014,8 @@ extern "C" int hpc_attention_decode_fp8_async(
   a.ks_block_stride = kscale_block_stride;
   a.ks_row_stride = kscale_row_stride;
   a.ks_head_stride = kscale_head_stride;
+  bool sliced = false;
+  const int share_shift = decode_slices(num_seq_q, num_head_q / num_head_kv, 32, &sliced);
   // second generation (head pairs per load, deep prefetch, in-kernel plan) when the layout allows it
   {
     hpc::decode2::Args b;
@@ -994,10 +1052,12 @@ extern "C" int hpc_attention_decode_fp8_async(
     b.ktok = quant_type == 0 ? 1 : 0;
     if (quant_type == 1 || hpc_dev_tuning_get(kDevDecodeQt0FirstGen) != 1) {
       const int rc = try_second_generation(b, workspace, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, block_size,
-                                           kcache_head_stride, vcache_head_stride, stream);
+                                           kcache_head_stride, vcache_head_stride, stream, share_shift);
       if (rc <= 0) return rc;
     }
   }
+  if (sliced)
+    return quant_type == 1 ? launch_sliced<true, 1>(a, num_bins, stream) : launch_sliced<true, 0>(a, num_bins, stream);
   if (quant_type == 1) return launch<true, 1>(a, num_bins, c.num_nb, stream);
   return launch<true, 0>(a, num_bins, c.num_nb, stream);
 }

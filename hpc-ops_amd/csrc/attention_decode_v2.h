@@ -23,6 +23,12 @@ struct Args {
   const float* vscale;   // [1] or [Hkv]
   int num_batch, num_seq_q, num_head_kv, g_shift, page_shift, max_blocks;
   int ldq, ldy, qscale_stride, new_kv_included;
+  // one kv head per workgroup only (mode 3): the workgroup's head index is a VIRTUAL head - slice (vh & (slices - 1)) of the
+  // 1 << share_shift slices that kv head vh >> share_shift's q heads are cut into (GQA group 16 with more q rows than a form
+  // holds).  num_head_kv counts virtual heads and g_shift is the slice's group then: q heads, q scales, y rows, partial slots
+  // and arrival counters are addressed by vh exactly as for a real head; K / V pages, per-token K scales and per-head V
+  // scales by vh >> share_shift.  0 everywhere else.
+  int share_shift = 0;
   int min_range_cost;  // smallest range of the in-kernel plan, in cost units (64-token tiles + 2 per request)
   int bf16;       // 1: bf16 q / K / V (no scales; ldq and every stride in BYTES), 0: fp8 e4m3
   int ktok = 0;   // fp8: 1 = per-token K scales in the pages' tail rows (kscale + ks_* strides) and per-head V scales (quant_type 0)
@@ -49,10 +55,12 @@ struct Args {
 // the first time a workspace is used (the kernel leaves it zero); its place and size do not depend on the call.
 constexpr int64_t kCounterBytes = 64 * 1024;
 int64_t workspace_bytes(int num_wg);  // partial slots (2 per workgroup x 2 heads), after the first-generation region
-// 3: one kv head per workgroup (fp8, per-tensor scales, 17 ... 32 q rows per kv head, any page layout, pages of 32 / 64 tokens);
+// 3: one kv head per workgroup (fp8 with either scale scheme on pages of 32 / 64 tokens, bf16 on pages of 16 / 32 / 64; 17 ... 32 q
+//    rows per (virtual) kv head, any page layout; the only mode that serves a.share_shift > 0);
 // 0: not served here; 1: served (NHD pages with adjacent heads contiguous - 128 B apart for fp8, 256 B for bf16 -, or, fp8
 // with per-tensor scales and development key kDevDecodeHndPair = 1, HND pages with a head's tokens contiguous (a.hnd is set then); an even number of kv heads,
-// <= 16 q rows per kv head, <= 1024 requests).
+// <= 16 q rows per kv head, <= 1024 requests).  Any power-of-two GQA group 1 ... 16 whose rows fit (the four-head development form:
+// groups 4 and 8 only).
 int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int64_t v_head_stride);
 int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStream_t stream);
 #ifdef HPC_DEV

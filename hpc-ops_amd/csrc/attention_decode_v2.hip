@@ -287,6 +287,24 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
     rng = (wg >> 3) * 2 + (e >> 2);
   }
   if (a.mate_from > 0 && wg >= a.mate_from) pr ^= a.pair_xor;
+  if constexpr (kSolo) {
+    // Virtual heads (Args::share_shift > 0): the slices of one kv head stream the SAME K / V rows.  Workgroups go round the 8 XCDs
+    // in index order and every XCD has an L2 of its own, so sibling slices on neighbouring workgroup indices (virtual head index
+    // minor) each fetch the rows from memory - measured at 8 kv heads: two slices cost 1.85-2.05 x one pass, four 3.3-3.8 x.  So
+    // siblings sit a multiple of 8 workgroups apart - the same XCD, the same dispatch wave, the same range: 1.40-1.58 x and
+    // 2.1-2.4 x (profiles/gqa_groups_decode.txt; the product launches two slices only, attention_decode.hip::decode_slices).  kv head count a multiple of 8: kv head minor, slice major.  A divisor of 8: a row
+    // of 8 workgroups holds 8 / heads ranges x heads, the slices follow in the next rows.  Other counts: kv head minor (no guarantee).
+    if (a.share_shift > 0) {
+      const int ss = a.share_shift, hk = npair >> ss;
+      if (hk < 8 && (8 % hk) == 0 && (nrange % (8 / hk)) == 0) {
+        const int x = wg & 7, j = wg >> 3;
+        pr = ((x % hk) << ss) | (j & ((1 << ss) - 1));
+        rng = (j >> ss) * (8 / hk) + x / hk;
+      } else {
+        pr = ((pr % hk) << ss) | (pr / hk);
+      }
+    }
+  }
   int lwg = wg;         // logical workgroup index: partial slots are addressed by (slice offset + range)
   int lwg0 = pr * nrange;  // first logical index of this slice
   if (a.pair_wgs[0] > 0 && npair == 4) {
@@ -473,7 +491,9 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
   const int ks3 = sgpr(kHnd ? static_cast<uint32_t>(a.k_head_stride) + kRpi * k_rs : 3 * kRpi * k_rs);
   const int vs1 = sgpr(kRpi * v_rs), vs2 = sgpr(kHnd ? static_cast<uint32_t>(a.v_head_stride) : 2 * kRpi * v_rs);
   const int vs3 = sgpr(kHnd ? static_cast<uint32_t>(a.v_head_stride) + kRpi * v_rs : 3 * kRpi * v_rs);
-  const int mem_slice = a.dev_slice > 0 ? a.dev_slice - 1 : pr;
+  // (one head per workgroup: pr may be a virtual head - a slice of a kv head's q heads, Args::share_shift - whose K / V, K scales and V
+  //  scale are the real head's; wave-uniform, so the shift lives in scalar registers)
+  const int mem_slice = kSolo ? (pr >> a.share_shift) : (a.dev_slice > 0 ? a.dev_slice - 1 : pr);
   const uint64_t kbase_h = reinterpret_cast<uint64_t>(a.kcache) + static_cast<uint64_t>(mem_slice) * (kSolo ? static_cast<uint64_t>(a.k_head_stride) : kHnd ? 2 * static_cast<uint64_t>(a.k_head_stride) : kRowB);
   const uint64_t vbase_h = reinterpret_cast<uint64_t>(a.vcache) + static_cast<uint64_t>(mem_slice) * (kSolo ? static_cast<uint64_t>(a.v_head_stride) : kHnd ? 2 * static_cast<uint64_t>(a.v_head_stride) : kRowB);
   const uint32_t kbs = static_cast<uint32_t>(a.k_block_stride), vbs = static_cast<uint32_t>(a.v_block_stride);  // < 4 GB (eligible())
@@ -970,8 +990,8 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
           for (int hh = 0; hh < 2; ++hh) row_scale[hh] = a.scale_log2 * __uint_as_float(qsc[hh]) * kmul;
           out_scale = as_constf(a.vscale)[0];  // the 1/256 of the reference formula cancels: l = 256 sum p
           if constexpr (kKtok) {  // per-head V scales
-            out_scale_h[0] = as_constf(a.vscale)[kSolo ? pr : pr * 2];
-            out_scale_h[1] = as_constf(a.vscale)[kSolo ? pr : pr * 2 + 1];
+            out_scale_h[0] = as_constf(a.vscale)[kSolo ? (pr >> a.share_shift) : pr * 2];
+            out_scale_h[1] = as_constf(a.vscale)[kSolo ? (pr >> a.share_shift) : pr * 2 + 1];
           }
         }
       }
@@ -1513,6 +1533,7 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
     const bool wanted = k60 == 3 ? true : k60 == 2 ? !pair_case : (k60 == 0 && rows > 16);  // 3: every eligible call (A/B against the pair forms)
     if (shape_ok && wanted) return 3;
   }
+  if (a.share_shift > 0) return 0;  // virtual heads (slices of a group-16 kv head's q heads) exist in the one-head form only
   const bool hnd = !a.bf16 && !a.ktok && a.k_token_stride == 128 && a.v_token_stride == 128 && k_head_stride >= 128 * block_size &&
                    v_head_stride >= 128 * block_size && (k_head_stride % 16) == 0 && (v_head_stride % 16) == 0 &&
                    k_head_stride < (1ll << 28) && v_head_stride < (1ll << 28) && a.num_head_kv > 1 && hpc_dev_tuning_get(kDevDecodeHndPair) == 1;
@@ -1541,7 +1562,10 @@ int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int6
   // profiles/round3_decode_fp8_forms_ab.txt): the wider rows do not pay in the kernel although they do in a pure streaming
   // probe - the waves sit in the load issue either way (tools/prof_decode.py: 52-57 % of a wave's cycles).  So head
   // pairs stay the default and development key kDevDecodeQuadForm = 2 selects the four-head form (kept: tested, half the softmax work).
-  const bool quad = !a.bf16 && !a.hnd && (a.num_head_kv % 4) == 0 && a.num_seq_q * group <= 8 && hpc_dev_tuning_get(kDevDecodeQuadForm) == 2;
+  // (development form: GQA groups 4 and 8 only - its column -> (head, q row) selects were written and tested for those; groups 1 and
+  // 2 stay on head pairs whatever the key says)
+  const bool quad = !a.bf16 && !a.hnd && (a.num_head_kv % 4) == 0 && (group == 4 || group == 8) && a.num_seq_q * group <= 8 &&
+                    hpc_dev_tuning_get(kDevDecodeQuadForm) == 2;
   return quad ? 2 : 1;
 }
 

@@ -51,8 +51,10 @@ DecodeCommon decode_common_checks(const at::Tensor& q, const at::Tensor& kcache,
   TORCH_CHECK(q.size(2) == 128, "we only support head dim 128.");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == 128, "q heads must be contiguous");
   TORCH_CHECK(kcache.stride(3) == 1 && vcache.stride(3) == 1, "kv cache dims must be contiguous");
+  TORCH_CHECK(kcache.size(2) > 0 && q.size(1) % kcache.size(2) == 0, "num_head_q must be a multiple of num_head_k.");
   c.group = static_cast<int>(q.size(1) / kcache.size(2));
-  TORCH_CHECK(c.group == 4 || c.group == 8, "we only support num_head_q / num_head_k == 4 or 8.");
+  TORCH_CHECK(c.group == 1 || c.group == 2 || c.group == 4 || c.group == 8 || c.group == 16,
+              "we only support num_head_q / num_head_k == 1, 2, 4, 8 or 16.");
   return c;
 }
 

@@ -35,7 +35,10 @@ def attention_decode_bf16(
     """Paged decode attention in bfloat16 (reference hpc/attention.py:336-417).
 
     Args:
-        q: [num_batch * num_seq_q, num_head_q, 128] bfloat16 (num_seq_q = mtp + 1).
+        q: [num_batch * num_seq_q, num_head_q, 128] bfloat16 (num_seq_q = mtp + 1).  num_head_q / num_head_kv must be
+            1, 2, 4, 8 or 16 (the ratios the prefill ops take); every ratio takes mtp 0..4.  Ratio 16 at mtp 3 / 4 (64 / 80 q
+            rows per kv head) is served as 2 slices of the kv head's q heads - its K / V are read once per slice: 1.4-1.5 x
+            the time of one pass at mtp 3 (2 x with num_seq_kvcache on the host), 2 x at mtp 4.
         kcache / vcache: paged caches, logical [num_blocks, block_size, num_head_kv, 128] bfloat16;
             any block/token/head strides (NHD-contiguous and HND-backed views both work).  Unused
             slots of a request's last block should be zero (they are masked anyway).
@@ -75,7 +78,10 @@ def attention_decode_fp8(
     softmax(Q K^T * qscale * kscale / sqrt(head_dim)) V * vscale, bfloat16 output.
 
     Args (beyond attention_decode_bf16):
-        q: [num_batch * num_seq_q, num_head_q, 128] float8_e4m3fn.
+        q: [num_batch * num_seq_q, num_head_q, 128] float8_e4m3fn.  num_head_q / num_head_kv must be 1, 2, 4, 8 or 16;
+            every ratio takes mtp 0..3.  Ratio 16 at mtp 2 / 3 (48 / 64 q rows per kv head) is served as 2 slices of the kv
+            head's q heads - its K / V are read twice: 1.4-1.6 x the time of one pass on pages of 32 / 64 tokens, 2 x on
+            pages of 16.
         kcache / vcache: paged caches of 1-byte elements (float8_e4m3fn).
         qscale: float32 [num_batch * num_seq_q, num_head_q] per-token per-head Q scale.
         kscale: float32 [1] (QPERTOKEN_PERHEAD_KPERTENSOR_VPERTENSOR) or the view of the K-cache

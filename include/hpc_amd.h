@@ -80,7 +80,22 @@ int hpc_assign_attention_decode_task_async(int* task_map, const int* num_seq_kvc
                                            int num_seq_q, int new_kv_included, int min_process_len,
                                            hpc_stream_t stream);
 
-/* ---- decode attention (paged KV, D = 128, GQA group 4 or 8) ----------------------------------------
+/* ---- decode attention (paged KV, D = 128, GQA group 1, 2, 4, 8 or 16) -------------------------------
+ * num_head_q / num_head_kv in {1, 2, 4, 8, 16} - the groups the prefill ops take; any other ratio is HPC_ERR_UNSUPPORTED.
+ * A call routes by its q rows per kv head, num_seq_q * group:
+ *   <= 16     head pairs (NHD pages, even kv head count, device lengths) or the first-generation one-block form
+ *             (HND pages, odd kv head count, NULL lengths): groups 1 and 2 at every num_seq_q, group 16 at num_seq_q 1;
+ *   17 ... 32 one kv head per workgroup (fp8: pages of 32 / 64, device lengths) or the first generation's two-block
+ *             form: group 16 at num_seq_q 2, group 8 at 3 / 4;
+ *   33 ... 48 bf16 only, group 8 at num_seq_q 5 and group 16 at num_seq_q 3: the first generation's three-block form;
+ *   group 16 beyond that (fp8 num_seq_q 3 / 4: 48 / 64 rows; bf16 4 / 5: 64 / 80): no wider form - the kv head's 16 q heads are
+ *             served as 2 slices of 8.  At num_seq_q 3 / 4 each slice is a virtual kv head of the one-head-per-workgroup form
+ *             that reads the real head's K / V: its bytes are requested twice, sibling slices run on the same XCD when the kv
+ *             head count divides or is a multiple of 8, and its L2 absorbs about half of the repeat (1.4-1.6 x the time of
+ *             one pass; profiles/gqa_groups_decode.txt).  Outside that form's conditions (device lengths; fp8: pages of 32 / 64;
+ *             num_batch * num_head_kv * 2 <= 16384), and at bf16 num_seq_q 5 (40 rows per slice: the three-block form), the call
+ *             runs as one first-generation pass per slice: 2 x the time of a pass.  No sliced call is refused.
+ * hpc_attention_decode_workspace_bytes is unchanged by slicing (partial slots are per workgroup).
  * reference: attention_decode_bf16_async / attention_decode_fp8_async,
  *            src/attention/decode/decode.h:17-35 (kernels under src/attention/decode/sm90/).
  * q [B*Sq, Hq, 128] (row stride ldQ elements), kcache/vcache logical [blocks, block_size, Hkv, 128]

@@ -1,6 +1,6 @@
 """Development tool: randomised cross-check of the fp8 decode forms - one kv head per workgroup (product for 17-32 q rows per kv head;
 development key 60 = 2 also below that) against the first generation (key 60 = 1), per-tensor and per-token K scales, NHD / HND
-pages of 32 / 64 tokens, both new_kv_included settings, random batches with empty, short and long requests.  The two kernels
+pages of 32 / 64 tokens, both new_kv_included settings, GQA groups 1 / 2 / 4 / 8 / 16, random batches with empty, short and long requests.  The two kernels
 split requests at different points, so outputs agree to fp rounding of the merges, not bit for bit: max |dy| <= 0.03 at |y| ~ 1.
 usage: python tools/fuzz_decode_forms.py [cases=40] [seed=0] [mode=pair]
 mode=pair: the head-pair form itself (product: even head counts, <= 16 q rows, NHD pages - incl. underloaded launches whose short
@@ -21,17 +21,20 @@ rnd = random.Random(seed)
 f8 = torch.float8_e4m3fn
 worst = 0.0
 for case in range(n_cases):
-    hkv, g = rnd.choice([(8, 8), (4, 8), (1, 8), (2, 8), (16, 8), (3, 8), (2, 4), (6, 4)])
+    # (kv heads, GQA group): groups 1, 2 and 16 beside 4 and 8 - both forms take every power of two up to 16 whose rows fit
+    hkv, g = rnd.choice([(8, 8), (4, 8), (1, 8), (2, 8), (16, 8), (3, 8), (2, 4), (6, 4),
+                         (8, 1), (3, 1), (8, 2), (2, 2), (4, 16), (1, 16), (2, 16)])
     hq = hkv * g
-    sq = rnd.choice([3, 4]) if g == 8 else 4
-    low = rnd.random() < 0.3          # <= 16 q rows: reachable through key 60 = 2 only
-    if low: sq = rnd.choice([1, 2]) if g == 8 else rnd.choice([1, 2, 4])
+    hi = [s for s in (1, 2, 3, 4) if 16 < s * g <= 32]   # one kv head per workgroup in the product
+    lo = [s for s in (1, 2, 3, 4) if s * g <= 16]        # <= 16 q rows: reachable through key 60 = 2 only
+    low = rnd.random() < 0.3 or not hi
+    sq = rnd.choice(lo if low else hi)
     P = rnd.choice([32, 64])
     hnd = rnd.random() < 0.5
     if PAIR:
-        hkv, g = rnd.choice([(8, 8), (4, 8), (2, 8), (16, 8), (2, 4), (6, 4)])
+        hkv, g = rnd.choice([(8, 8), (4, 8), (2, 8), (16, 8), (2, 4), (6, 4), (8, 1), (2, 1), (8, 2), (2, 2), (4, 16), (2, 16)])
         hq = hkv * g
-        sq = rnd.choice([1, 2]) if g == 8 else rnd.choice([1, 2, 4])
+        sq = rnd.choice([s for s in (1, 2, 3, 4) if s * g <= 16])
         P, hnd = rnd.choice([16, 32, 64]), False
     ktok = rnd.random() < 0.4 and P >= 32
     nkv = rnd.random() < 0.7

@@ -323,3 +323,61 @@ def ref_attn_by_kv_head(q, kvcache, block_ids, num_seq_q, lens_total, rows=None,
                 y = y * (v_scale / 256.0)
             out[oi, :, hs] = y.transpose(0, 1).to(torch.bfloat16)
     return out
+
+
+def ref_prefill_by_kv_head(q, kcache, vcache, cu_seqlens_q, block_ids, seqlens_kv, qscale=None, kscale=None, vscale=None,
+                           k_per_token=False, block_mask=None, q_chunk=512):
+    """ref_prefill_fp8 (qscale given) or ref_prefill_bf16 (qscale None; block_ids None: contiguous K / V) for long
+    requests: the same arithmetic one kv head and `q_chunk` q rows at a time, so that 20 000 cached tokens at 64 q heads
+    materialise neither an L x L `tril` nor `repeat_interleave(group)` of K / V (many GB).  Every q row still meets all L
+    keys of its request in one matmul / softmax, so its value does not depend on the chunking.  Bit-equal to the pinned
+    oracles, block mask and per-token K scales included (tests/test_prefill_bar.py)."""
+    total_q, hq, d = q.shape
+    hkv = kcache.shape[-2]
+    group = hq // hkv
+    fp8 = qscale is not None
+    out = torch.empty(total_q, hq, vcache.shape[-1], dtype=torch.bfloat16)
+    for b in range(cu_seqlens_q.numel() - 1):
+        a0, a1 = int(cu_seqlens_q[b]), int(cu_seqlens_q[b + 1])
+        sq = a1 - a0
+        if sq == 0:
+            continue
+        if block_ids is None:
+            L, ids = sq, None
+        else:
+            L, P = int(seqlens_kv[b]), kcache.shape[1]
+            ids = block_ids[b, : (L + P - 1) // P].long()
+        col = torch.arange(L)
+        for g in range(hkv):
+            hs = slice(g * group, (g + 1) * group)
+            if ids is None:
+                K, V = kcache[a0:a1, g], vcache[a0:a1, g]
+            else:
+                K, V = kcache[ids, :, g].reshape(-1, d)[:L], vcache[ids, :, g].reshape(-1, vcache.shape[-1])[:L]
+            BK = K.float().unsqueeze(0).expand(group, -1, -1)
+            BV = V.float().unsqueeze(0).expand(group, -1, -1)
+            if fp8 and k_per_token:
+                ksb = kscale[ids].contiguous().view(torch.float32)[:, :, g].reshape(-1)[:L].float()
+            for c0 in range(0, sq, q_chunk):
+                c1 = min(sq, c0 + q_chunk)
+                BQ = q[a0 + c0 : a0 + c1, hs].float().transpose(0, 1)
+                mask = col[None, :] <= (L - sq + torch.arange(c0, c1))[:, None]
+                if not fp8:
+                    scores = torch.matmul(BQ, BK.transpose(-2, -1)) / math.sqrt(d)
+                    scores = scores.masked_fill(~mask, float("-inf"))
+                    out[a0 + c0 : a0 + c1, hs] = torch.matmul(F.softmax(scores, dim=-1), BV).transpose(0, 1).to(torch.bfloat16)
+                    continue
+                scores = torch.matmul(BQ, BK.transpose(-2, -1)) * qscale[b, hs, c0:c1].unsqueeze(-1) / math.sqrt(d)
+                scores = scores * (ksb[None, None, :] if k_per_token else kscale[0])
+                if block_mask is not None:
+                    em = block_mask[b, hs].bool().repeat_interleave(128, dim=-2)[:, c0:c1, :]
+                    em = em.repeat_interleave(128, dim=-1)[:, :, :L]
+                    scores = scores.masked_fill(~em, float("-inf"))
+                scores = scores.masked_fill(~mask, float("-inf"))
+                w = torch.exp(scores - scores.max(dim=-1, keepdim=True)[0])
+                gsum = w.sum(dim=-1, keepdim=True)
+                w8 = (w * 256.0).to(torch.float8_e4m3fn).float()
+                o = torch.matmul(w8, BV) / gsum
+                o = o * vscale[g] / 256.0 if k_per_token else o * (vscale[0] / 256.0)
+                out[a0 + c0 : a0 + c1, hs] = o.transpose(0, 1).to(torch.bfloat16)
+    return out

@@ -7,7 +7,8 @@ import pytest
 import torch
 
 from oracle import attention as oattn
-from utils import allclose
+from prefill_needles import TAU_PREFILL_UNIFORM_BF16
+from utils import allclose, attn_close
 
 
 def paged_case(seq_q, seq_kv, hq, hkv, block_size, seed=41):
@@ -57,6 +58,7 @@ def test_attention_with_kvcache_prefill_bf16(num_batch, num_seq_q, num_seq_kv, k
     my = hpc.attention_with_kvcache_prefill_bf16(q.cuda(), kc, vc, cu.cuda(), bid.cuda(), lens.cuda(), num_seq_q, output=out)
     assert my.data_ptr() == out.data_ptr()
     assert allclose(gt, my.cpu(), atol=0.016, rtol=0.016)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_BF16)
 
 
 @pytest.mark.gpu
@@ -72,6 +74,7 @@ def test_prefill_bf16_paged_ragged(hq, hkv, block_size):
     my = hpc.attention_with_kvcache_prefill_bf16(q.cuda(), kvd[:, 0], kvd[:, 1], cu.cuda(), bid.cuda(), lens.cuda(),
                                                  max(seq_q))
     assert allclose(gt, my.cpu(), atol=0.016, rtol=0.016)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_BF16)
 
 
 @pytest.mark.gpu
@@ -92,6 +95,7 @@ def test_attention_prefill_bf16_contiguous(seq, hq, hkv, use_output):
     my = hpc.attention_prefill_bf16(q.cuda(), k.cuda(), v.cuda(), torch.tensor(seq, dtype=torch.int32).cuda(), cu.cuda(),
                                     max(seq), output=out)
     assert allclose(gt, my.cpu(), atol=0.016, rtol=0.016)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_BF16)
 
 
 @pytest.mark.dev
@@ -119,3 +123,4 @@ def test_prefill_bf16_transposing_reads_equal_the_perm_form(hq, hkv, block_size)
     assert torch.equal(new, old)
     gt = oattn.ref_prefill_bf16(q, kv[:, 0], kv[:, 1], cu, bid, lens)
     assert allclose(gt, new.cpu(), atol=0.016, rtol=0.016)
+    assert attn_close(gt, new.cpu(), TAU_PREFILL_UNIFORM_BF16)

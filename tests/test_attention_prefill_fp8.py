@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from oracle import attention as oattn
-from utils import allclose
+from prefill_needles import TAU_PREFILL_UNIFORM_FP8, TAU_PREFILL_UNIFORM_FP8_KTOK
+from utils import allclose, attn_close
 
 F8 = torch.float8_e4m3fn
 
@@ -67,6 +68,7 @@ def test_attention_with_kvcache_prefill_fp8(kv_layout, num_seq_q, use_output):
         assert my.data_ptr() == out.data_ptr()
     assert my.dtype == torch.bfloat16
     assert allclose(gt, my.cpu(), atol=0.1, rtol=0.02)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_FP8)
 
 
 @pytest.mark.gpu
@@ -84,6 +86,7 @@ def test_prefill_fp8_ragged_requests(hq, hkv, block_size):
     my = hpc.attention_with_kvcache_prefill_fp8(q.cuda(), kvd[:, 0], kvd[:, 1], qscale.cuda(), kscale.cuda(),
                                                 vscale.cuda(), cu.cuda(), bid.cuda(), lens.cuda(), max(seq_q))
     assert allclose(gt, my.cpu(), atol=0.1, rtol=0.02)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_FP8)
 
 
 @pytest.mark.gpu
@@ -121,6 +124,7 @@ def test_prefill_fp8_k_per_token(hq, hkv, block_size):
         cu.cuda(), bid.cuda(), lens.cuda(), max(seq_q),
         quant_type=hpc.QuantType.QPERTOKEN_PERHEAD_KPERTOKEN_PERHEAD_VPERHEAD)
     assert allclose(gt, my.cpu(), atol=0.1, rtol=0.02)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_FP8_KTOK)
 
 
 def block_sparse_mask(batch, heads, nrow, ncol, skip_ratio, gen):
@@ -157,6 +161,7 @@ def test_blocksparse_prefill_fp8(kv_layout, num_seq, skip_ratio, hq, hkv):
         q.cuda(), kc, vc, qscale.cuda(), kscale.cuda(), vscale.cuda(), cu.cuda(), bid.cuda(), lens.cuda(), num_seq,
         block_mask=None if bm is None else bm.to(torch.uint8).cuda())
     assert allclose(gt, my.cpu(), atol=0.1, rtol=0.02)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_FP8)
 
 
 @pytest.mark.gpu
@@ -182,3 +187,4 @@ def test_blocksparse_prefill_fp8_cached_prefix_and_ragged():
         q.cuda(), kvd[:, 0], kvd[:, 1], qscale.cuda(), kscale.cuda(), vscale.cuda(), cu.cuda(), bid.cuda(),
         lens.cuda(), max(seq_q), block_mask=bm.to(torch.uint8).cuda())
     assert allclose(gt, my.cpu(), atol=0.1, rtol=0.02)
+    assert attn_close(gt, my.cpu(), TAU_PREFILL_UNIFORM_FP8)

@@ -1,13 +1,12 @@
 // Paged decode attention for gfx950: bf16 and fp8 (e4m3) KV, D=128, GQA group 1/2/4/8/16 (the groups the prefill
 // ops take), dynamic split-KV task map, plus the split-KV combine kernel.  The kernels address q rows as
-// row >> g_shift, row & (G - 1) with G read at run time; a call routes by its q rows per kv head (num_seq_q * G): <= 16
-// head pairs or this file's one-block form, 17 ... 32 one kv head per workgroup (attention_decode_v2.hip) or the two-block
-// form, 33 ... 48 bf16 three blocks; group 16 with more rows than a form holds is served as slices of a kv head's q
-// heads (decode_slices() below).
+// row >> g_shift, row & (G - 1) with G read at run time.  Which form and grid a call runs - this file's one-, two- or three-block
+// form or the second generation (attention_decode_v2.hip) - is decided by decode_route() (attention_decode_route.h); the C entries
+// at the end of this file validate, route, fill the argument block of the chosen generation and launch.
 //
 // Replaces reference src/attention/decode/sm90/{dynamic,static}/smallm_{bf16,fp8_*}_dim128_*.cu(h)
 // and src/attention/decode/splitk_combine_kernels.cuh (static split-K becomes "schedule on the
-// fly", see hpc/_entry_attention.py).
+// fly", see assign_task.hip).
 //
 // MI355X design (HBM-bound op: 256/512 B of KV per token per kv-head, ~8 FLOP/B):
 //  * KV is streamed HBM -> VGPR with 16-byte (fp8 V: 8-byte) non-temporal buffer loads, every load
@@ -66,7 +65,7 @@ struct Args {
   const float* vscale;  // fp8: [1] or [Hkv]
   int num_batch, num_seq_q, num_head_kv, g_shift, page_shift, max_blocks;
   int hq_shift;  // q heads per kv head in MEMORY, log2: kv head h's q heads (and q scales, y rows) start at h << hq_shift.  = g_shift
-                 // except in a pass over one slice of a group-16 kv head's q heads (launch_sliced: g_shift is the slice's group)
+                 // except in a pass over one slice of a group-16 kv head's q heads (DecodeRoute::passes: g_shift is the slice's group)
   int ldq, ldy, qscale_stride;
   int solo_ok;  // bins full of short tasks may run one task per wave (tuning key kDevDecodeNoWaveSolo = 1 turns it off)
   long k_block_stride, k_token_stride, k_head_stride;  // elements
@@ -703,138 +702,47 @@ __global__ __launch_bounds__(kThreads) void decode_combine_kernel(const Args a, 
   st16(dst, pk);
 }
 
+// One launch of the main kernel per pass (DecodeRoute::passes, attention_decode_route.h).  Two passes serve group 16 with more q rows per
+// kv head than a form holds: one per slice of 8 adjacent q heads, the slice's q heads, q scales and y rows reached through offset base
+// pointers and hq_shift (g_shift is the slice's group); K / V, the task map and the scratch are the call's - the passes run one after
+// the other in the stream and each leaves the arrival counters zero.  Every pass streams the whole cache: 2 x the time of one.
 template <bool kFp8, int kQuant>
-int launch(const Args& a, int num_bins, int num_nb, hipStream_t stream) {
+int launch(Args a, const DecodeRoute& r, hipStream_t stream) {
   const bool temporal = hpc_dev_tuning_get(kDevDecodeKvTemporal) == 1;
 #define HPC_DECODE_LAUNCH(NB)                                                                   \
   if (temporal)                                                                                 \
-    decode_kernel<kFp8, kQuant, NB, 0><<<num_bins, kThreads, 0, stream>>>(a);                   \
+    decode_kernel<kFp8, kQuant, NB, 0><<<r.num_wg, kThreads, 0, stream>>>(a);                   \
   else                                                                                          \
-    decode_kernel<kFp8, kQuant, NB, 2><<<num_bins, kThreads, 0, stream>>>(a)
-  if (num_nb == 1) {
-    HPC_DECODE_LAUNCH(1);
-  } else if (num_nb == 2) {
-    HPC_DECODE_LAUNCH(2);
-  } else if (num_nb == 3) {
-    if constexpr (kFp8) {
-      return HPC_ERR_UNSUPPORTED;  // fp8 supports num_seq_q <= 4
+    decode_kernel<kFp8, kQuant, NB, 2><<<r.num_wg, kThreads, 0, stream>>>(a)
+  for (int pass = 0; pass < r.passes; ++pass) {
+    if (r.num_nb == 1) {
+      HPC_DECODE_LAUNCH(1);
+    } else if (r.num_nb == 2) {
+      HPC_DECODE_LAUNCH(2);
+    } else if constexpr (kFp8) {
+      return HPC_ERR_UNSUPPORTED;  // three blocks: bf16 only (fp8 has num_seq_q <= 4)
     } else {
       HPC_DECODE_LAUNCH(3);
     }
-  } else {
-    return HPC_ERR_UNSUPPORTED;
+    HPC_CHECK_LAUNCH();
+    if (r.combine_kernel) {  // more (kv head, request) pairs than arrival counters: the chunks are merged by a second launch
+      decode_combine_kernel<<<a.num_batch * a.num_head_kv * r.num_nb, kThreads, 0, stream>>>(a, r.num_nb);
+      HPC_CHECK_LAUNCH();
+    }
+    a.q = static_cast<const uint8_t*>(a.q) + 8 * 128 * (kFp8 ? 1 : 2);  // the next slice
+    a.y += 8 * 128;
+    if (a.qscale) a.qscale += 8;
   }
 #undef HPC_DECODE_LAUNCH
-  HPC_CHECK_LAUNCH();
-  if (!a.arrive) {  // more (kv head, request) pairs than arrival counters: the chunks are merged by a second launch
-    decode_combine_kernel<<<a.num_batch * a.num_head_kv * num_nb, kThreads, 0, stream>>>(a, num_nb);
-    HPC_CHECK_LAUNCH();
-  }
   return HPC_OK;
-}
-
-// Group 16 with more q rows per kv head than a form holds, on the first generation: one pass per slice of 8 adjacent q heads
-// (24 / 32 rows: two blocks; bf16 40 rows: three), the slice's q heads, q scales and y rows reached through offset base pointers
-// and hq_shift; K / V, the task map and the scratch are the call's - the passes run one after the other in the stream and each
-// leaves the arrival counters zero.  Every pass streams the whole cache: 2 x the time of one.  Serves the sliced calls that the
-// one-head-per-workgroup form (attention_decode_v2.hip, virtual heads) cannot take: fp8 on pages of 16, lengths on the host, more
-// arrival counters than 64 KB.
-template <bool kFp8, int kQuant>
-int launch_sliced(const Args& a, int num_bins, hipStream_t stream) {
-  constexpr int kSliceShift = 3;  // 8 q heads
-  Args s = a;
-  s.g_shift = kSliceShift;
-  const int num_nb = ((a.num_seq_q << kSliceShift) + 15) / 16;
-  for (int sl = 0; sl < (1 << (a.g_shift - kSliceShift)); ++sl) {
-    const long heads = static_cast<long>(sl) << kSliceShift;
-    s.q = static_cast<const uint8_t*>(a.q) + heads * 128 * (kFp8 ? 1 : 2);
-    s.y = a.y + heads * 128;
-    s.qscale = a.qscale ? a.qscale + heads : nullptr;
-    const int rc = launch<kFp8, kQuant>(s, num_bins, num_nb, stream);
-    if (rc != HPC_OK) return rc;
-  }
-  return HPC_OK;
-}
-
-struct Common {
-  int num_nb;
-  int code;
-};
-
-inline Common fill_common(Args& a, void* y_ptr, void* workspace, const int* task_map_ptr,
-                          const void* q_ptr, const void* kcache_ptr, const void* vcache_ptr,
-                          const int* block_ids_ptr, int num_bins, int num_batch, int num_seq_q,
-                          int num_head_q, int num_head_kv, int num_dim_qk, int num_dim_v,
-                          int block_size, int num_seq_max_blocks, int ldY, int ldQ, int64_t kbs,
-                          int64_t kts, int64_t khs, int64_t vbs, int64_t vts, int64_t vhs, int align) {
-  Common c{0, HPC_OK};
-  if (!y_ptr || !workspace || !task_map_ptr || !q_ptr || !kcache_ptr || !vcache_ptr || !block_ids_ptr) {
-    c.code = HPC_ERR_INVALID;
-    return c;
-  }
-  if (num_dim_qk != 128 || num_dim_v != 128 ||
-      (block_size != 16 && block_size != 32 && block_size != 64)) {
-    c.code = HPC_ERR_UNSUPPORTED;
-    return c;
-  }
-  if (num_head_kv <= 0 || num_head_q % num_head_kv || num_batch <= 0 || num_bins <= 0) {
-    c.code = HPC_ERR_INVALID;
-    return c;
-  }
-  const int group = num_head_q / num_head_kv;
-  // powers of two up to 16: q rows are addressed by shift and mask (the prefill ops take the same set)
-  if ((group != 1 && group != 2 && group != 4 && group != 8 && group != 16) || num_seq_q < 1 || num_seq_q > 5) {
-    c.code = HPC_ERR_UNSUPPORTED;
-    return c;
-  }
-  const int m = align - 1;  // elements per 16 bytes - 1
-  if ((ldQ & m) || (ldY & 7) || (kts & m) || (vts & m) || (khs & m) || (vhs & m) || (kbs & m) || (vbs & m)) {
-    c.code = HPC_ERR_UNSUPPORTED;  // 16-byte vector accesses
-    return c;
-  }
-  c.num_nb = (num_seq_q * group + 15) / 16;
-  a.q = q_ptr;
-  a.kcache = kcache_ptr;
-  a.vcache = vcache_ptr;
-  a.block_ids = block_ids_ptr;
-  a.task_map = task_map_ptr;
-  a.y = static_cast<uint16_t*>(y_ptr);
-  // the workspace starts with the arrival counters of split requests (zero-once region, shared with the second
-  // generation: one of the two runs per call); development key kDevDecodeCombineKernel = 1: the round-1 form (combine kernel)
-  a.arrive = static_cast<int64_t>(num_batch) * num_head_kv * 4 <= hpc::decode2::kCounterBytes && hpc_dev_tuning_get(kDevDecodeCombineKernel) != 1
-                 ? static_cast<int*>(workspace) : nullptr;
-  char* ws = static_cast<char*>(workspace) + hpc::decode2::kCounterBytes;
-  a.part_o = reinterpret_cast<float*>(ws);
-  ws += static_cast<int64_t>(num_bins) * 2 * 16 * c.num_nb * 128 * 4;
-  a.part_lse = reinterpret_cast<float*>(ws);
-  ws += static_cast<int64_t>(num_bins) * 2 * 16 * c.num_nb * 4;
-  a.first_bin = reinterpret_cast<int*>(ws);
-  a.qscale = a.kscale = a.vscale = nullptr;
-  a.num_batch = num_batch;
-  a.num_seq_q = num_seq_q;
-  a.num_head_kv = num_head_kv;
-  a.g_shift = a.hq_shift = __builtin_ctz(static_cast<unsigned>(group));
-  a.page_shift = block_size == 64 ? 6 : (block_size == 32 ? 5 : 4);
-  a.max_blocks = num_seq_max_blocks;
-  a.solo_ok = hpc_dev_tuning_get(kDevDecodeNoWaveSolo) != 1;
-  a.ldq = ldQ;
-  a.ldy = ldY;
-  a.qscale_stride = 0;
-  a.k_block_stride = kbs;
-  a.k_token_stride = kts;
-  a.k_head_stride = khs;
-  a.v_block_stride = vbs;
-  a.v_token_stride = vts;
-  a.v_head_stride = vhs;
-  a.ks_block_stride = a.ks_row_stride = a.ks_head_stride = 0;
-  a.scale_log2 = 0.08838834764831845f * 1.4426950408889634f;  // 1/sqrt(128) * log2(e)
-  return c;
 }
 
 }  // namespace decode
 }  // namespace hpc
 
 namespace {
+using namespace hpc;
+
 int64_t v1_workspace_bytes(int num_bins, int num_batch, int num_head_kv, int num_seq_q, int heads_per_group) {
   const int64_t rows = (static_cast<int64_t>(num_seq_q) * heads_per_group + 15) / 16 * 16;
   const int64_t part_o = static_cast<int64_t>(num_bins) * 2 * rows * 128 * 4;
@@ -844,10 +752,10 @@ int64_t v1_workspace_bytes(int num_bins, int num_batch, int num_head_kv, int num
 }
 }  // namespace
 
-// Scratch of one decode call: [arrival counters of the second-generation kernel: hpc_attention_decode_workspace_zero_bytes()
-// bytes that must be zero the first time the buffer is used and are left zero by every call] [the first-generation
-// kernel's region: 2 partial slots per bin, first-bin table] [the second-generation FP8 / NHD kernel's partial slots:
-// 2 per workgroup x 2 heads; its grid never exceeds num_bins workgroups].
+// Scratch of one decode call: [arrival counters: hpc_attention_decode_workspace_zero_bytes() bytes that must be zero the first time
+// the buffer is used and are left zero by every call; shared by the two generations, one of which runs per call] [the first
+// generation's region: 2 partial slots per bin, first-bin table] [the second generation's partial slots: 2 per workgroup x 2 heads;
+// its grid never exceeds num_bins workgroups].
 extern "C" int64_t hpc_attention_decode_workspace_bytes(int num_bins, int num_batch, int num_head_kv,
                                                         int num_seq_q, int heads_per_group) {
   if (num_bins <= 0 || num_batch <= 0 || num_head_kv <= 0 || num_seq_q <= 0 || heads_per_group <= 0)
@@ -857,8 +765,6 @@ extern "C" int64_t hpc_attention_decode_workspace_bytes(int num_bins, int num_ba
 }
 extern "C" int64_t hpc_attention_decode_workspace_zero_bytes(void) { return hpc::decode2::kCounterBytes; }
 
-// development (tools/prof_decode.py): device buffer [workgroups][4 waves][12] uint64 that the profiling build of the
-// second-generation kernel fills with per-wave s_memtime sums; null = the shipped kernel
 #ifdef HPC_DEV
 // development build: number of arrivals (either kernel generation) that drew a ticket above their request's chunk count
 // since the last reset - a stale arrival counter (a caller-owned workspace that was never zeroed makes the
@@ -872,65 +778,170 @@ extern "C" int hpc_dev_decode_ticket_overruns(int reset) {
   const int v2 = hpc::decode2::ticket_overruns(reset != 0);
   return v2 < 0 ? -1 : v + v2;
 }
+// development (tools/prof_decode.py): device buffer [workgroups][4 waves][12] uint64 that the profiling build of the
+// second-generation kernel fills with per-wave s_memtime sums; null = the shipped kernel
 static void* g_decode_prof = nullptr;
 extern "C" int hpc_dev_decode_prof_buffer(void* p) {
   g_decode_prof = p;
   return 0;
 }
+// development (tests/test_decode_route.py): decode_route() on flat arrays, the members of DecodeCall and DecodeRoute in their order
+extern "C" int hpc_dev_decode_route(const int64_t* call, int n_in, int* route, int n_out) {
+  if (!call || !route || n_in != 19 || n_out != 9) return HPC_ERR_INVALID;
+  const auto i = [call](int k) { return static_cast<int>(call[k]); };
+  const DecodeCall c{call[0] != 0, i(1),     call[2] != 0, i(3),     i(4),     i(5),     i(6),     i(7),     i(8),    call[9],
+                     call[10],     call[11], call[12],     call[13], call[14], call[15], call[16], call[17], i(18)};
+  const DecodeRoute r = decode_route(c);
+  const int out[9] = {r.code, r.generation, r.mode, r.hnd, r.share_shift, r.passes, r.num_nb, r.num_wg, r.combine_kernel};
+  for (int k = 0; k < 9; ++k) route[k] = out[k];
+  return HPC_OK;
+}
 #else
 static constexpr void* g_decode_prof = nullptr;  // production build: the profiling instantiations are not emitted
 #endif
 
-// Group 16 with more q rows per kv head than any form holds (`max_rows`: fp8 32; bf16 48 - the first generation's three-block form
-// runs 16 x 3 rows in one pass, 319 / 395 us against 365 / 503 us as two slices on the C3 mix / uniform 8k at 8 kv heads,
-// profiles/gqa_groups_decode.txt): the kv head's 16 q heads are served as two slices of 8 adjacent q heads.
-//  * num_seq_q 3, 4 (24 / 32 rows per slice): each slice is a virtual kv head of the one-head-per-workgroup form.  A slice's q
-//    heads, q scales and y rows are contiguous at (virtual head) << 3 - what that kernel computes for a real head of group 8;
-//    only K / V / K-scale / V-scale addresses use the real head (decode2::Args::share_shift = 1).  A kv head's K / V bytes are
-//    requested once per slice; sibling slices share an XCD's L2 where the kv head count allows (see the kernel): 1.40-1.58 x the
-//    time of one pass.  A call that form cannot take (fp8 on pages of 16, host lengths, more arrival counters than 64 KB,
-//    development keys that switch the second generation off) runs as one first-generation pass per slice (launch_sliced: 2 x).
-//  * bf16 num_seq_q 5 (40 rows per slice): two passes of the first generation's three-block form, 599 / 755 us - measured
-//    against four slices of 20 rows on the one-head form: 659 / 899 us.
-// Returns share_shift for the one-head form (0: not sliced, or sliced on the first generation only - see `sliced`).
-static int decode_slices(int num_seq_q, int group, int max_rows, bool* sliced) {
-  *sliced = group == 16 && num_seq_q * group > max_rows;
-  return *sliced && num_seq_q * 8 <= 32 ? 1 : 0;
+namespace {
+// What a C entry was given (include/hpc_amd.h), fp8 or bf16 (no scales, quant_type 1); K / V strides in ELEMENTS, K-scale strides in bytes.
+struct Entry {
+  bool fp8;
+  void *y, *workspace;
+  const int* task_map;
+  const void *q, *kcache, *vcache;
+  const int *block_ids, *lens;
+  const float* qscale;
+  const void* kscale;
+  const float* vscale;
+  int new_kv_included, quant_type, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, num_dim_qk, num_dim_v, block_size, max_blocks;
+  int qscale_stride, ldY, ldQ;
+  int64_t k_block_stride, k_token_stride, k_head_stride, v_block_stride, v_token_stride, v_head_stride;
+  int64_t ks_block_stride, ks_row_stride, ks_head_stride;
+  hipStream_t stream;
+  int eb() const { return fp8 ? 1 : 2; }  // bytes per element
+  int g_shift() const { return __builtin_ctz(static_cast<unsigned>(num_head_q / num_head_kv)); }
+};
+constexpr float kScaleLog2 = 0.08838834764831845f * 1.4426950408889634f;  // 1/sqrt(128) * log2(e)
+
+// What decode_route() does not see: the operands and the row strides of q and y.  The two halves refuse in the order the entries
+// always did - fp8 scales, fp8 form, operands, head dims | page size, counts, group, rows, K / V alignment (the route) | ldQ, ldY.
+int check_operands(const Entry& e) {
+  if (e.fp8 && (!e.qscale || !e.kscale || !e.vscale)) return HPC_ERR_INVALID;
+  if (e.fp8 && ((e.quant_type != 0 && e.quant_type != 1) || e.num_seq_q > 4)) return HPC_ERR_UNSUPPORTED;  // the route's first refusal
+  if (!e.y || !e.workspace || !e.task_map || !e.q || !e.kcache || !e.vcache || !e.block_ids) return HPC_ERR_INVALID;
+  return e.num_dim_qk == 128 && e.num_dim_v == 128 ? HPC_OK : HPC_ERR_UNSUPPORTED;
 }
 
-// Second generation (attention_decode_v2.hip: head pairs per load, deep prefetch, in-kernel plan and merge) when the
-// layout allows it.  Returns HPC_OK when it launched, 1 when the call is not its case (the caller goes on to the
-// first generation), a negative code on a launch error.  Strides in `b` are BYTES.
-// `share_shift` > 0: the call is served as 1 << share_shift slices per kv head (decode_slices() above) - the kernel sees
-// num_head_kv << share_shift virtual heads of group (num_head_q / num_head_kv) >> share_shift, one per workgroup.
-static int try_second_generation(hpc::decode2::Args& b, void* workspace, int num_bins, int num_batch, int num_seq_q,
-                                 int num_head_q, int num_head_kv, int block_size, int64_t k_head_stride_bytes,
-                                 int64_t v_head_stride_bytes, hipStream_t stream, int share_shift = 0) {
-  b.share_shift = share_shift;
-  b.num_head_kv = num_head_kv << share_shift;
-  b.g_shift = __builtin_ctz(static_cast<unsigned>(num_head_q / b.num_head_kv));
-  b.part_o = b.part_lse = nullptr;
-  b.arrive = nullptr;
-  b.dev_nomem = hpc_dev_tuning_get(kDevDecodeNoKvLoads);
-  b.min_range_cost = hpc_dev_tuning_get(kDevDecodeMinRangeCost) > 0 ? hpc_dev_tuning_get(kDevDecodeMinRangeCost) : 8;  // development key kDevDecodeMinRangeCost overrides (15 x 64 + 1 x 16k tokens: 87 us without a floor, 47 / 49 / 61 / 105 us at 8 / 16 / 32 / 64)
-  b.prof = g_decode_prof;
-  if (hpc_dev_tuning_get(kDevDecodeFp8NoPair) == 1) return 1;  // development key kDevDecodeFp8NoPair = 1: first generation only
-  const int mode = hpc::decode2::mode_of(b, num_head_q, block_size, k_head_stride_bytes, v_head_stride_bytes);
+DecodeCall describe(const Entry& e) {
   int dev = 0;
-  if (mode == 0 || hipGetDevice(&dev) != hipSuccess) return 1;
-  if (share_shift > 0 && mode != 3) return 1;
-  const int unit = mode == 3 ? b.num_head_kv : num_head_kv / (mode == 2 ? 4 : 2);  // workgroup = (token range, head pair, quad or (virtual) head)
-  int num_wg = 2 * hpc_get_cu_count(dev);  // two 4-wave workgroups per CU (<= 256 registers, 65 KB of LDS each)
-  const int wg_dev = hpc_dev_tuning_get(kDevDecodeGrid);
-  if (wg_dev > 0) num_wg = wg_dev;
-  if (num_wg > num_bins) num_wg = num_bins;  // the scratch is sized for num_bins workgroups
-  num_wg -= num_wg % unit;
-  if (num_wg <= 0) return 1;  // fewer bins than head pairs: the first generation takes it
-  char* base = static_cast<char*>(workspace);
-  char* part = base + hpc::decode2::kCounterBytes +
-               v1_workspace_bytes(num_bins, num_batch, num_head_kv, num_seq_q, num_head_q / num_head_kv);
-  return hpc::decode2::launch(b, base, part, num_wg, mode, stream);
+  const int cus = hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
+  return {!e.fp8, e.quant_type, e.lens != nullptr, e.num_bins, e.num_batch, e.num_seq_q, e.num_head_q, e.num_head_kv, e.block_size,
+          e.k_block_stride * e.eb(), e.k_token_stride * e.eb(), e.k_head_stride * e.eb(), e.v_block_stride * e.eb(),
+          e.v_token_stride * e.eb(), e.v_head_stride * e.eb(), e.ks_block_stride, e.ks_row_stride, e.ks_head_stride, cus};
 }
+
+// The first generation's argument block.  Strides in elements.
+decode::Args fill_first(const Entry& e, const DecodeRoute& r) {
+  decode::Args a;
+  a.q = e.q;
+  a.kcache = e.kcache;
+  a.vcache = e.vcache;
+  a.block_ids = e.block_ids;
+  a.task_map = e.task_map;
+  a.y = static_cast<uint16_t*>(e.y);
+  // the workspace starts with the arrival counters of split requests (zero-once region)
+  a.arrive = r.combine_kernel ? nullptr : static_cast<int*>(e.workspace);
+  const int64_t rows = (e.num_seq_q * (e.num_head_q / e.num_head_kv) + 15) / 16 * 16;  // of the whole call, as v1_workspace_bytes()
+  a.part_o = reinterpret_cast<float*>(static_cast<char*>(e.workspace) + decode2::kCounterBytes);
+  a.part_lse = a.part_o + e.num_bins * 2 * rows * 128;
+  a.first_bin = reinterpret_cast<int*>(a.part_lse + e.num_bins * 2 * rows);
+  a.qscale = e.qscale;
+  a.kscale = static_cast<const float*>(e.kscale);
+  a.vscale = e.vscale;
+  a.num_batch = e.num_batch;
+  a.num_seq_q = e.num_seq_q;
+  a.num_head_kv = e.num_head_kv;
+  a.hq_shift = e.g_shift();
+  a.g_shift = r.passes > 1 ? 3 : a.hq_shift;  // a pass serves a slice of 8 q heads
+  a.page_shift = __builtin_ctz(static_cast<unsigned>(e.block_size));
+  a.max_blocks = e.max_blocks;
+  a.solo_ok = hpc_dev_tuning_get(kDevDecodeNoWaveSolo) != 1;
+  a.ldq = e.ldQ;
+  a.ldy = e.ldY;
+  a.qscale_stride = e.qscale_stride;
+  a.k_block_stride = e.k_block_stride;
+  a.k_token_stride = e.k_token_stride;
+  a.k_head_stride = e.k_head_stride;
+  a.v_block_stride = e.v_block_stride;
+  a.v_token_stride = e.v_token_stride;
+  a.v_head_stride = e.v_head_stride;
+  a.ks_block_stride = e.ks_block_stride;
+  a.ks_row_stride = e.ks_row_stride;
+  a.ks_head_stride = e.ks_head_stride;
+  a.scale_log2 = kScaleLog2;
+  return a;
+}
+
+// The second generation's argument block, but for the members that decode2::launch() derives from the grid.  Strides in BYTES; the
+// kernel sees num_head_kv << share_shift virtual heads of group (num_head_q / num_head_kv) >> share_shift (decode2::Args::share_shift).
+decode2::Args fill_second(const Entry& e, const DecodeRoute& r) {
+  decode2::Args b;
+  b.q = e.q;
+  b.kcache = e.kcache;
+  b.vcache = e.vcache;
+  b.block_ids = e.block_ids;
+  b.lens = e.lens;
+  b.task_map = e.task_map;
+  b.y = static_cast<uint16_t*>(e.y);
+  char* ws = static_cast<char*>(e.workspace);
+  b.arrive = reinterpret_cast<int*>(ws);
+  b.part_o = reinterpret_cast<float*>(ws + decode2::kCounterBytes + v1_workspace_bytes(e.num_bins, e.num_batch, e.num_head_kv, e.num_seq_q,
+                                                                                      e.num_head_q / e.num_head_kv));
+  b.part_lse = b.part_o + static_cast<int64_t>(r.num_wg) * 2 * 2 * 16 * 128;
+  b.qscale = e.qscale;
+  b.kscale = static_cast<const float*>(e.kscale);
+  b.vscale = e.vscale;
+  b.num_batch = e.num_batch;
+  b.num_seq_q = e.num_seq_q;
+  b.num_head_kv = e.num_head_kv << r.share_shift;
+  b.g_shift = e.g_shift() - r.share_shift;
+  b.page_shift = __builtin_ctz(static_cast<unsigned>(e.block_size));
+  b.max_blocks = e.max_blocks;
+  b.ldq = e.ldQ * e.eb();
+  b.ldy = e.ldY;
+  b.qscale_stride = e.qscale_stride;
+  b.new_kv_included = e.new_kv_included;
+  b.share_shift = r.share_shift;
+  // development key kDevDecodeMinRangeCost overrides (15 x 64 + 1 x 16k tokens: 87 us without a floor, 47 / 49 / 61 / 105 us at 8 / 16 / 32 / 64)
+  b.min_range_cost = hpc_dev_tuning_get(kDevDecodeMinRangeCost) > 0 ? hpc_dev_tuning_get(kDevDecodeMinRangeCost) : 8;
+  b.bf16 = !e.fp8;
+  b.ktok = e.fp8 && e.quant_type == 0;
+  b.dev_nomem = hpc_dev_tuning_get(kDevDecodeNoKvLoads);
+  b.k_block_stride = e.k_block_stride * e.eb();
+  b.k_token_stride = e.k_token_stride * e.eb();
+  b.v_block_stride = e.v_block_stride * e.eb();
+  b.v_token_stride = e.v_token_stride * e.eb();
+  b.ks_block_stride = e.ks_block_stride;
+  b.ks_row_stride = e.ks_row_stride;
+  b.ks_head_stride = e.ks_head_stride;
+  b.hnd = r.hnd;
+  b.k_head_stride = e.k_head_stride * e.eb();
+  b.v_head_stride = e.v_head_stride * e.eb();
+  b.scale_log2 = kScaleLog2;
+  b.prof = g_decode_prof;
+  return b;
+}
+
+// validate, route, fill the argument block of the generation that runs, launch
+int run(const Entry& e) {
+  if (const int rc = check_operands(e); rc != HPC_OK) return rc;
+  const DecodeRoute r = decode_route(describe(e));
+  if (r.code != HPC_OK) return r.code;
+  if ((e.ldQ * e.eb() & 15) || (e.ldY & 7)) return HPC_ERR_UNSUPPORTED;  // 16-byte vector accesses
+  if (r.generation == 2) return decode2::launch(fill_second(e, r), r, e.stream);
+  const decode::Args a = fill_first(e, r);
+  if (!e.fp8) return decode::launch<false, 1>(a, r, e.stream);
+  return e.quant_type == 1 ? decode::launch<true, 1>(a, r, e.stream) : decode::launch<true, 0>(a, r, e.stream);
+}
+}  // namespace
 
 extern "C" int hpc_attention_decode_bf16_async(
     void* y_ptr, void* workspace, const int* task_map_ptr, const void* q_ptr, const void* kcache_ptr,
@@ -939,50 +950,10 @@ extern "C" int hpc_attention_decode_bf16_async(
     int num_seq_max_blocks, int ldY, int ldQ, int64_t kcache_block_stride,
     int64_t kcache_token_stride, int64_t kcache_head_stride, int64_t vcache_block_stride,
     int64_t vcache_token_stride, int64_t vcache_head_stride, hipStream_t stream) {
-  using namespace hpc::decode;
-  Args a;
-  const Common c = fill_common(a, y_ptr, workspace, task_map_ptr, q_ptr, kcache_ptr, vcache_ptr,
-                               block_ids_ptr, num_bins, num_batch, num_seq_q, num_head_q,
-                               num_head_kv, num_dim_qk, num_dim_v, block_size, num_seq_max_blocks,
-                               ldY, ldQ, kcache_block_stride, kcache_token_stride,
-                               kcache_head_stride, vcache_block_stride, vcache_token_stride,
-                               vcache_head_stride, 8);
-  if (c.code != HPC_OK) return c.code;
-  bool sliced = false;
-  const int share_shift = decode_slices(num_seq_q, num_head_q / num_head_kv, 48, &sliced);
-  if (num_seq_kvcache_ptr && hpc_dev_tuning_get(kDevDecodeBf16NoPair) != 1 && sliced == (share_shift > 0)) {  // development key kDevDecodeBf16NoPair = 1: bf16 on the first generation only
-    hpc::decode2::Args b;
-    b.q = q_ptr;
-    b.kcache = kcache_ptr;
-    b.vcache = vcache_ptr;
-    b.block_ids = block_ids_ptr;
-    b.lens = num_seq_kvcache_ptr;
-    b.task_map = task_map_ptr;
-    b.y = static_cast<uint16_t*>(y_ptr);
-    b.qscale = b.kscale = b.vscale = nullptr;
-    b.num_batch = num_batch;
-    b.num_seq_q = num_seq_q;
-    b.num_head_kv = num_head_kv;
-    b.g_shift = a.g_shift;
-    b.page_shift = a.page_shift;
-    b.max_blocks = num_seq_max_blocks;
-    b.ldq = ldQ * 2;  // bytes
-    b.ldy = ldY;
-    b.qscale_stride = 0;
-    b.new_kv_included = new_kv_included;
-    b.bf16 = 1;
-    b.k_block_stride = kcache_block_stride * 2;
-    b.k_token_stride = kcache_token_stride * 2;
-    b.v_block_stride = vcache_block_stride * 2;
-    b.v_token_stride = vcache_token_stride * 2;
-    b.ks_block_stride = b.ks_row_stride = b.ks_head_stride = 0;
-    b.scale_log2 = a.scale_log2;
-    const int rc = try_second_generation(b, workspace, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, block_size,
-                                         kcache_head_stride * 2, vcache_head_stride * 2, stream, share_shift);
-    if (rc <= 0) return rc;
-  }
-  if (sliced) return launch_sliced<false, 1>(a, num_bins, stream);
-  return launch<false, 1>(a, num_bins, c.num_nb, stream);
+  return run({false, y_ptr, workspace, task_map_ptr, q_ptr, kcache_ptr, vcache_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, nullptr,
+              nullptr, new_kv_included, 1, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, num_dim_qk, num_dim_v, block_size,
+              num_seq_max_blocks, 0, ldY, ldQ, kcache_block_stride, kcache_token_stride, kcache_head_stride, vcache_block_stride,
+              vcache_token_stride, vcache_head_stride, 0, 0, 0, stream});
 }
 
 extern "C" int hpc_attention_decode_fp8_async(
@@ -994,70 +965,9 @@ extern "C" int hpc_attention_decode_fp8_async(
     int64_t kcache_token_stride, int64_t kcache_head_stride, int64_t vcache_block_stride,
     int64_t vcache_token_stride, int64_t vcache_head_stride, int64_t kscale_block_stride,
     int64_t kscale_row_stride, int64_t kscale_head_stride, hipStream_t stream) {
-  using namespace hpc::decode;
-  if (!qscale_ptr || !kscale_ptr || !vscale_ptr) return HPC_ERR_INVALID;
-  if (quant_type != 0 && quant_type != 1) return HPC_ERR_UNSUPPORTED;
-  if (num_seq_q > 4) return HPC_ERR_UNSUPPORTED;
-  Args a;
-  const Common c = fill_common(a, y_ptr, workspace, task_map_ptr, q_ptr, kcache_ptr, vcache_ptr,
-                               block_ids_ptr, num_bins, num_batch, num_seq_q, num_head_q,
-                               num_head_kv, num_dim_qk, num_dim_v, block_size, num_seq_max_blocks,
-                               ldY, ldQ, kcache_block_stride, kcache_token_stride,
-                               kcache_head_stride, vcache_block_stride, vcache_token_stride,
-                               vcache_head_stride, 16);
-  if (c.code != HPC_OK) return c.code;
-  if (quant_type == 0 && block_size < 32) return HPC_ERR_UNSUPPORTED;  // scale rows hold 32 tokens
-  a.qscale = qscale_ptr;
-  a.kscale = static_cast<const float*>(kscale_ptr);
-  a.vscale = vscale_ptr;
-  a.qscale_stride = qscale_pad_stride;
-  a.ks_block_stride = kscale_block_stride;
-  a.ks_row_stride = kscale_row_stride;
-  a.ks_head_stride = kscale_head_stride;
-  bool sliced = false;
-  const int share_shift = decode_slices(num_seq_q, num_head_q / num_head_kv, 32, &sliced);
-  // second generation (head pairs per load, deep prefetch, in-kernel plan) when the layout allows it
-  {
-    hpc::decode2::Args b;
-    b.q = q_ptr;
-    b.kcache = kcache_ptr;
-    b.vcache = vcache_ptr;
-    b.block_ids = block_ids_ptr;
-    b.lens = num_seq_kvcache_ptr;
-    b.task_map = task_map_ptr;
-    b.y = static_cast<uint16_t*>(y_ptr);
-    b.qscale = qscale_ptr;
-    b.kscale = static_cast<const float*>(kscale_ptr);
-    b.vscale = vscale_ptr;
-    b.num_batch = num_batch;
-    b.num_seq_q = num_seq_q;
-    b.num_head_kv = num_head_kv;
-    b.g_shift = a.g_shift;
-    b.page_shift = a.page_shift;
-    b.max_blocks = num_seq_max_blocks;
-    b.ldq = ldQ;
-    b.ldy = ldY;
-    b.qscale_stride = qscale_pad_stride;
-    b.new_kv_included = new_kv_included;
-    b.bf16 = 0;
-    b.k_block_stride = kcache_block_stride;
-    b.k_token_stride = kcache_token_stride;
-    b.v_block_stride = vcache_block_stride;
-    b.v_token_stride = vcache_token_stride;
-    b.ks_block_stride = kscale_block_stride;
-    b.ks_row_stride = kscale_row_stride;
-    b.ks_head_stride = kscale_head_stride;
-    b.scale_log2 = a.scale_log2;
-    // quant_type 0 (per-token K scales, per-head V scales) runs there too since round 6 (development key kDevDecodeQt0FirstGen = 1: first generation)
-    b.ktok = quant_type == 0 ? 1 : 0;
-    if (quant_type == 1 || hpc_dev_tuning_get(kDevDecodeQt0FirstGen) != 1) {
-      const int rc = try_second_generation(b, workspace, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, block_size,
-                                           kcache_head_stride, vcache_head_stride, stream, share_shift);
-      if (rc <= 0) return rc;
-    }
-  }
-  if (sliced)
-    return quant_type == 1 ? launch_sliced<true, 1>(a, num_bins, stream) : launch_sliced<true, 0>(a, num_bins, stream);
-  if (quant_type == 1) return launch<true, 1>(a, num_bins, c.num_nb, stream);
-  return launch<true, 0>(a, num_bins, c.num_nb, stream);
+  return run({true, y_ptr, workspace, task_map_ptr, q_ptr, kcache_ptr, vcache_ptr, block_ids_ptr, num_seq_kvcache_ptr, qscale_ptr,
+              kscale_ptr, vscale_ptr, new_kv_included, quant_type, num_bins, num_batch, num_seq_q, num_head_q, num_head_kv, num_dim_qk,
+              num_dim_v, block_size, num_seq_max_blocks, qscale_pad_stride, ldY, ldQ, kcache_block_stride, kcache_token_stride,
+              kcache_head_stride, vcache_block_stride, vcache_token_stride, vcache_head_stride, kscale_block_stride, kscale_row_stride,
+              kscale_head_stride, stream});
 }

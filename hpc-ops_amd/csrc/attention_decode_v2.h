@@ -1,8 +1,11 @@
-// Interface between the decode-attention C entry (attention_decode.hip) and the second-generation
-// FP8 / NHD kernel (attention_decode_v2.hip).  Internal header.
+// Interface between the decode-attention C entries (attention_decode.hip) and the second-generation kernel
+// (attention_decode_v2.hip): fp8 with per-tensor or per-token K scales and bf16, head pairs on NHD (development: HND) pages,
+// four heads (development), or one (virtual) kv head per workgroup on any page layout.  Internal header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "attention_decode_route.h"
 
 namespace hpc {
 namespace decode2 {
@@ -51,18 +54,10 @@ struct Args {
   void* prof;  // development: per-wave timing sums [workgroups][4][12] uint64 (null = off)
 };
 
-// Arrival counters of split requests: a fixed region at the very start of a call's workspace.  It must be zero
-// the first time a workspace is used (the kernel leaves it zero); its place and size do not depend on the call.
-constexpr int64_t kCounterBytes = 64 * 1024;
 int64_t workspace_bytes(int num_wg);  // partial slots (2 per workgroup x 2 heads), after the first-generation region
-// 3: one kv head per workgroup (fp8 with either scale scheme on pages of 32 / 64 tokens, bf16 on pages of 16 / 32 / 64; 17 ... 32 q
-//    rows per (virtual) kv head, any page layout; the only mode that serves a.share_shift > 0);
-// 0: not served here; 1: served (NHD pages with adjacent heads contiguous - 128 B apart for fp8, 256 B for bf16 -, or, fp8
-// with per-tensor scales and development key kDevDecodeHndPair = 1, HND pages with a head's tokens contiguous (a.hnd is set then); an even number of kv heads,
-// <= 16 q rows per kv head, <= 1024 requests).  Any power-of-two GQA group 1 ... 16 whose rows fit (the four-head development form:
-// groups 4 and 8 only).
-int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int64_t v_head_stride);
-int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStream_t stream);
+// Launches the form that `r` (generation 2) names on r.num_wg workgroups.  `a`: filled by the entry but for the members that follow
+// from the grid (pair_xor ... dev_slice); a.arrive is the workspace's counter region, left zero also when the launch fails.
+int launch(Args a, const DecodeRoute& r, hipStream_t stream);
 #ifdef HPC_DEV
 // development build: arrivals that drew a ticket ABOVE their request's chunk count since the last reset - the signature of
 // an arrival counter that was not zero on entry (the zero-bytes contract of the workspace was broken: the last arriver is

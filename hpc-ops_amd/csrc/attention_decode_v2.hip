@@ -292,7 +292,7 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
     // in index order and every XCD has an L2 of its own, so sibling slices on neighbouring workgroup indices (virtual head index
     // minor) each fetch the rows from memory - measured at 8 kv heads: two slices cost 1.85-2.05 x one pass, four 3.3-3.8 x.  So
     // siblings sit a multiple of 8 workgroups apart - the same XCD, the same dispatch wave, the same range: 1.40-1.58 x and
-    // 2.1-2.4 x (profiles/gqa_groups_decode.txt; the product launches two slices only, attention_decode.hip::decode_slices).  kv head count a multiple of 8: kv head minor, slice major.  A divisor of 8: a row
+    // 2.1-2.4 x (profiles/gqa_groups_decode.txt; the product launches two slices only, attention_decode_route.h).  kv head count a multiple of 8: kv head minor, slice major.  A divisor of 8: a row
     // of 8 workgroups holds 8 / heads ranges x heads, the slices follow in the next rows.  Other counts: kv head minor (no guarantee).
     if (a.share_shift > 0) {
       const int ss = a.share_shift, hk = npair >> ss;
@@ -1498,77 +1498,6 @@ int64_t workspace_bytes(int num_wg) {
   return part_o + part_lse;
 }
 
-int mode_of(Args& a, int num_head_q, int block_size, int64_t k_head_stride, int64_t v_head_stride) {
-  if (a.num_head_kv <= 0 || num_head_q % a.num_head_kv) return 0;
-  const int group = num_head_q / a.num_head_kv;
-  const int head_bytes = a.bf16 ? 256 : 128;  // strides in BYTES: adjacent kv heads of a token must be contiguous (NHD pages)
-  // ... or (fp8, per-tensor scales) a head's tokens: HND pages - development key kDevDecodeHndPair = 1 only.  Measured (profiles/round6_decode_ab.txt,
-  // call 3): against the first-generation kernel the HND form wins on length mixes (C3 mix 137.3 vs 141.2 us, 32 x 128 + 32 x 4k
-  // 57.8 vs 60.6) and loses where the task map gives every workgroup one whole (request, head) and this kernel's plan cuts every
-  // request in two (uniform 8k: 181.7 us = 0.74 against 164-178 us = 0.75-0.82) - and 1 KB contiguous pieces stream no faster
-  // through this pipeline than the NHD form's 256-byte slices do (0.74 vs 0.76 on uniform 8k): the access pattern is not what
-  // bounds it.  HND pages stay on the first generation.
-  a.hnd = 0;
-  a.k_head_stride = k_head_stride;
-  a.v_head_stride = v_head_stride;
-  // One kv head per workgroup with up to 32 q rows (kSolo, mode 3): speculative steps with 17 ... 32 q rows per kv head (round 6).
-  // Any head / token strides (NHD and HND pages), any head count, pages of 32 / 64 tokens.  Measured against the first generation's
-  // two-block form (profiles/round6_decode_ab.txt, call 8; C3 lengths, us): num_seq_q 3, 8 / 64 heads NHD mix 195.6 -> 163.8,
-  // uniform 8k 220 -> 196; HND 193 -> 150 / 218 -> 180; num_seq_q 4: 4 / 32 heads 112 -> 87.5 / 112 -> 95, 1 / 8 heads 49.5 -> 41.4.
-  // Development key kDevDecodeSoloForm: 1 = never (rounds 1-5), 2 = also every other fp8 call with per-tensor scales that the pair form does not
-  // take (<= 16 q rows on HND pages or with an odd head count) - there the first generation stays ahead (one kv head, 8 q rows:
-  // 31 against 38-40 us; HND mix 138 / 139, 32 x 128 + 32 x 4k 63 against 71 us).
-  {
-    const int rows = a.num_seq_q * group, k60 = hpc_dev_tuning_get(kDevDecodeSoloForm);
-    const bool pair_case = (a.num_head_kv % 2) == 0 && rows <= 16 && k_head_stride == head_bytes && v_head_stride == head_bytes &&
-                           (!a.ktok || a.ks_head_stride == 128);
-    const bool ks_ok = !a.ktok || (a.ks_block_stride > 0 && a.ks_block_stride < (1ll << 32) && (a.ks_row_stride % 4) == 0 &&
-                                   (a.ks_head_stride % 4) == 0);
-    const bool shape_ok = ks_ok && a.lens != nullptr && rows <= 32 && (block_size == 64 || block_size == 32 || (a.bf16 && block_size == 16)) &&
-                          (a.k_token_stride % 16) == 0 && (a.v_token_stride % 16) == 0 && (k_head_stride % 16) == 0 &&
-                          (v_head_stride % 16) == 0 && (a.k_block_stride % 16) == 0 && (a.v_block_stride % 16) == 0 &&
-                          a.k_block_stride > 0 && a.v_block_stride > 0 && a.k_block_stride < (1ll << 32) &&
-                          a.v_block_stride < (1ll << 32) && a.k_token_stride * 32 < (1ll << 31) && a.v_token_stride * 32 < (1ll << 31) &&
-                          a.num_batch <= 64 * 16 && static_cast<int64_t>(a.num_batch) * a.num_head_kv * 4 <= kCounterBytes;
-    const bool wanted = k60 == 3 ? true : k60 == 2 ? !pair_case : (k60 == 0 && rows > 16);  // 3: every eligible call (A/B against the pair forms)
-    if (shape_ok && wanted) return 3;
-  }
-  if (a.share_shift > 0) return 0;  // virtual heads (slices of a group-16 kv head's q heads) exist in the one-head form only
-  const bool hnd = !a.bf16 && !a.ktok && a.k_token_stride == 128 && a.v_token_stride == 128 && k_head_stride >= 128 * block_size &&
-                   v_head_stride >= 128 * block_size && (k_head_stride % 16) == 0 && (v_head_stride % 16) == 0 &&
-                   k_head_stride < (1ll << 28) && v_head_stride < (1ll << 28) && a.num_head_kv > 1 && hpc_dev_tuning_get(kDevDecodeHndPair) == 1;
-  if (hnd) {
-    a.hnd = 1;
-    k_head_stride = v_head_stride = head_bytes;  // the checks below are the NHD form's
-  }
-  const bool ok = a.lens != nullptr && (a.num_head_kv % 2) == 0 && a.num_seq_q * group <= 16 && k_head_stride == head_bytes &&
-                  v_head_stride == head_bytes && (block_size == 64 || block_size == 32 || block_size == 16) &&
-                  (a.k_token_stride % 16) == 0 && (a.v_token_stride % 16) == 0 && (a.k_block_stride % 16) == 0 &&
-                  (a.v_block_stride % 16) == 0 && a.k_block_stride > 0 && a.v_block_stride > 0 &&
-                  a.k_block_stride < (1ll << 32) && a.v_block_stride < (1ll << 32) && a.num_batch <= 64 * 16 &&
-                  static_cast<int64_t>(a.num_batch) * (a.num_head_kv / 2) * 4 <= kCounterBytes;
-  if (!ok) {
-    a.hnd = 0;
-    return 0;
-  }
-  // per-token K scales (quant_type 0): a wave-iteration's 32 tokens x 2 heads of scales must be one contiguous 256-byte piece
-  // of a page's tail row - pages of 32 / 64 tokens, 32 floats per head and row, adjacent heads 128 bytes apart
-  if (a.ktok && (a.bf16 || block_size < 32 || a.ks_head_stride != 128 || a.ks_block_stride <= 0 || a.ks_block_stride >= (1ll << 32) ||
-                 (a.ks_row_stride % 4) != 0))
-    return 0;
-  if (a.ktok) return 1;
-  // fp8 with <= 8 q rows per kv head and a multiple of 4 kv heads can run four heads per workgroup (kQuad).  Measured
-  // 3-5 % SLOWER than head pairs on the graded shapes (uniform 8k 188.8 vs 183.0 us, C3 mix 145.4 vs 138.6 us, same box,
-  // profiles/round3_decode_fp8_forms_ab.txt): the wider rows do not pay in the kernel although they do in a pure streaming
-  // probe - the waves sit in the load issue either way (tools/prof_decode.py: 52-57 % of a wave's cycles).  So head
-  // pairs stay the default and development key kDevDecodeQuadForm = 2 selects the four-head form (kept: tested, half the softmax work).
-  // (development form: GQA groups 4 and 8 only - its column -> (head, q row) selects were written and tested for those; groups 1 and
-  // 2 stay on head pairs whatever the key says)
-  const bool quad = !a.bf16 && !a.hnd && (a.num_head_kv % 4) == 0 && (group == 4 || group == 8) && a.num_seq_q * group <= 8 &&
-                    hpc_dev_tuning_get(kDevDecodeQuadForm) == 2;
-  return quad ? 2 : 1;
-}
-
 #ifdef HPC_DEV
 int ticket_overruns(bool reset) {
   int v = 0;
@@ -1579,70 +1508,31 @@ int ticket_overruns(bool reset) {
 }
 #endif
 
-namespace {
-// After the kernel launch of launch().  The contract of the counter region is "zero on entry, zero on exit": a launch that
-// was refused leaves it as it found it, but the caller cannot tell a refused launch from one that died half way - restore
-// the invariant in stream order before reporting (best effort: the stream may be beyond repair).
-int launch_status(void* counters, hipStream_t stream) {
-  if (hipGetLastError() == hipSuccess) return HPC_OK;
-  (void)hipMemsetAsync(counters, 0, kCounterBytes, stream);
-  (void)hipGetLastError();
-  return HPC_ERR_LAUNCH;
-}
-}  // namespace
-
-int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStream_t stream) {
+// The members of the argument block that follow from the grid, and the development keys that only set a kernel parameter.
+static void set_grid_params(Args& a, const DecodeRoute& r) {
   int dev = 0;
   const int cus = hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-  char* ws = static_cast<char*>(partials);
-  a.part_o = reinterpret_cast<float*>(ws);
-  ws += static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 128 * 4;
-  a.part_lse = reinterpret_cast<float*>(ws);
-  a.arrive = static_cast<int*>(counters);
-  const bool temporal = hpc_dev_tuning_get(kDevDecodeKvTemporal) == 1;
-  if (mode == 3) {  // one kv head per workgroup
-    a.dev_slice = a.xcd_map = a.dev_sleep = 0;
-    a.pair_xor = a.mate_from = 0;
-    a.pair_wgs[0] = a.pair_wgs[1] = a.pair_wgs[2] = a.pair_wgs[3] = 0;
-    a.big_pct = 100;
-    {  // the pair form's CU-mate rule (a CU's two workgroups on slices across an address bit) makes no difference here - masks 1, 2,
-       // 4, 6 on 8 heads: C3 mix 160.6-164.3 us with and without, call 8 - so it is off; development key kDevDecodePairSwizzle = mask + 1 switches it on
-      const int k36 = hpc_dev_tuning_get(kDevDecodePairSwizzle);
-      const int mask = k36 > 0 ? k36 - 1 : 0;
-      const int np = a.num_head_kv;
-      if (cus > 0 && num_wg > cus && (np & (np - 1)) == 0 && mask > 0 && mask < np && cus % np == 0) {
-        a.pair_xor = mask;
-        a.mate_from = cus;
-      }
-    }
-    if (a.bf16)
-      decode2_kernel<2, true, false, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else if (a.ktok)
-      decode2_kernel<2, false, false, false, true, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else if (kHpcDevBuild && a.prof)
-      decode2_kernel<2, false, true, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else
-      decode2_kernel<2, false, false, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    return launch_status(counters, stream);
-  }
-  a.dev_slice = hpc_dev_tuning_get(kDevDecodeOneSlice);
-  a.xcd_map = hpc_dev_tuning_get(kDevDecodeXcdMap);
-  a.dev_sleep = hpc_dev_tuning_get(kDevDecodeSleep);
-  a.dev_merge_dup = hpc_dev_tuning_get(kDevDecodeMergeDup) == 1;
-  a.dev_nosnap = hpc_dev_tuning_get(kDevDecodeNoSnap) == 1;
+  const int num_wg = r.num_wg;
+  const bool pairs = r.mode != 3;  // head pairs or quads; else one kv head per workgroup: none of the timing keys, shares or longer ranges
+  const int units = pairs ? a.num_head_kv / (r.mode == 2 ? 4 : 2) : a.num_head_kv;
+  a.dev_slice = pairs ? hpc_dev_tuning_get(kDevDecodeOneSlice) : 0;
+  a.xcd_map = pairs ? hpc_dev_tuning_get(kDevDecodeXcdMap) : 0;
+  a.dev_sleep = pairs ? hpc_dev_tuning_get(kDevDecodeSleep) : 0;
+  a.dev_merge_dup = pairs && hpc_dev_tuning_get(kDevDecodeMergeDup) == 1;
+  a.dev_nosnap = pairs && hpc_dev_tuning_get(kDevDecodeNoSnap) == 1;
   // the second workgroup of every CU on the slice across address bit 9 (see the kernel): slices of 256 B (fp8 pairs) -> pair
   // index bit 1, of 512 B (bf16 pairs, fp8 quads) -> bit 0.  Measured per shape (profiles/round5_decode_pair_map_ab.txt):
   // fp8 8 / 64 heads +4-6 %, 16 / 128 heads +4 % (bit 8: +2 %, bit 10: 0), bf16 8 / 64 +1-2.5 % (bit 10: 0); with two pairs
   // (4 kv heads, fp8) only bit 8 exists: +2 % on the length mix, +-1 % on uniform lengths - taken.  Needs a power-of-two pair
   // count that holds the bit, more than one workgroup per CU, whole rows of pairs in front of the second workgroups, equal
   // shares.  Development key kDevDecodePairSwizzle = mask + 1 overrides the mask (1 = off: both workgroups of a CU on the same slice).
+  // One kv head per workgroup: the rule makes no difference - masks 1, 2, 4, 6 on 8 heads: C3 mix 160.6-164.3 us with and without
+  // (profiles/round6_decode_ab.txt, call 8) - so it is off but for the key.
   {
-    const int npair = a.num_head_kv / (mode == 2 ? 4 : 2);
     const int k36 = hpc_dev_tuning_get(kDevDecodePairSwizzle);
-    int mask = (a.bf16 || mode == 2 || npair == 2) ? 1 : 2;
-    if (k36 > 0) mask = k36 - 1;
+    const int mask = k36 > 0 ? k36 - 1 : !pairs ? 0 : (a.bf16 || r.mode == 2 || units == 2) ? 1 : 2;
     // (HND pages: a workgroup walks whole 1 KB pieces of a head - no slice fixes address bits 8-9, the rule has nothing to separate)
-    const bool ok = cus > 0 && num_wg > cus && (npair & (npair - 1)) == 0 && mask > 0 && mask < npair && cus % npair == 0 &&
+    const bool ok = cus > 0 && num_wg > cus && (units & (units - 1)) == 0 && mask > 0 && mask < units && cus % units == 0 &&
                     (!a.hnd || k36 > 0);
     a.pair_xor = ok ? mask : 0;
     a.mate_from = ok ? cus : 0;
@@ -1652,7 +1542,7 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
   // at d1 = 12 of 128 and nothing on uniform 8k (where the even split puts exactly one request half on every
   // workgroup); development keys kDevDecodeExtraWg256 / kDevDecodeExtraWg768 set the deltas (value - 100, per 128 workgroups of a slice).
   a.pair_wgs[0] = a.pair_wgs[1] = a.pair_wgs[2] = a.pair_wgs[3] = 0;
-  if (!a.bf16 && mode == 1 && a.num_head_kv == 8 && num_wg >= 256 && num_wg % 4 == 0) {
+  if (!a.bf16 && r.mode == 1 && a.num_head_kv == 8 && num_wg >= 256 && num_wg % 4 == 0) {
     const int k30 = hpc_dev_tuning_get(kDevDecodeExtraWg256), k31 = hpc_dev_tuning_get(kDevDecodeExtraWg768);
     const int even = num_wg / 4;
     int d1 = (k30 != 0 ? k30 - 100 : 0) * even / 128, d3 = (k31 != 0 ? k31 - 100 : 0) * even / 128;
@@ -1667,40 +1557,41 @@ int launch(Args a, void* counters, void* partials, int num_wg, int mode, hipStre
   // Measured: no gain at 108 / 115 / 122 % (C3 mix 139.7 / 139.0 / 138.4 us vs 139.3 us) - when a CU's first workgroup
   // ends early its second one speeds up, and the chip's aggregate rate does not change: the spread of finish times
   // (first halves 119-143 us, second halves 142-169 us on uniform 8k) is not where the time goes.  Off.
-  {
-    const int k32 = hpc_dev_tuning_get(kDevDecodeFirstHalfPct);
-    a.big_pct = 100;
-    if (k32 > 100 && k32 <= 200 && cus > 0 && num_wg == 2 * cus &&
-        (num_wg / 2) % (a.num_head_kv / (mode == 2 ? 4 : 2)) == 0)
-      a.big_pct = k32;
-  }
-  if (a.ktok) {
-    decode2_kernel<2, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-  } else if (a.hnd) {
-    if (kHpcDevBuild && a.prof)
-      decode2_kernel<2, false, true, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else
-      decode2_kernel<2, false, false, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-  } else if (a.bf16) {
-    if (temporal)
-      decode2_kernel<0, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else
-      decode2_kernel<2, true><<<num_wg, kThreads, 0, stream>>>(a);
-  } else if (kHpcDevBuild && mode == 2) {
-    if (a.prof)  // development: per-wave s_memtime sums (hpc_dev_decode_prof_buffer)
-      decode2_kernel<2, false, true, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else if (temporal)
-      decode2_kernel<0, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-    else
-      decode2_kernel<2, false, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-  } else if (kHpcDevBuild && a.prof) {  // development: per-wave s_memtime sums (hpc_dev_decode_prof_buffer)
-    decode2_kernel<2, false, true><<<num_wg, kThreads, 0, stream>>>(a);
-  } else if (temporal) {
-    decode2_kernel<0><<<num_wg, kThreads, 0, stream>>>(a);
-  } else {
-    decode2_kernel<2><<<num_wg, kThreads, 0, stream>>>(a);
-  }
-  return launch_status(counters, stream);
+  const int k32 = hpc_dev_tuning_get(kDevDecodeFirstHalfPct);
+  a.big_pct = pairs && k32 > 100 && k32 <= 200 && cus > 0 && num_wg == 2 * cus && (num_wg / 2) % units == 0 ? k32 : 100;
+}
+
+int launch(Args a, const DecodeRoute& r, hipStream_t stream) {
+  set_grid_params(a, r);
+  // One instantiation per form.  The tests that are constant in the product come first in a condition: the development-only
+  // instantiations (profiling: per-wave s_memtime sums, hpc_dev_decode_prof_buffer; four heads; temporal KV loads) are not emitted there.
+  const bool temporal = hpc_dev_tuning_get(kDevDecodeKvTemporal) == 1, solo = r.mode == 3, quad = r.mode == 2;
+#define HPC_DECODE2(...) decode2_kernel<__VA_ARGS__><<<r.num_wg, kThreads, 0, stream>>>(a)
+  // clang-format off                                    kAux bf16   prof   quad   ktok   hnd    solo
+  if (solo && a.bf16)                           HPC_DECODE2(2, true,  false, false, false, false, true);
+  else if (solo && a.ktok)                      HPC_DECODE2(2, false, false, false, true,  false, true);
+  else if (kHpcDevBuild && solo && a.prof)      HPC_DECODE2(2, false, true,  false, false, false, true);
+  else if (solo)                                HPC_DECODE2(2, false, false, false, false, false, true);
+  else if (a.ktok)                              HPC_DECODE2(2, false, false, false, true);
+  else if (kHpcDevBuild && a.hnd && a.prof)     HPC_DECODE2(2, false, true,  false, false, true);
+  else if (a.hnd)                               HPC_DECODE2(2, false, false, false, false, true);
+  else if (temporal && a.bf16)                  HPC_DECODE2(0, true);
+  else if (a.bf16)                              HPC_DECODE2(2, true);
+  else if (kHpcDevBuild && quad && a.prof)      HPC_DECODE2(2, false, true,  true);
+  else if (kHpcDevBuild && temporal && quad)    HPC_DECODE2(0, false, false, true);
+  else if (kHpcDevBuild && quad)                HPC_DECODE2(2, false, false, true);
+  else if (kHpcDevBuild && a.prof)              HPC_DECODE2(2, false, true);
+  else if (temporal)                            HPC_DECODE2(0);
+  else                                          HPC_DECODE2(2);
+  // clang-format on
+#undef HPC_DECODE2
+  // The contract of the counter region is "zero on entry, zero on exit": a launch that was refused leaves it as it found it, but the
+  // caller cannot tell a refused launch from one that died half way - restore the invariant in stream order before reporting (best
+  // effort: the stream may be beyond repair).
+  if (hipGetLastError() == hipSuccess) return HPC_OK;
+  (void)hipMemsetAsync(a.arrive, 0, kCounterBytes, stream);
+  (void)hipGetLastError();
+  return HPC_ERR_LAUNCH;
 }
 
 }  // namespace decode2

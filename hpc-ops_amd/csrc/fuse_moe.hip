@@ -16,32 +16,7 @@
 //  * Everything is launched back to back on one stream (hipGraph-capturable, no host sync).
 #include "hpc_common.h"
 #include "group_gemm.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
-
-extern "C" int hpc_group_gemm_blockwise_fp8_async(
-    void* y_ptr, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
-    const void* cu_seqlens_ptr, const void* xscale_ptr, const void* wscale_ptr,
-    const void* row_index_ptr, const void* col_base_ptr, int num_group, int m, int n, int k,
-    int num_block_k_pad4, int tile_m, int64_t xscale_row_stride, int64_t xscale_kb_stride,
-    const void* cu_tiles128_ptr, hipStream_t stream);
-int hpc_group_gemm_blockwise_fp8_act(void* act_out, void* act_scale, const void* x_ptr, const void* w_ptr,
-                                     const void* seqlens_ptr, const void* cu_seqlens_ptr, const void* xscale_ptr,
-                                     const void* wscale_ptr, const void* row_index_ptr, int num_group, int m, int n,
-                                     int k, int num_block_k_pad4, int64_t xscale_row_stride, int64_t xscale_kb_stride,
-                                     const void* cu_tiles128_ptr, hipStream_t stream);
-
-int hpc_group_gemm_pertensor_fp8_act(void* act_out, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
-                                     const void* cu_seqlens_ptr, const void* yscale_ptr, const void* row_index_ptr,
-                                     const void* act_mul_scale_ptr, int use_bf16_mul, int num_group, int m, int x_rows,
-                                     int n, int k, const void* cu_tiles128_ptr, hipStream_t stream);
-bool hpc_ggemm_p8_selected(int num_group, int m, int n, int k, const void* cu_tiles128);
-
-extern "C" int hpc_group_gemm_pertensor_fp8_async(void* y_ptr, const void* x_ptr, const void* w_ptr,
-                                                  const void* seqlens_ptr, const void* cu_seqlens_ptr,
-                                                  const void* yscale_ptr, const void* row_index_ptr,
-                                                  int num_group, int m, int x_rows, int n, int k,
-                                                  const void* cu_tiles128_ptr, hipStream_t stream);
 
 namespace hpc {
 namespace moe {
@@ -712,6 +687,60 @@ extern "C" int64_t hpc_fuse_moe_blockwise_workspace_bytes(int num_tokens, int nu
   return moe_ws_layout(num_tokens, num_topk, hidden_size, intermediate_size2, num_expert).total;
 }
 
+namespace {
+// What the two pipelines differ in: the scales of the two GEMMs and of the activation between them.
+struct MoeScales {
+  bool blockwise;  // x_scale [token][hidden / 128] and 128 x 128 weight scale blocks (rows padded to *_pad4 floats), activation
+                   // quantised per 128 columns; else one scale per expert on each GEMM and act_mul_scale[0] on the activation
+  const void *x_scale, *gate_up, *down, *act_mul;
+  int gate_up_pad4, down_pad4, use_bf16_mul;
+};
+
+// count + slot -> gate-up GEMM (+ activation) -> down GEMM -> top-k reduce; ws_inter2: the intermediate_size2 of the workspace layout
+int fuse_moe(void* y_ptr, void* workspace, const void* x_ptr, const void* gate_up_weight_ptr, const void* down_weight_ptr,
+             const MoeScales& s, const void* topk_ids_ptr, const void* topk_scale_ptr, const void* shared_output_ptr,
+             int num_tokens, int hidden_size, int intermediate_size2, int ws_inter2, int num_topk, int num_expert, int rank_ep,
+             hipStream_t stream) {
+  const int inter = intermediate_size2 / 2;
+  const int m = num_tokens * num_topk;
+  const MoeWs w = moe_ws_layout(num_tokens, num_topk, hidden_size, ws_inter2, num_expert);
+  char* ws = static_cast<char*>(workspace);
+  int rc = hpc_moe_count_and_slot_async(topk_ids_ptr, num_tokens, num_topk, num_expert, rank_ep, 128,
+                                        ws + w.seqlens, ws + w.cu_seqlens, ws + w.tiles,
+                                        ws + w.cu_tiles, ws + w.topk_pos, ws + w.row_index, stream);
+  if (rc) return rc;
+  // gate_up: rows come straight from x through row_index, blockwise scales from x_scale[token][kb].  Where ggemm_route() puts
+  // the activation (+ quantisation) into the GEMM's epilogue the bf16 gate-up matrix is never written; else it runs here.
+  int fused = 0;
+  rc = s.blockwise
+           ? hpc_group_gemm_blockwise_fp8_act(ws + w.gate_up_out, ws + w.down_in, ws + w.down_in_scale, x_ptr, gate_up_weight_ptr,
+                                              ws + w.seqlens, ws + w.cu_seqlens, s.x_scale, s.gate_up, ws + w.row_index, nullptr,
+                                              num_expert, m, intermediate_size2, hidden_size, s.gate_up_pad4, 16,
+                                              hidden_size / 128, 1, ws + w.cu_tiles, stream, &fused)
+           : hpc_group_gemm_pertensor_fp8_act(ws + w.gate_up_out, ws + w.down_in, s.act_mul, s.use_bf16_mul, x_ptr,
+                                              gate_up_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens, s.gate_up, ws + w.row_index,
+                                              num_expert, m, num_tokens, intermediate_size2, hidden_size, ws + w.cu_tiles, stream,
+                                              &fused);
+  if (rc) return rc;
+  const int* num_rows = reinterpret_cast<const int*>(ws + w.cu_seqlens) + num_expert;
+  if (!fused)
+    rc = s.blockwise ? hpc_act_mul_and_blockwise_quant_async(ws + w.down_in, ws + w.down_in_scale, ws + w.gate_up_out, num_rows, m,
+                                                             inter, inter / 128, 1, nullptr, stream)
+                     : hpc_act_mul_and_quant_async(ws + w.down_in, ws + w.gate_up_out, s.act_mul, num_rows, m, inter,
+                                                   s.use_bf16_mul, stream);
+  if (rc) return rc;
+  rc = s.blockwise
+           ? hpc_group_gemm_blockwise_fp8_async(ws + w.down_out, ws + w.down_in, down_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens,
+                                                ws + w.down_in_scale, s.down, nullptr, nullptr, num_expert, m, hidden_size, inter,
+                                                s.down_pad4, 16, inter / 128, 1, ws + w.cu_tiles, stream)
+           : hpc_group_gemm_pertensor_fp8_async(ws + w.down_out, ws + w.down_in, down_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens,
+                                                s.down, nullptr, num_expert, m, m, hidden_size, inter, ws + w.cu_tiles, stream);
+  if (rc) return rc;
+  return hpc_moe_reduce_async(y_ptr, ws + w.down_out, ws + w.topk_pos, topk_scale_ptr,
+                              shared_output_ptr, num_tokens, num_topk, hidden_size, stream);
+}
+}  // namespace
+
 extern "C" int hpc_fuse_moe_blockwise_async(
     void* y_ptr, void* workspace, const void* x_ptr, const void* x_scale_ptr,
     const void* gate_up_weight_ptr, const void* gate_up_weight_scale_ptr,
@@ -726,45 +755,9 @@ extern "C" int hpc_fuse_moe_blockwise_async(
   if ((hidden_size & 127) || (intermediate_size2 & 255) || num_topk > 128) return HPC_ERR_UNSUPPORTED;
   if (num_tokens <= 0) return HPC_OK;
   (void)num_expert_total;
-  const int inter = intermediate_size2 / 2;
-  const int m = num_tokens * num_topk;
-  const MoeWs w = moe_ws_layout(num_tokens, num_topk, hidden_size, intermediate_size2, num_expert);
-  char* ws = static_cast<char*>(workspace);
-  int rc = hpc_moe_count_and_slot_async(topk_ids_ptr, num_tokens, num_topk, num_expert, rank_ep, 128,
-                                        ws + w.seqlens, ws + w.cu_seqlens, ws + w.tiles,
-                                        ws + w.cu_tiles, ws + w.topk_pos, ws + w.row_index, stream);
-  if (rc) return rc;
-  // gate_up: rows come straight from x through row_index, scales from x_scale[token][kb].  With the 256 x 256 tile
-  // kernel the activation + quantisation runs in the GEMM's epilogue (a tile = 128 gate rows + the 128 up rows of
-  // the same columns) and the bf16 gate-up matrix is never written (development key kDevMoeSplitAct = 1: keep them apart)
-  if ((inter & 127) == 0 && hpc_dev_tuning_get(kDevMoeSplitAct) != 1 &&
-      hpc_ggemm_p8_selected(num_expert, m, intermediate_size2, hidden_size, ws + w.cu_tiles)) {
-    rc = hpc_group_gemm_blockwise_fp8_act(ws + w.down_in, ws + w.down_in_scale, x_ptr, gate_up_weight_ptr,
-                                          ws + w.seqlens, ws + w.cu_seqlens, x_scale_ptr, gate_up_weight_scale_ptr,
-                                          ws + w.row_index, num_expert, m, intermediate_size2, hidden_size,
-                                          gate_up_ws_pad4, hidden_size / 128, 1, ws + w.cu_tiles, stream);
-    if (rc) return rc;
-  } else {
-    rc = hpc_group_gemm_blockwise_fp8_async(ws + w.gate_up_out, x_ptr, gate_up_weight_ptr,
-                                            ws + w.seqlens, ws + w.cu_seqlens, x_scale_ptr,
-                                            gate_up_weight_scale_ptr, ws + w.row_index, nullptr,
-                                            num_expert, m, intermediate_size2, hidden_size,
-                                            gate_up_ws_pad4, 16, hidden_size / 128, 1, ws + w.cu_tiles, stream);
-    if (rc) return rc;
-    rc = hpc_act_mul_and_blockwise_quant_async(
-        ws + w.down_in, ws + w.down_in_scale, ws + w.gate_up_out,
-        reinterpret_cast<const int*>(ws + w.cu_seqlens) + num_expert, m, inter, inter / 128, 1, nullptr,
-        stream);
-    if (rc) return rc;
-  }
-  rc = hpc_group_gemm_blockwise_fp8_async(ws + w.down_out, ws + w.down_in, down_weight_ptr,
-                                          ws + w.seqlens, ws + w.cu_seqlens, ws + w.down_in_scale,
-                                          down_weight_scale_ptr, nullptr, nullptr, num_expert, m,
-                                          hidden_size, inter, down_ws_pad4, 16, inter / 128, 1,
-                                          ws + w.cu_tiles, stream);
-  if (rc) return rc;
-  return hpc_moe_reduce_async(y_ptr, ws + w.down_out, ws + w.topk_pos, topk_scale_ptr,
-                              shared_output_ptr, num_tokens, num_topk, hidden_size, stream);
+  const MoeScales s{true, x_scale_ptr, gate_up_weight_scale_ptr, down_weight_scale_ptr, nullptr, gate_up_ws_pad4, down_ws_pad4, 0};
+  return fuse_moe(y_ptr, workspace, x_ptr, gate_up_weight_ptr, down_weight_ptr, s, topk_ids_ptr, topk_scale_ptr, shared_output_ptr,
+                  num_tokens, hidden_size, intermediate_size2, intermediate_size2, num_topk, num_expert, rank_ep, stream);
 }
 
 // Per-tensor pipeline (reference fuse_moe_async, src/fuse_moe/fuse_moe.cu:14-60, and the gather-free
@@ -781,40 +774,8 @@ extern "C" int hpc_fuse_moe_pertensor_async(
     return HPC_ERR_INVALID;
   if ((hidden_size & 63) || (intermediate_size2 & 127) || num_topk > 128) return HPC_ERR_UNSUPPORTED;
   if (num_tokens <= 0) return HPC_OK;
-  const int inter = intermediate_size2 / 2;
-  const int m = num_tokens * num_topk;
-  const MoeWs w = moe_ws_layout(num_tokens, num_topk, hidden_size, (intermediate_size2 + 255) / 256 * 256,
-                                num_expert);
-  char* ws = static_cast<char*>(workspace);
-  int rc = hpc_moe_count_and_slot_async(topk_ids_ptr, num_tokens, num_topk, num_expert, rank_ep, 128,
-                                        ws + w.seqlens, ws + w.cu_seqlens, ws + w.tiles,
-                                        ws + w.cu_tiles, ws + w.topk_pos, ws + w.row_index, stream);
-  if (rc) return rc;
-  // With the 256 x 256 tile kernel the activation + quantisation runs in the gate-up GEMM's epilogue (a tile = 128
-  // gate rows + the 128 up rows of the same columns): the bf16 gate-up matrix is never written (development key
-  // 19 = 1 keeps the two kernels apart)
-  if ((inter & 127) == 0 && (hidden_size & 127) == 0 && hpc_dev_tuning_get(kDevMoeSplitAct) != 1 &&
-      hpc_ggemm_p8_selected(num_expert, m, intermediate_size2, hidden_size, ws + w.cu_tiles)) {
-    rc = hpc_group_gemm_pertensor_fp8_act(ws + w.down_in, x_ptr, gate_up_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens,
-                                          gate_up_scale_ptr, ws + w.row_index, act_and_mul_scale_ptr, use_bf16_mul,
-                                          num_expert, m, num_tokens, intermediate_size2, hidden_size, ws + w.cu_tiles,
-                                          stream);
-    if (rc) return rc;
-  } else {
-    rc = hpc_group_gemm_pertensor_fp8_async(ws + w.gate_up_out, x_ptr, gate_up_weight_ptr, ws + w.seqlens,
-                                            ws + w.cu_seqlens, gate_up_scale_ptr, ws + w.row_index,
-                                            num_expert, m, num_tokens, intermediate_size2, hidden_size,
-                                            ws + w.cu_tiles, stream);
-    if (rc) return rc;
-    rc = hpc_act_mul_and_quant_async(ws + w.down_in, ws + w.gate_up_out, act_and_mul_scale_ptr,
-                                     reinterpret_cast<const int*>(ws + w.cu_seqlens) + num_expert, m, inter,
-                                     use_bf16_mul, stream);
-    if (rc) return rc;
-  }
-  rc = hpc_group_gemm_pertensor_fp8_async(ws + w.down_out, ws + w.down_in, down_weight_ptr, ws + w.seqlens,
-                                          ws + w.cu_seqlens, down_scale_ptr, nullptr, num_expert, m, m,
-                                          hidden_size, inter, ws + w.cu_tiles, stream);
-  if (rc) return rc;
-  return hpc_moe_reduce_async(y_ptr, ws + w.down_out, ws + w.topk_pos, topk_scale_ptr,
-                              shared_output_ptr, num_tokens, num_topk, hidden_size, stream);
+  const MoeScales s{false, nullptr, gate_up_scale_ptr, down_scale_ptr, act_and_mul_scale_ptr, 0, 0, use_bf16_mul};
+  return fuse_moe(y_ptr, workspace, x_ptr, gate_up_weight_ptr, down_weight_ptr, s, topk_ids_ptr, topk_scale_ptr, shared_output_ptr,
+                  num_tokens, hidden_size, intermediate_size2, (intermediate_size2 + 255) / 256 * 256, num_topk, num_expert, rank_ep,
+                  stream);
 }

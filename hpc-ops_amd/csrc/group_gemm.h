@@ -1,6 +1,6 @@
 // Shared argument block of the grouped FP8 GEMM kernels: the streaming form and the entry points that fill the block
 // (group_gemm_blockwise.hip), the 128 x 128 and 256 x 128 tiled forms (group_gemm_tiled.hip, group_gemm_tiled256.hip) and
-// the 256 x 256 tile kernel (group_gemm_p8.hip).
+// the 256 x 256 tile kernel (group_gemm_p8.hip); and what these files call of one another.
 #pragma once
 #include <stdint.h>
 
@@ -43,13 +43,23 @@ struct Args {
 }  // namespace ggemm
 }  // namespace hpc
 
-// tiled (MFMA-bound) form for large groups; `cu_tiles` = exclusive scan of ceil(seqlens / 128).
-int hpc_ggemm_launch_tiled(const hpc::ggemm::Args& a, const int* cu_tiles, int num_group, int m, int n,
+namespace hpc { struct GgemmRoute; }  // group_gemm_route.h
+// The launchers of the three tile kernels: each launches what `r` names.  `cu_tiles` = exclusive scan of ceil(seqlens / 128).
+int hpc_ggemm_launch_tiled(const hpc::ggemm::Args& a, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                            hipStream_t stream);
-int hpc_ggemm_launch_tiled256(const hpc::ggemm::Args& a, const int* cu_tiles, int num_group, int m, int n,
+int hpc_ggemm_launch_tiled256(const hpc::ggemm::Args& a, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                               hipStream_t stream);
-// 256 x 256 tile, staggered wave groups (group_gemm_p8.hip); derives its 256-token tiles from the same scan
-int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a, const int* cu_tiles, int num_group, int m, int n,
+int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                         hipStream_t stream);
-// would launch_stream_gemm pick the 256 x 256 kernel for this problem? (the fused MoE asks before it fuses)
-bool hpc_ggemm_p8_selected(int num_group, int m, int n, int k, const void* cu_tiles128);
+
+// Gate-up GEMM of a fused MoE (group_gemm_blockwise.hip): the arguments of hpc_group_gemm_{blockwise,pertensor}_fp8_async with
+// n = 2 * inter, plus the epilogue's outputs (Args::act_out ...).  *fused = GgemmRoute::act: 1 they are written, 0 y is, as by the plain entry.
+int hpc_group_gemm_blockwise_fp8_act(void* y_ptr, void* act_out, void* act_scale, const void* x_ptr, const void* w_ptr,
+                                     const void* seqlens_ptr, const void* cu_seqlens_ptr, const void* xscale_ptr,
+                                     const void* wscale_ptr, const void* row_index_ptr, const void* col_base_ptr, int num_group,
+                                     int m, int n, int k, int num_block_k_pad4, int tile_m, int64_t xscale_row_stride,
+                                     int64_t xscale_kb_stride, const void* cu_tiles128_ptr, hipStream_t stream, int* fused);
+int hpc_group_gemm_pertensor_fp8_act(void* y_ptr, void* act_out, const void* act_mul_scale_ptr, int use_bf16_mul,
+                                     const void* x_ptr, const void* w_ptr, const void* seqlens_ptr, const void* cu_seqlens_ptr,
+                                     const void* yscale_ptr, const void* row_index_ptr, int num_group, int m, int x_rows, int n,
+                                     int k, const void* cu_tiles128_ptr, hipStream_t stream, int* fused);

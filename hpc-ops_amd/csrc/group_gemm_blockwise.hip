@@ -14,19 +14,16 @@
 // workgroup through a small double-buffered LDS tile, fetched at the same prefetch depth as the
 // weights (vmcnt retires in order, so a shallower activation pipeline would drain the weight
 // stream).  Per 128-wide k block the fp32 partial is rescaled by xs*ws and accumulated (reference
-// kernels.cuh:806-836).  Groups above ~40 rows go to the tiled kernels (group_gemm_tiled256.hip,
-// group_gemm_tiled.hip) - see launch_stream_gemm at the end of this file.
+// kernels.cuh:806-836).  Groups from 16 rows on go to the tile kernels (group_gemm_p8.hip,
+// group_gemm_tiled256.hip, group_gemm_tiled.hip) - see ggemm_route() in group_gemm_route.h.
 #include "hpc_common.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
 #include "group_gemm.h"
+#include "group_gemm_route.h"
 
 namespace hpc {
 namespace ggemm {
 
-
-
-constexpr int kThreads = 256;
 // stages in flight per wave (template kDepth, default 4); one stage = 2 k-blocks = 256 B per weight row
 constexpr int kXRow = 272;    // LDS bytes per staged activation row (256 + 16: conflict-free b128 reads)
 
@@ -472,141 +469,82 @@ __global__ __launch_bounds__(256, 2) void gemm_blockwise_stream2_kernel(const Ar
 }  // namespace ggemm
 }  // namespace hpc
 
-bool hpc_ggemm_p8_selected(int num_group, int m, int n, int k, const void* cu_tiles128) {
-  const int tiled_mode = hpc_dev_tuning_get(kDevGgemmTiledMode);
-  // (up to 64 groups the kernel finds its work item from one round of lane-parallel loads, above that from one round
-  // per 64 groups: tests/test_fuse_moe_blockwise.py::test_group_gemm_blockwise_many_groups, 65 ... 256 groups)
-  // From 16 rows per group on (round 5; rounds 2-4: from 192): with the carried tails, the tail body for <= 64 rows and the
-  // half-tile body the 256 x 256 kernel overtakes the 256 x 128 ring kernel everywhere and the streaming kernel from
-  // ~16 rows per group (fused MoE, E64 / top-8 / H4096 / I11008, us: T = 128 1554-1561 against 1564-1676, T = 256
-  // 1590-1596 against 1711-1836, T = 512 1753-1755 against 1876-1978, T = 1024 2069-2102 against 2432-2607; below
-  // it loses: T = 64 1552-1563 against 1396-1461 - profiles/round5_moe_kernel_choice.txt).  Development key kDevGgemmP8From192 restores
-  // the old threshold.
-  const int p8_from = hpc_dev_tuning_get(kDevGgemmP8From192) == 1 ? 192 : 16;
-  return cu_tiles128 && n % 256 == 0 && k >= 128 &&
-         (tiled_mode == 4 || (tiled_mode == 0 && m / num_group >= p8_from));
-}
-
 namespace {
-int launch_stream_gemm(hpc::ggemm::Args& a, int num_group, int m, int n, const void* cu_tiles128,
-                       hipStream_t stream) {
+using hpc::GgemmRoute, hpc::ggemm::Args;
+
+int launch_stream(const Args& a, const GgemmRoute& r, hipStream_t stream) {
   using namespace hpc::ggemm;
-  // groups above ~20 tokens: tiled kernels (need the scan of ceil(seqlens/128)): the 256 x 128 LDS-DMA ring
-  // kernel when n allows (one pass over the weights for up to 128 tokens, 100 KB in flight per CU without
-  // staging registers; measured on E64 / top-8: T = 128 (16 per group) 1.61 vs 1.50 ms for the streaming form,
-  // T = 192 1.63 vs 1.79, T = 256 1.73 vs 1.85, T = 384 1.75 ms), else the 128 x 128 register-staged one
-  // development key kDevGgemmTiledMode: 0 auto, 1 never tiled, 2 always 256 x 128 (when possible), 3 always 128 x 128,
-  // 4 always 256 x 256 (when possible)
-  const int tiled_mode = hpc_dev_tuning_get(kDevGgemmTiledMode);
-  // the 256 x 256 kernel from 16 rows per group on (hpc_ggemm_p8_selected: tail body for <= 64 rows, half-tile body for <= 128)
-  if (tiled_mode != 1 && hpc_ggemm_p8_selected(num_group, m, n, a.K, cu_tiles128))
-    return hpc_ggemm_launch_p8(a, static_cast<const int*>(cu_tiles128), num_group, m, n, stream);
-  if (cu_tiles128 && n % 128 == 0 && tiled_mode != 1 && (tiled_mode >= 2 || m / num_group > 20)) {
-    if (n % 256 == 0 && a.K >= 128 && tiled_mode != 3)
-      return hpc_ggemm_launch_tiled256(a, static_cast<const int*>(cu_tiles128), num_group, m, n, stream);
-    return hpc_ggemm_launch_tiled(a, static_cast<const int*>(cu_tiles128), num_group, m, n, stream);
-  }
-  // tokens served per pass over the weights, from the average group size (the reference picks its
-  // tileM the same way, fuse_moe/entry.cc:525-543); larger groups take several passes
-  const int avg = m / num_group;
-  const int forced = hpc_dev_tuning_get(kDevStreamGemmForm);
-  // forced: 1 / 2 / 3 / 4 = tokens-per-pass 16 / 32 / 48 / 64 with 16 rows per wave; 8 = 64 tokens, 32 rows per
-  // wave; 16 / 32 = 64 / 32 tokens with 8 waves per workgroup
-  // measured on E64 / top-8: 16 tokens per pass up to ~10 per group, 32 up to ~22, then 48 (one pass still
-  // covers nearly every group of a 32-average batch; 64 per pass is register-bound and slower)
-  const int mt = forced ? forced : (avg <= 10 ? 1 : (avg <= 22 ? 2 : 3));
-  if (mt == 8 && n % 128 == 0) {
-    dim3 grid(n / 128, num_group);
-    gemm_blockwise_stream_kernel<4, 2><<<grid, kThreads, 0, stream>>>(a);
-  } else if (mt == 16 && n % 128 == 0) {  // 64 tokens per pass, 8 waves x 16 rows
-    dim3 grid(n / 128, num_group);
-    gemm_blockwise_stream_kernel<4, 1, 8, 3><<<grid, 512, 0, stream>>>(a);
-  } else if (mt == 32 && n % 128 == 0) {  // 32 tokens per pass, 8 waves x 16 rows
-    dim3 grid(n / 128, num_group);
-    gemm_blockwise_stream_kernel<2, 1, 8><<<grid, 512, 0, stream>>>(a);
-  } else {
-    dim3 grid(n / 64, num_group);
-    const int k56 = hpc_dev_tuning_get(kDevStreamGemmLoop);  // development key kDevStreamGemmLoop: 1 = the stage loop of rounds 1-5, 2 = the new loop on K = 32 MFMAs
-    if (mt == 1 && k56 == 0)
-      gemm_blockwise_stream2_kernel<1, 4><<<grid, kThreads, 0, stream>>>(a);
-    else if (mt == 2 && k56 == 0)
-      gemm_blockwise_stream2_kernel<2, 4><<<grid, kThreads, 0, stream>>>(a);
-    else if (kHpcDevBuild && mt == 1 && k56 == 2)
-      gemm_blockwise_stream2_kernel<1, 4, false><<<grid, kThreads, 0, stream>>>(a);
-    else if (kHpcDevBuild && mt == 2 && k56 == 2)
-      gemm_blockwise_stream2_kernel<2, 4, false><<<grid, kThreads, 0, stream>>>(a);
-    else if (mt == 1)
-      gemm_blockwise_stream_kernel<1, 1><<<grid, kThreads, 0, stream>>>(a);
-    else if (mt == 3)
-      gemm_blockwise_stream_kernel<3, 1, 4, 3><<<grid, kThreads, 0, stream>>>(a);
-    else if (mt == 4)
-      gemm_blockwise_stream_kernel<4, 1, 4, 3><<<grid, kThreads, 0, stream>>>(a);
-    else
-      gemm_blockwise_stream_kernel<2, 1><<<grid, kThreads, 0, stream>>>(a);
-  }
+  const dim3 grid(r.grid_x, r.grid_y);
+  const int t = r.threads;
+  if (r.mt == 8)  // 64 tokens per pass, 4 waves x 32 rows
+    gemm_blockwise_stream_kernel<4, 2><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 16)  // 64 tokens per pass, 8 waves x 16 rows
+    gemm_blockwise_stream_kernel<4, 1, 8, 3><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 32)  // 32 tokens per pass, 8 waves x 16 rows
+    gemm_blockwise_stream_kernel<2, 1, 8><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 1 && r.loop == 0)
+    gemm_blockwise_stream2_kernel<1, 4><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 2 && r.loop == 0)
+    gemm_blockwise_stream2_kernel<2, 4><<<grid, t, 0, stream>>>(a);
+  else if (kHpcDevBuild && r.mt == 1 && r.loop == 2)
+    gemm_blockwise_stream2_kernel<1, 4, false><<<grid, t, 0, stream>>>(a);
+  else if (kHpcDevBuild && r.mt == 2 && r.loop == 2)
+    gemm_blockwise_stream2_kernel<2, 4, false><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 1)
+    gemm_blockwise_stream_kernel<1, 1><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 3)
+    gemm_blockwise_stream_kernel<3, 1, 4, 3><<<grid, t, 0, stream>>>(a);
+  else if (r.mt == 4)
+    gemm_blockwise_stream_kernel<4, 1, 4, 3><<<grid, t, 0, stream>>>(a);
+  else
+    gemm_blockwise_stream_kernel<2, 1><<<grid, t, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
 
-// The argument block without y, tile_m, col_base and the epilogue fields, which the entry points set.
-// Blockwise scales: 128 x 128 weight blocks, activation scales per row and k-block.
-hpc::ggemm::Args blockwise_args(const void* x, const void* w, const void* xscale, const void* wscale, const void* seqlens,
-                                const void* cu_seqlens, const void* row_index, int n, int k, int num_block_k_pad4,
-                                int64_t xscale_row_stride, int64_t xscale_kb_stride) {
-  hpc::ggemm::Args a;
+// The argument block's fields that do not depend on the scale kind, every other one 0 / null; KB = ceil(k / 128).
+Args common_args(void* y, const void* x, const void* w, const void* seqlens, const void* cu_seqlens, const void* row_index,
+                 int n, int k) {
+  Args a{};
   a.x = static_cast<const uint8_t*>(x);
   a.w = static_cast<const uint8_t*>(w);
-  a.xs = static_cast<const float*>(xscale);
-  a.ws = static_cast<const float*>(wscale);
+  a.y = static_cast<uint16_t*>(y);
   a.seqlens = static_cast<const int*>(seqlens);
   a.cu_seqlens = static_cast<const int*>(cu_seqlens);
   a.row_index = static_cast<const int*>(row_index);
   a.N = n;
   a.K = k;
-  a.KB = k / 128;
-  a.ws_group_stride = (n / 128) * num_block_k_pad4;
-  a.ws_ntile_stride = num_block_k_pad4;
-  a.ws_kb_stride = 1;
-  a.has_xs = 1;
-  a.x_bytes = 0xfffffe00u;  // x may be indexed through row_index: rows beyond m exist (< 4 GB checked)
-  a.xs_row_stride = xscale_row_stride;
-  a.xs_kb_stride = xscale_kb_stride;
+  a.KB = (k + 127) / 128;
   return a;
 }
-// Per-tensor scales: one output scale per group, no activation scales; k_blocks = a.KB.
-hpc::ggemm::Args pertensor_args(const void* x, const void* w, const void* yscale, const void* seqlens,
-                                const void* cu_seqlens, const void* row_index, int x_rows, int n, int k, int k_blocks) {
-  hpc::ggemm::Args a;
-  a.x = static_cast<const uint8_t*>(x);
-  a.w = static_cast<const uint8_t*>(w);
-  a.xs = static_cast<const float*>(yscale);  // unused (has_xs = 0), any valid pointer
-  a.ws = static_cast<const float*>(yscale);
-  a.seqlens = static_cast<const int*>(seqlens);
-  a.cu_seqlens = static_cast<const int*>(cu_seqlens);
-  a.row_index = static_cast<const int*>(row_index);
-  a.col_base = nullptr;
-  a.N = n;
-  a.K = k;
-  a.KB = k_blocks;
-  a.tile_m = 16;
-  a.ws_group_stride = 1;
-  a.ws_ntile_stride = 0;
-  a.ws_kb_stride = 0;
-  a.has_xs = 0;
-  a.x_bytes = static_cast<unsigned>(static_cast<int64_t>(x_rows) * k);
-  a.xs_row_stride = 0;
-  a.xs_kb_stride = 0;
-  return a;
+
+// The one path of the four entries behind their operand checks: route the call, launch what the route names.  `a` carries both
+// outputs, y and (fused != null: a gate-up GEMM) the activation's; the route says which one is written.  (Only the epilogue
+// instantiations read act_scale, act_mul_scale and use_bf16_mul: a null act_out is all that a route without the epilogue needs.)
+int route_and_launch(Args a, int num_group, int m, const void* cu_tiles128, hipStream_t stream, int* fused) {
+  const GgemmRoute r = hpc::ggemm_route({a.has_xs != 0, fused != nullptr, num_group, m, a.N, a.K, cu_tiles128 != nullptr});
+  if (r.code) return r.code;
+  if (fused) *fused = r.act;
+  if (r.act)
+    a.y = nullptr;
+  else
+    a.act_out = nullptr;
+  const int* cu_tiles = static_cast<const int*>(cu_tiles128);
+  switch (r.kernel) {
+    case 4: return hpc_ggemm_launch_p8(a, r, cu_tiles, num_group, stream);
+    case 3: return hpc_ggemm_launch_tiled256(a, r, cu_tiles, num_group, stream);
+    case 2: return hpc_ggemm_launch_tiled(a, r, cu_tiles, num_group, stream);
+    default: return launch_stream(a, r, stream);
+  }
 }
 }  // namespace
 
-extern "C" int hpc_group_gemm_blockwise_fp8_async(
-    void* y_ptr, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
-    const void* cu_seqlens_ptr, const void* xscale_ptr, const void* wscale_ptr,
-    const void* row_index_ptr, const void* col_base_ptr, int num_group, int m, int n, int k,
-    int num_block_k_pad4, int tile_m, int64_t xscale_row_stride, int64_t xscale_kb_stride,
-    const void* cu_tiles128_ptr, hipStream_t stream) {
-  using namespace hpc::ggemm;
+// Blockwise scales: 128 x 128 weight blocks, activation scales per row and k-block.
+int hpc_group_gemm_blockwise_fp8_act(void* y_ptr, void* act_out, void* act_scale, const void* x_ptr, const void* w_ptr,
+                                     const void* seqlens_ptr, const void* cu_seqlens_ptr, const void* xscale_ptr,
+                                     const void* wscale_ptr, const void* row_index_ptr, const void* col_base_ptr, int num_group,
+                                     int m, int n, int k, int num_block_k_pad4, int tile_m, int64_t xscale_row_stride,
+                                     int64_t xscale_kb_stride, const void* cu_tiles128_ptr, hipStream_t stream, int* fused) {
   if (!y_ptr || !x_ptr || !w_ptr || !seqlens_ptr || !cu_seqlens_ptr || !xscale_ptr || !wscale_ptr)
     return HPC_ERR_INVALID;
   if (num_group <= 0 || n <= 0 || k <= 0) return HPC_ERR_INVALID;
@@ -614,67 +552,78 @@ extern "C" int hpc_group_gemm_blockwise_fp8_async(
   if ((n & 127) || (k & 127)) return HPC_ERR_UNSUPPORTED;  // 128x128 weight scale blocks
   if (num_block_k_pad4 < k / 128) return HPC_ERR_INVALID;
   if (static_cast<int64_t>(m) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;  // 32-bit x offsets
-  Args a = blockwise_args(x_ptr, w_ptr, xscale_ptr, wscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k,
-                          num_block_k_pad4, xscale_row_stride, xscale_kb_stride);
-  a.y = static_cast<uint16_t*>(y_ptr);
+  Args a = common_args(y_ptr, x_ptr, w_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k);
+  a.xs = static_cast<const float*>(xscale_ptr);
+  a.ws = static_cast<const float*>(wscale_ptr);
   a.col_base = static_cast<const int*>(col_base_ptr);
   a.tile_m = tile_m;
-  return launch_stream_gemm(a, num_group, m, n, cu_tiles128_ptr, stream);
+  a.ws_group_stride = (n / 128) * num_block_k_pad4;
+  a.ws_ntile_stride = num_block_k_pad4;
+  a.ws_kb_stride = 1;
+  a.has_xs = 1;
+  a.x_bytes = 0xfffffe00u;  // x may be indexed through row_index: rows beyond m exist (< 4 GB checked)
+  a.xs_row_stride = xscale_row_stride;
+  a.xs_kb_stride = xscale_kb_stride;
+  a.act_out = static_cast<uint8_t*>(act_out);
+  a.act_scale = static_cast<float*>(act_scale);
+  return route_and_launch(a, num_group, m, cu_tiles128_ptr, stream, fused);
 }
 
-// Per-tensor variant: Y = bf16( (X W^T) * y_scale[g] ), no activation scales.
+extern "C" int hpc_group_gemm_blockwise_fp8_async(
+    void* y_ptr, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
+    const void* cu_seqlens_ptr, const void* xscale_ptr, const void* wscale_ptr,
+    const void* row_index_ptr, const void* col_base_ptr, int num_group, int m, int n, int k,
+    int num_block_k_pad4, int tile_m, int64_t xscale_row_stride, int64_t xscale_kb_stride,
+    const void* cu_tiles128_ptr, hipStream_t stream) {
+  return hpc_group_gemm_blockwise_fp8_act(y_ptr, nullptr, nullptr, x_ptr, w_ptr, seqlens_ptr, cu_seqlens_ptr, xscale_ptr, wscale_ptr,
+                                          row_index_ptr, col_base_ptr, num_group, m, n, k, num_block_k_pad4, tile_m,
+                                          xscale_row_stride, xscale_kb_stride, cu_tiles128_ptr, stream, nullptr);
+}
+
+// Per-tensor variant: Y = bf16( (X W^T) * y_scale[g] ), no activation scales; the fused epilogue writes
+// e4m3(silu(gate) * up * act_mul_scale[0]).
 // reference: group_gemm_fp8_async / group_gemm_pertensor_fp8 (src/group_gemm/group_gemm.h,
 // kernels.cuh:215-530) and the gather-free cp.async path (cp_async/group_gemm_fp8_scatter.cu).
 // n % 64 == 0, k % 64 == 0.
-extern "C" int hpc_group_gemm_pertensor_fp8_async(void* y_ptr, const void* x_ptr, const void* w_ptr,
-                                                  const void* seqlens_ptr, const void* cu_seqlens_ptr,
-                                                  const void* yscale_ptr, const void* row_index_ptr,
-                                                  int num_group, int m, int x_rows, int n, int k,
-                                                  const void* cu_tiles128_ptr, hipStream_t stream) {
-  using namespace hpc::ggemm;
+int hpc_group_gemm_pertensor_fp8_act(void* y_ptr, void* act_out, const void* act_mul_scale_ptr, int use_bf16_mul,
+                                     const void* x_ptr, const void* w_ptr, const void* seqlens_ptr, const void* cu_seqlens_ptr,
+                                     const void* yscale_ptr, const void* row_index_ptr, int num_group, int m, int x_rows, int n,
+                                     int k, const void* cu_tiles128_ptr, hipStream_t stream, int* fused) {
   if (!y_ptr || !x_ptr || !w_ptr || !seqlens_ptr || !cu_seqlens_ptr || !yscale_ptr) return HPC_ERR_INVALID;
   if (num_group <= 0 || n <= 0 || k <= 0 || x_rows <= 0) return HPC_ERR_INVALID;
   if (m <= 0) return HPC_OK;
   if ((n & 63) || (k & 63)) return HPC_ERR_UNSUPPORTED;
   if (static_cast<int64_t>(x_rows) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a = pertensor_args(x_ptr, w_ptr, yscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, x_rows, n, k, (k + 127) / 128);
-  a.y = static_cast<uint16_t*>(y_ptr);
-  return launch_stream_gemm(a, num_group, m, n, cu_tiles128_ptr, stream);
-}
-
-// Gate-up GEMM of the per-tensor fused MoE with out = e4m3(silu(gate) * up * act_mul_scale[0]) in its epilogue (256 x 256
-// tile kernel; the caller has checked hpc_ggemm_p8_selected, inter % 128 == 0 and k % 128 == 0).  Same arguments as
-// hpc_group_gemm_pertensor_fp8_async with n = 2 * inter; writes act_out e4m3 [m, inter].
-int hpc_group_gemm_pertensor_fp8_act(void* act_out, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
-                                     const void* cu_seqlens_ptr, const void* yscale_ptr, const void* row_index_ptr,
-                                     const void* act_mul_scale_ptr, int use_bf16_mul, int num_group, int m, int x_rows,
-                                     int n, int k, const void* cu_tiles128_ptr, hipStream_t stream) {
-  using namespace hpc::ggemm;
-  if (static_cast<int64_t>(x_rows) * k > 0xfffffe00ll || static_cast<int64_t>(n) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a = pertensor_args(x_ptr, w_ptr, yscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, x_rows, n, k, k / 128);
-  a.y = nullptr;
+  Args a = common_args(y_ptr, x_ptr, w_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k);
+  a.xs = static_cast<const float*>(yscale_ptr);  // unused (has_xs = 0), any valid pointer
+  a.ws = static_cast<const float*>(yscale_ptr);
+  a.tile_m = 16;
+  a.ws_group_stride = 1;  // has_xs, col_base and the other scale strides stay 0
+  a.x_bytes = static_cast<unsigned>(static_cast<int64_t>(x_rows) * k);
   a.act_out = static_cast<uint8_t*>(act_out);
   a.act_mul_scale = static_cast<const float*>(act_mul_scale_ptr);
   a.use_bf16_mul = use_bf16_mul;
-  return hpc_ggemm_launch_p8(a, static_cast<const int*>(cu_tiles128_ptr), num_group, m, n, stream);
+  return route_and_launch(a, num_group, m, cu_tiles128_ptr, stream, fused);
 }
 
-// Gate-up GEMM of the fused MoE with SiLU(gate) * up + 128-block quantisation in its epilogue (256 x 256 tile kernel;
-// the caller has checked hpc_ggemm_p8_selected and inter % 128 == 0).  Same arguments as
-// hpc_group_gemm_blockwise_fp8_async with n = 2 * inter; writes act_out e4m3 [m, inter] and act_scale f32 [m, inter/128].
-int hpc_group_gemm_blockwise_fp8_act(void* act_out, void* act_scale, const void* x_ptr, const void* w_ptr,
-                                     const void* seqlens_ptr, const void* cu_seqlens_ptr, const void* xscale_ptr,
-                                     const void* wscale_ptr, const void* row_index_ptr, int num_group, int m, int n,
-                                     int k, int num_block_k_pad4, int64_t xscale_row_stride, int64_t xscale_kb_stride,
-                                     const void* cu_tiles128_ptr, hipStream_t stream) {
-  using namespace hpc::ggemm;
-  if (static_cast<int64_t>(m) * k > 0xfffffe00ll || static_cast<int64_t>(n) * k > 0xfffffe00ll) return HPC_ERR_UNSUPPORTED;
-  Args a = blockwise_args(x_ptr, w_ptr, xscale_ptr, wscale_ptr, seqlens_ptr, cu_seqlens_ptr, row_index_ptr, n, k,
-                          num_block_k_pad4, xscale_row_stride, xscale_kb_stride);
-  a.y = nullptr;
-  a.col_base = nullptr;
-  a.tile_m = 16;
-  a.act_out = static_cast<uint8_t*>(act_out);
-  a.act_scale = static_cast<float*>(act_scale);
-  return hpc_ggemm_launch_p8(a, static_cast<const int*>(cu_tiles128_ptr), num_group, m, n, stream);
+extern "C" int hpc_group_gemm_pertensor_fp8_async(void* y_ptr, const void* x_ptr, const void* w_ptr, const void* seqlens_ptr,
+                                                  const void* cu_seqlens_ptr, const void* yscale_ptr, const void* row_index_ptr,
+                                                  int num_group, int m, int x_rows, int n, int k, const void* cu_tiles128_ptr,
+                                                  hipStream_t stream) {
+  return hpc_group_gemm_pertensor_fp8_act(y_ptr, nullptr, nullptr, 0, x_ptr, w_ptr, seqlens_ptr, cu_seqlens_ptr, yscale_ptr,
+                                          row_index_ptr, num_group, m, x_rows, n, k, cu_tiles128_ptr, stream, nullptr);
 }
+
+#ifdef HPC_DEV
+// development (tests/test_ggemm_route.py): ggemm_route() on flat arrays, the members of GgemmCall and GgemmRoute in their order
+extern "C" int hpc_dev_ggemm_route(const int64_t* call, int n_in, int* route, int n_out) {
+  if (!call || !route || n_in != 7 || n_out != 18) return HPC_ERR_INVALID;
+  const auto i = [call](int k) { return static_cast<int>(call[k]); };
+  const GgemmRoute r = hpc::ggemm_route({call[0] != 0, call[1] != 0, i(2), i(3), i(4), i(5), call[6] != 0});
+  const int out[18] = {r.code,   r.kernel, r.act,          r.grid_x,       r.grid_y,    r.threads,   r.mt,
+                       r.loop,   r.tile_tokens,            r.k_tail,       r.no_dma,    r.loop_variant,
+                       r.no_half_tile,     r.nt_single,    r.tail_regs,    r.item_scan_old, r.ext_rows, r.item_order};
+  for (int k = 0; k < 18; ++k) route[k] = out[k];
+  return HPC_OK;
+}
+#endif

@@ -36,9 +36,9 @@
 //   * epilogue: neighbouring row blocks are exchanged between lane quarters (v_permlane16_swap) so that a
 //     lane stores 16 contiguous bytes of an output row instead of 8.
 #include "hpc_common.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
 #include "group_gemm.h"
+#include "group_gemm_route.h"
 
 namespace hpc {
 namespace ggemm {
@@ -1622,8 +1622,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_p8_kernel(const Args a, 
 #ifdef HPC_DEV
 // development key kDevP8LoopVariant: variant of the k-loop for the blockwise kernels (A/B runs, tools/tune_ggemm.py; tools/prof_p8.py)
 template <class Cfg>
-void launch_blockwise_variant(const Args& a, const int* cu_tiles, int num_group, dim3 grid, hipStream_t stream) {
-  if (a.act_out)
+void launch_blockwise_variant(const Args& a, bool act, const int* cu_tiles, int num_group, dim3 grid, hipStream_t stream) {
+  if (act)
     gemm_fp8_p8_kernel<Cfg, true, false, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
   else
     gemm_fp8_p8_kernel<Cfg, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
@@ -1642,57 +1642,39 @@ extern "C" int hpc_dev_p8_prof_buffer(void* p) {
 }
 #endif
 
-int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a_in, const int* cu_tiles, int num_group, int m, int n,
+int hpc_ggemm_launch_p8(const hpc::ggemm::Args& a_in, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                         hipStream_t stream) {
   using namespace hpc::ggemm;
+  static_assert(kBM == 256 && kBN == 256 && kBK == 128 && kThreads == 512, "ggemm_route() states the tile and the workgroup");
   Args a = a_in;
-  a.no_half_tile = hpc_dev_tuning_get(kDevP8NoHalfTile);  // development: 1 = full body only, 2 = no tail body
-  // a group's ONLY (<= 64-row) token tile streams its weights non-temporally (development key kDevP8TailTemporal = 1: default policy).
-  // (A four-stage form of the weight rings with a single-slab token ring - 96 instead of 64 KB of weights in flight per CU -
-  // was built, bit-identical, and measured no faster: T = 256 1 515-1 563 against 1 505-1 512 us, profiles/
-  // round5_moe_kernel_choice.txt; the stream is not bound by the bytes in flight at that point.  Removed.)
-  a.nt_single = hpc_dev_tuning_get(kDevP8TailTemporal) != 1;
-  a.tail_regs = hpc_dev_tuning_get(kDevP8TailRegs) == 1;
-  a.item_scan_old = hpc_dev_tuning_get(kDevP8ItemScanOld) == 1;
-  // a group's short tail (<= 16 rows per full tile it has) rides along with its full tiles instead of running as a tail
-  // item (blockwise scales; development key kDevP8NoRideAlong = 1: tail items for every tail, the dispatch of round 5)
-  a.ext_rows = hpc_dev_tuning_get(kDevP8NoRideAlong) != 1;
-  if (n % kBN || a.K < kBK) return HPC_ERR_UNSUPPORTED;
-  const long max_tiles = m / kBM + num_group;  // upper bound of sum_g ceil(len_g / 256)
-  const long items = max_tiles * (n / kBN) + 16;  // + 16: the per-XCD chunks of the full and of the tail tiles round up
-  // tail tiles stay next to their full siblings (order 0).  Order 1 - all full tiles first, tail tiles last, which evens
-  // out the end of a launch (the down GEMM of the MoE has ~9.4 items per CU) - measured SLOWER on the same box: gate-up /
-  // down GEMM 3493 / 1624 us against 3225 / 1583 us: a tail tile that cannot meet its weight tile in L2 streams it from
-  // memory and its DMA pieces land late (development key kDevP8TailsLast = 1 selects order 1; profiles/round5_moe_ggemm_ab.txt)
-  a.item_order = hpc_dev_tuning_get(kDevP8TailsLast) == 1 ? 1 : 0;
-  if (items > 0x7fffffffl) return HPC_ERR_UNSUPPORTED;
-  dim3 grid(static_cast<unsigned>(items));
+  a.no_half_tile = r.no_half_tile;
+  a.nt_single = r.nt_single;
+  a.tail_regs = r.tail_regs;
+  a.item_scan_old = r.item_scan_old;
+  a.ext_rows = r.ext_rows;
+  a.item_order = r.item_order;
+  const dim3 grid(r.grid_x);
+  const bool xs = a.has_xs;
+  using P = CfgProduct;
 #ifdef HPC_DEV
   a.prof = g_p8_prof;
-  if (a.has_xs && hpc_dev_tuning_get(kDevP8LoopVariant) > 0) {
-    switch (hpc_dev_tuning_get(kDevP8LoopVariant)) {
-      case 1: launch_blockwise_variant<CfgProf>(a, cu_tiles, num_group, grid, stream); break;
-      case 2: launch_blockwise_variant<CfgRound4>(a, cu_tiles, num_group, grid, stream); break;
-      case 3: launch_blockwise_variant<CfgRound4Prof>(a, cu_tiles, num_group, grid, stream); break;
-      case 4: launch_blockwise_variant<CfgNoPrio>(a, cu_tiles, num_group, grid, stream); break;
-      default: return HPC_ERR_INVALID;
-    }
-    HPC_CHECK_LAUNCH();
-    return HPC_OK;
-  }
+  if (r.loop_variant == 1) launch_blockwise_variant<CfgProf>(a, r.act, cu_tiles, num_group, grid, stream);
+  else if (r.loop_variant == 2) launch_blockwise_variant<CfgRound4>(a, r.act, cu_tiles, num_group, grid, stream);
+  else if (r.loop_variant == 3) launch_blockwise_variant<CfgRound4Prof>(a, r.act, cu_tiles, num_group, grid, stream);
+  else if (r.loop_variant == 4) launch_blockwise_variant<CfgNoPrio>(a, r.act, cu_tiles, num_group, grid, stream);
+  else
 #endif
-  using P = CfgProduct;
-  if (a.has_xs && a.act_out)
+  if (xs && r.act)
     gemm_fp8_p8_kernel<P, true, false, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (a.act_out && a.K % kBK)
+  else if (r.act && r.k_tail)  // (no call is routed here: ggemm_route() fuses at k % 128 == 0 only)
     gemm_fp8_p8_kernel<P, false, false, true, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (a.act_out)
+  else if (r.act)
     gemm_fp8_p8_kernel<P, false, false, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (kHpcDevBuild && a.has_xs && hpc_dev_tuning_get(kDevP8NoDma) == 1)
+  else if (kHpcDevBuild && r.no_dma)  // (the constant keeps the instantiation out of the product)
     gemm_fp8_p8_kernel<P, true, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (a.has_xs)
+  else if (xs)
     gemm_fp8_p8_kernel<P, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  else if (a.K % kBK)  // per-tensor scales, K % 128 == 64: the k-tail instantiation
+  else if (r.k_tail)  // per-tensor scales, K % 128 == 64: the k-tail instantiation
     gemm_fp8_p8_kernel<P, false, false, false, true><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
   else
     gemm_fp8_p8_kernel<P, false><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);

@@ -10,6 +10,7 @@
 #include "hpc_common.h"
 #include "../../include/hpc_amd.h"
 #include "group_gemm.h"
+#include "group_gemm_route.h"
 
 namespace hpc {
 namespace ggemm {
@@ -159,13 +160,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_fp8_tiled_kernel(const Args 
 }  // namespace ggemm
 }  // namespace hpc
 
-int hpc_ggemm_launch_tiled(const hpc::ggemm::Args& a, const int* cu_tiles, int num_group, int m, int n,
+int hpc_ggemm_launch_tiled(const hpc::ggemm::Args& a, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                            hipStream_t stream) {
   using namespace hpc::ggemm;
-  if (n % kTile) return HPC_ERR_UNSUPPORTED;
-  const int max_tiles = m / kTile + num_group;  // upper bound of sum_g ceil(len_g / 128)
-  dim3 grid(n / kTile, max_tiles);
-  gemm_fp8_tiled_kernel<<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
+  static_assert(kTile == 128 && kThreads == 256, "ggemm_route() states the tile and the workgroup");
+  gemm_fp8_tiled_kernel<<<dim3(r.grid_x, r.grid_y), r.threads, 0, stream>>>(a, cu_tiles, num_group);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }

@@ -17,9 +17,9 @@
 //     scale is a scalar load; fp32 partial of a 128-k block is rescaled into the running sum as before;
 //   * DMA issue is spread over the k-step and the instruction order pinned (see the pipeline comment).
 #include "hpc_common.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
 #include "group_gemm.h"
+#include "group_gemm_route.h"
 
 namespace hpc {
 namespace ggemm {
@@ -359,30 +359,18 @@ extern "C" int hpc_debug_tiled256_prof(unsigned long long* out16, int reset) {
 }
 #endif
 
-int hpc_ggemm_launch_tiled256(const hpc::ggemm::Args& a, const int* cu_tiles, int num_group, int m, int n,
+int hpc_ggemm_launch_tiled256(const hpc::ggemm::Args& a, const hpc::GgemmRoute& r, const int* cu_tiles, int num_group,
                               hipStream_t stream) {
   using namespace hpc::ggemm;
-  if (n % kBN || a.K < kBK) return HPC_ERR_UNSUPPORTED;
-  // The 32-token-tile form (4-slab ring: three weight slabs in flight) was meant for 40-128 tokens per
-  // group; measured it is SLOWER (E64: 3.6 ms vs 2.2 ms at T = 256 .. 768) - its extra token tiles re-read
-  // the weight tile through L2 and do a quarter of the MFMA work per slab - so it only runs on request.
-  const bool narrow = hpc_dev_tuning_get(kDevTiled256Form) == 2;
-  // 64-token tiles (8 x 1 waves of 32 x 64, 42 KB per slab, three slabs in the ring) - also measured SLOWER than
-  // the 128-token tile on groups of 24-64 rows (E64: T = 256 2.19 vs 1.73 ms, T = 384 2.25 vs 1.75 ms): on request only
-  const bool half = hpc_dev_tuning_get(kDevTiled256Form) == 3;
-  const long max_tiles = m / kBM + num_group;  // upper bound of sum_g ceil(len_g / 128)
-  const long items = max_tiles * (n / kBN) * (narrow ? 4 : (half ? 2 : 1)) + 8;  // + 8: the per-XCD chunks round up
-  if (items > 0x7fffffffl) return HPC_ERR_UNSUPPORTED;
-  dim3 grid(static_cast<unsigned>(items));
-  if (a.has_xs) {
-    if (narrow) gemm_fp8_tiled256_kernel<true, 32><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-    else if (half) gemm_fp8_tiled256_kernel<true, 64><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-    else gemm_fp8_tiled256_kernel<true, 128><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  } else {
-    if (narrow) gemm_fp8_tiled256_kernel<false, 32><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-    else if (half) gemm_fp8_tiled256_kernel<false, 64><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-    else gemm_fp8_tiled256_kernel<false, 128><<<grid, kThreads, 0, stream>>>(a, cu_tiles, num_group);
-  }
+  static_assert(kBM == 128 && kBN == 256 && kBK == 128 && kThreads == 512, "ggemm_route() states the tile and the workgroup");
+  const dim3 grid(r.grid_x);
+  const bool xs = a.has_xs;
+  if (xs && r.tile_tokens == 32) gemm_fp8_tiled256_kernel<true, 32><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
+  else if (xs && r.tile_tokens == 64) gemm_fp8_tiled256_kernel<true, 64><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
+  else if (xs) gemm_fp8_tiled256_kernel<true, 128><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
+  else if (r.tile_tokens == 32) gemm_fp8_tiled256_kernel<false, 32><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
+  else if (r.tile_tokens == 64) gemm_fp8_tiled256_kernel<false, 64><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
+  else gemm_fp8_tiled256_kernel<false, 128><<<grid, r.threads, 0, stream>>>(a, cu_tiles, num_group);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }

@@ -640,3 +640,30 @@ def test_reformat_x_scale_and_deepep_group_gemm(num_group, actual_m, m):
     for i in range(num_group):
         a, c = int(cu[i]), int(seqlens[i])
         assert allclose(gt[a : a + c].float(), my.cpu()[a : a + c].float(), rtol=0.01, atol=0.05)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("num_tokens", [8, 256])  # 2 / 64 rows per expert: the streaming kernel / the 256 x 256 kernel with the epilogue
+def test_fuse_moe_blockwise_refuses_short_weight_scale_rows(num_tokens):
+    """gate_up_ws_pad4 < hidden / 128 is HPC_ERR_INVALID whichever kernel the gate-up GEMM routes to: the fused form goes
+    through the operand checks of the plain grouped GEMM entry (it used to read past the scale rows instead)."""
+    import hpc
+
+    lib = hpc._C.lib
+    topk, E, H, I = 2, 8, 512, 256
+    d = "cuda"
+    ids = torch.sort(torch.multinomial(torch.ones(num_tokens, E), topk).to(torch.int32), dim=1)[0].to(d)
+    sc = torch.full((num_tokens, topk), 0.5, device=d)
+    x = torch.zeros((num_tokens, H), device=d).to(F8)
+    xs = torch.ones((num_tokens, H // 128), device=d)
+    guw, guws = torch.zeros((E, 2 * I, H), device=d).to(F8), torch.ones((E, 2 * I // 128, 4), device=d)
+    dw, dws = torch.zeros((E, H, I), device=d).to(F8), torch.ones((E, H // 128, 4), device=d)
+    ws = torch.zeros(lib.hpc_fuse_moe_blockwise_workspace_bytes(num_tokens, topk, H, 2 * I, E), dtype=torch.uint8, device=d)
+    y = torch.zeros((num_tokens, H), dtype=torch.bfloat16, device=d)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    call = lambda pad4: lib.hpc_fuse_moe_blockwise_async(  # noqa: E731
+        p(y), p(ws), p(x), p(xs), p(guw), p(guws), p(dw), p(dws), p(ids), p(sc), None, num_tokens, H, 2 * I, topk, E, E, pad4, 4,
+        0, None)
+    assert call(3) == -2  # HPC_ERR_INVALID: hidden / 128 = 4 scales per row
+    assert call(4) == 0
+    torch.cuda.synchronize()

@@ -140,17 +140,27 @@ def test_count_and_gather_bit_exact():
     assert torch.equal(tiles.cpu(), (cnt_ref + 7) // 8)
 
 
+def _eight_groups(actual_m):
+    return [actual_m, actual_m, 0] + [actual_m] * 5
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("actual_m", [8, 30, 70])
-def test_group_gemm_pertensor(actual_m):
+@pytest.mark.parametrize("seqlens,n,k", [
+    pytest.param(_eight_groups(8), 1024, 1792, id="8"), pytest.param(_eight_groups(30), 1024, 1792, id="30"),
+    pytest.param(_eight_groups(70), 1024, 1792, id="70"),
+    # rows of the routing table that no other case launches with every development key at 0, 43 rows per group:
+    # k < 128 keeps the call off the 256 x 256 kernel: the 128 x 128 kernel with half a k-block
+    pytest.param([0, 1, 129], 256, 64, id="k64_tiled128"),
+    # n % 128 == 64 keeps it off every tile kernel: the streaming kernel at 48 tokens per pass
+    pytest.param([0, 1, 129], 192, 128, id="n192_stream48")])
+def test_group_gemm_pertensor(seqlens, n, k):
     import hpc
     from oracle import fuse_moe as omoe
 
     torch.manual_seed(0)
-    G, n, k = 8, 1024, 1792
-    seqlens = torch.full((G,), actual_m, dtype=torch.int32)
-    seqlens[2] = 0
-    total = int(seqlens.sum())
+    seqlens = torch.tensor(seqlens, dtype=torch.int32)
+    G, actual_m, total = len(seqlens), int(seqlens.max()), int(seqlens.sum())
+    # (num_seq_per_group_avg below gets the longest group; the per-tensor op ignores it - it has no tile-padded scale layout)
     x = torch.randn((total, k)).to(F8)
     w = torch.randn((G, n, k)).to(F8)
     scale = torch.rand(G) + 0.5

@@ -15,6 +15,7 @@
 //    count_and_gather op still produces the reference's gathered / transposed layouts.
 //  * Everything is launched back to back on one stream (hipGraph-capturable, no host sync).
 #include "hpc_common.h"
+#include "act_quant.h"
 #include "group_gemm.h"
 #include "../../include/hpc_amd.h"
 
@@ -239,9 +240,8 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(
     xs_t[static_cast<long>(kb) * m_pad + col] = x_scale[static_cast<long>(tok) * nkb + kb];
 }
 
-// a = silu(gate) * up in fp32 on the bf16 GEMM output, per 128 columns: scale = amax/448,
-// q = e4m3(a / (scale + 1e-8)).  16 lanes x 8 columns = one quant block.
-// out_scale[row * os_row_stride + jb * os_blk_stride].
+// a = silu(gate) * up in fp32 on the bf16 GEMM output, quantised per 128 columns (arithmetic: act_quant.h).
+// 16 lanes x 8 columns = one quant block.  out_scale[row * os_row_stride + jb * os_blk_stride].
 __global__ __launch_bounds__(kThreads) void act_mul_blockwise_quant_kernel(
     const uint16_t* __restrict__ gate_up, const int* __restrict__ num_rows_ptr, int max_rows,
     int inter, uint8_t* __restrict__ out, float* __restrict__ out_scale, long os_row_stride,
@@ -263,16 +263,16 @@ __global__ __launch_bounds__(kThreads) void act_mul_blockwise_quant_kernel(
     for (int j = 0; j < 4; ++j) {
       const float g0 = bf16lo_to_f32(gv[j]), g1 = bf16hi_to_f32(gv[j]);
       const float u0 = bf16lo_to_f32(uv[j]), u1 = bf16hi_to_f32(uv[j]);
-      a[2 * j] = g0 / (1.0f + __expf(-g0)) * u0;
-      a[2 * j + 1] = g1 / (1.0f + __expf(-g1)) * u1;
+      a[2 * j] = silu_mul(g0, u0);
+      a[2 * j + 1] = silu_mul(g1, u1);
       amax = fmaxf(amax, fmaxf(fabsf(a[2 * j]), fabsf(a[2 * j + 1])));
     }
   }
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
   if (!ok) return;
-  const float scale = amax / 448.0f;
-  const float inv = 1.0f / (scale + 1e-8f);
+  const float scale = e4m3_block_scale(amax);
+  const float inv = e4m3_block_inv(scale);
   u32x2 q;
   q[0] = quant_4xe4m3(a[0] * inv, a[1] * inv, a[2] * inv, a[3] * inv);
   q[1] = quant_4xe4m3(a[4] * inv, a[5] * inv, a[6] * inv, a[7] * inv);
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void act_mul_blockwise_quant_kernel(
 }
 
 // Per-tensor variant: q = e4m3( silu(gate) * up * scale[0] ); with use_bf16_mul the product is formed
-// in bf16 like the reference kernel (src/activation/activation.cu:19-75, :54-65).
+// in bf16 like the reference kernel (act_quant.h::silu_mul_scaled).
 __global__ __launch_bounds__(kThreads) void act_mul_quant_kernel(
     const uint16_t* __restrict__ gate_up, const float* __restrict__ scale,
     const int* __restrict__ num_rows_ptr, int max_rows, int inter, int use_bf16_mul,
@@ -303,10 +303,10 @@ __global__ __launch_bounds__(kThreads) void act_mul_quant_kernel(
   for (int j = 0; j < 4; ++j) {
     const float g0 = bf16lo_to_f32(gv[j]), g1 = bf16hi_to_f32(gv[j]);
     const float u0 = bf16lo_to_f32(uv[j]), u1 = bf16hi_to_f32(uv[j]);
-    float s0 = g0 / (1.0f + __expf(-g0)), s1 = g1 / (1.0f + __expf(-g1));
-    if (use_bf16_mul) {
-      s0 = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(s0)) * u0));
-      s1 = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(s1)) * u1));
+    float s0 = silu(g0), s1 = silu(g1);
+    if (use_bf16_mul) {  // silu_mul_scaled for the pair, under one branch
+      s0 = mul_bf16_rounded(s0, u0);
+      s1 = mul_bf16_rounded(s1, u1);
     } else {
       s0 *= u0;
       s1 *= u1;

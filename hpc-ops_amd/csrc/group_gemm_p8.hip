@@ -36,6 +36,7 @@
 //   * epilogue: neighbouring row blocks are exchanged between lane quarters (v_permlane16_swap) so that a
 //     lane stores 16 contiguous bytes of an output row instead of 8.
 #include "hpc_common.h"
+#include "act_quant.h"
 #include "../../include/hpc_amd.h"
 #include "group_gemm.h"
 #include "group_gemm_route.h"
@@ -248,6 +249,17 @@ struct CfgNoPrio : CfgProduct { static constexpr bool kPrio = false; };
 //  MFMAs, DMA pieces before the operand reads, DMA slot schedules with no piece in a load section / in an MMA section -
 //  all within noise of or behind the product loop once the carried tails were in)
 #endif
+
+// Plain epilogue of both bodies: a lane holds 4 rows (8 bytes) of a token's output row in each of two adjacent row blocks
+// a, b.  v_permlane16_swap hands lane quarter q the 8 rows [(q&2)*4, +8) of block (q&1): 16 contiguous bytes per store,
+// half as many stores.  Every lane takes part in the swap, so the `slot < m_cnt` guard and the store stay with the caller.
+__device__ __forceinline__ u32x4 swap_row_pair(const f32x4& a, const f32x4& b) {
+  const uint32_t a0 = pack_bf16x2(a[0], a[1]), a1 = pack_bf16x2(a[2], a[3]);
+  const uint32_t b0 = pack_bf16x2(b[0], b[1]), b1 = pack_bf16x2(b[2], b[3]);
+  const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
+  const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+  return u32x4{s0[0], s1[0], s0[1], s1[1]};
+}
 
 // kNoDma (development key kDevP8NoDma = 1, timing only - results are wrong): no DMA inside the k-loop
 // kAct: the gate-up GEMM of the fused MoE - a tile is 128 gate rows (wave group 0) + the 128 up rows of the same
@@ -827,8 +839,8 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
     // columns x 64 tokens, in the same lane <-> (column, token) mapping.  They swap halves through LDS (a
     // lane-linear 8-byte slot per block, bf16-rounded like the GEMM output the separate kernel would read): group
     // 0 finishes token blocks 0-1, group 1 token blocks 2-3.  a = silu(g) * u in fp32, abs-max over the tile's 128
-    // columns per token (32 values in the lane, 4 lanes per token), scale = amax / 448, q = e4m3(a / (scale + 1e-8)) -
-    // the arithmetic of act_mul_blockwise_quant_kernel (reference src/activation/activation.cu:282-355), bit for bit.
+    // columns per token (32 values in the lane, 4 lanes per token), then the scale and the cast: the arithmetic is
+    // act_quant.h's, which act_mul_blockwise_quant_kernel calls too.
     __builtin_amdgcn_s_barrier();  // every wave is past its last LDS read and its last (empty) DMA has landed
     uint32_t* xch = reinterpret_cast<uint32_t*>(s_mem) + (wm * 16 * 64 + lane) * 2;  // [strip][i * 2 + jj][lane] of 8 B
     // (half tile: only token blocks 0-1 exist - group 1 sends its up values, group 0 finishes, nothing else)
@@ -849,27 +861,18 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
         const int j = j0 + jj;
         const int slot = mt0 + row_of_slot(wm * 64 + j * 16 + r16);
         if constexpr (!kHasXs) {
-          // per-tensor API: a = silu(g) * u (bf16-rounded factors and product when use_bf16_mul), times one scale -
-          // the arithmetic of act_mul_quant_kernel (csrc/fuse_moe.hip), value for value
+          // per-tensor API: one scale, no abs-max (act_quant.h::silu_mul_scaled, as act_mul_quant_kernel)
           const float sc = a.act_mul_scale[0];
           uint8_t* orow = a.act_out + static_cast<long>(m0 + slot) * inter + col0 + g4 * 4;
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const u32x2 ov = *reinterpret_cast<const u32x2*>(xch + (i * 2 + jj) * 128);
-            const uint32_t m01 = pack_bf16x2(tot[i][j][0], tot[i][j][1]), m23 = pack_bf16x2(tot[i][j][2], tot[i][j][3]);
-            const float mine[4] = {bf16lo_to_f32(m01), bf16hi_to_f32(m01), bf16lo_to_f32(m23), bf16hi_to_f32(m23)};
-            const float oth[4] = {bf16lo_to_f32(ov[0]), bf16hi_to_f32(ov[0]), bf16lo_to_f32(ov[1]), bf16hi_to_f32(ov[1])};
-            float v[4];
+            float mine[4], oth[4], v[4];
+            bf16x4_to_f32(pack_bf16x2(tot[i][j][0], tot[i][j][1]), pack_bf16x2(tot[i][j][2], tot[i][j][3]), mine);
+            bf16x4_to_f32(ov[0], ov[1], oth);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float g = kGate ? mine[r] : oth[r], u = kGate ? oth[r] : mine[r];
-              float sv = g / (1.0f + __expf(-g));
-              if (a.use_bf16_mul)
-                sv = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(sv)) * u));
-              else
-                sv *= u;
-              v[r] = sv * sc;
-            }
+            for (int r = 0; r < 4; ++r)
+              v[r] = silu_mul_scaled(kGate ? mine[r] : oth[r], kGate ? oth[r] : mine[r], a.use_bf16_mul, sc);
             if (slot < m_cnt) *reinterpret_cast<uint32_t*>(orow + i * 16) = quant_4xe4m3(v[0], v[1], v[2], v[3]);
           }
           continue;
@@ -878,13 +881,12 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const u32x2 ov = *reinterpret_cast<const u32x2*>(xch + (i * 2 + jj) * 128);
-          const uint32_t m01 = pack_bf16x2(tot[i][j][0], tot[i][j][1]), m23 = pack_bf16x2(tot[i][j][2], tot[i][j][3]);
-          const float mine[4] = {bf16lo_to_f32(m01), bf16hi_to_f32(m01), bf16lo_to_f32(m23), bf16hi_to_f32(m23)};
-          const float oth[4] = {bf16lo_to_f32(ov[0]), bf16hi_to_f32(ov[0]), bf16lo_to_f32(ov[1]), bf16hi_to_f32(ov[1])};
+          float mine[4], oth[4];
+          bf16x4_to_f32(pack_bf16x2(tot[i][j][0], tot[i][j][1]), pack_bf16x2(tot[i][j][2], tot[i][j][3]), mine);
+          bf16x4_to_f32(ov[0], ov[1], oth);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float g = kGate ? mine[r] : oth[r], u = kGate ? oth[r] : mine[r];
-            const float v = g / (1.0f + __expf(-g)) * u;
+            const float v = silu_mul(kGate ? mine[r] : oth[r], kGate ? oth[r] : mine[r]);
             tot[i][j][r] = v;
             amax = fmaxf(amax, fabsf(v));
           }
@@ -892,8 +894,8 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
         // the token's other 96 columns sit in lanes r16 + 16, + 32, + 48
         amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
         amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        const float scale = amax / 448.0f;
-        const float inv = 1.0f / (scale + 1e-8f);
+        const float scale = e4m3_block_scale(amax);
+        const float inv = e4m3_block_inv(scale);
         if (slot < m_cnt) {
           uint8_t* orow = a.act_out + static_cast<long>(m0 + slot) * inter + col0 + g4 * 4;
 #pragma unroll
@@ -908,7 +910,7 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
     // into the second; each then reads the other's region
     // ride-along block: the up wave hands its two blocks (columns 16 wm .. and 64 + 16 wm .. of the tile's 128) to the gate
     // wave of the same strip index through the (now idle) ride-along row buffers; the token's abs-max over the 128 columns
-    // is folded over the four gate waves through the scale buffers - the tail body's epilogue (tail_finish), value for value
+    // is folded over the four gate waves through the scale buffers, as in the tail body's epilogue (tail_finish)
     uint32_t* ext_xch = reinterpret_cast<uint32_t*>(s_mem + kExtOff) + (wm * 2 * 64 + lane) * 2;  // [wm][unit][lane] of 8 B
     float* ext_red = reinterpret_cast<float*>(s_mem + kExtXsOff);                                 // [wm][16 tokens]
     if (wn == 0) {
@@ -925,27 +927,18 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
     }
     __syncthreads();
     if constexpr (kExt && !kHasXs) {
-      // per-tensor API: a = silu(g) * u (bf16-rounded factors and product when use_bf16_mul), times one scale - `finish` above,
-      // value for value; no abs-max, so no second barrier
+      // per-tensor API: one scale, no abs-max, so no second barrier
       if (wn == 0 && r16 < ext_cnt) {
         const float sc = a.act_mul_scale[0];
         uint8_t* orow = a.act_out + static_cast<long>(m0 + ext0 + r16) * inter + col0 + wm * 16 + g4 * 4;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const u32x2 ov = *reinterpret_cast<const u32x2*>(ext_xch + u * 128);
-          const uint32_t m01 = pack_bf16x2(tot_ext[u][0], tot_ext[u][1]), m23 = pack_bf16x2(tot_ext[u][2], tot_ext[u][3]);
-          const float gv[4] = {bf16lo_to_f32(m01), bf16hi_to_f32(m01), bf16lo_to_f32(m23), bf16hi_to_f32(m23)};
-          const float uv[4] = {bf16lo_to_f32(ov[0]), bf16hi_to_f32(ov[0]), bf16lo_to_f32(ov[1]), bf16hi_to_f32(ov[1])};
-          float v[4];
+          float gv[4], uv[4], v[4];
+          bf16x4_to_f32(pack_bf16x2(tot_ext[u][0], tot_ext[u][1]), pack_bf16x2(tot_ext[u][2], tot_ext[u][3]), gv);
+          bf16x4_to_f32(ov[0], ov[1], uv);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float sv = gv[r] / (1.0f + __expf(-gv[r]));
-            if (a.use_bf16_mul)
-              sv = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(sv)) * uv[r]));
-            else
-              sv *= uv[r];
-            v[r] = sv * sc;
-          }
+          for (int r = 0; r < 4; ++r) v[r] = silu_mul_scaled(gv[r], uv[r], a.use_bf16_mul, sc);
           *reinterpret_cast<uint32_t*>(orow + u * 64) = quant_4xe4m3(v[0], v[1], v[2], v[3]);
         }
       }
@@ -956,12 +949,12 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const u32x2 ov = *reinterpret_cast<const u32x2*>(ext_xch + u * 128);
-          const uint32_t m01 = pack_bf16x2(tot_ext[u][0], tot_ext[u][1]), m23 = pack_bf16x2(tot_ext[u][2], tot_ext[u][3]);
-          const float gv[4] = {bf16lo_to_f32(m01), bf16hi_to_f32(m01), bf16lo_to_f32(m23), bf16hi_to_f32(m23)};
-          const float uv[4] = {bf16lo_to_f32(ov[0]), bf16hi_to_f32(ov[0]), bf16lo_to_f32(ov[1]), bf16hi_to_f32(ov[1])};
+          float gv[4], uv[4];
+          bf16x4_to_f32(pack_bf16x2(tot_ext[u][0], tot_ext[u][1]), pack_bf16x2(tot_ext[u][2], tot_ext[u][3]), gv);
+          bf16x4_to_f32(ov[0], ov[1], uv);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = gv[r] / (1.0f + __expf(-gv[r])) * uv[r];
+            const float v = silu_mul(gv[r], uv[r]);
             tot_ext[u][r] = v;
             amax = fmaxf(amax, fabsf(v));
           }
@@ -973,8 +966,8 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
       __syncthreads();
       if (wn == 0 && r16 < ext_cnt) {
         const float amax = fmaxf(fmaxf(ext_red[r16], ext_red[16 + r16]), fmaxf(ext_red[32 + r16], ext_red[48 + r16]));
-        const float scale = amax / 448.0f;
-        const float inv = 1.0f / (scale + 1e-8f);
+        const float scale = e4m3_block_scale(amax);
+        const float inv = e4m3_block_inv(scale);
         const long row = static_cast<long>(m0 + ext0 + r16);
         uint8_t* orow = a.act_out + row * inter + col0 + wm * 16 + g4 * 4;
 #pragma unroll
@@ -995,19 +988,15 @@ __device__ __forceinline__ void p8_body(const Args& a, uint8_t* s_mem, int e, in
   }
   // ---- epilogue ---------------------------------------------------------------------------------------------
   // A lane holds rows n = wn*128 + i*16 + g4*4 + r of token slot wm*64 + j*16 + r16: 8 bytes of the token's output
-  // row per block.  v_permlane16_swap on the blocks i, i+1 hands lane quarter q the 8 rows [(q&2)*4, +8) of block
-  // i + (q&1): 16 contiguous bytes per store, half as many stores.
+  // row per block; the blocks i, i+1 go out together (swap_row_pair).
 #pragma unroll
   for (int j = 0; j < kJ; ++j) {
     const int slot = mt0 + row_of_slot(wm * 64 + j * 16 + r16);
     uint16_t* yrow = a.y + static_cast<long>(m0 + slot) * a.N + n0 + wn * 128 + (g4 & 1) * 16 + (g4 >> 1) * 8;
 #pragma unroll
     for (int i = 0; i < 8; i += 2) {
-      const uint32_t a0 = pack_bf16x2(tot[i][j][0], tot[i][j][1]), a1 = pack_bf16x2(tot[i][j][2], tot[i][j][3]);
-      const uint32_t b0 = pack_bf16x2(tot[i + 1][j][0], tot[i + 1][j][1]), b1 = pack_bf16x2(tot[i + 1][j][2], tot[i + 1][j][3]);
-      const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-      if (slot < m_cnt) *reinterpret_cast<u32x4*>(yrow + i * 16) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+      const u32x4 v = swap_row_pair(tot[i][j], tot[i + 1][j]);  // every lane takes part in the swap: outside the guard
+      if (slot < m_cnt) *reinterpret_cast<u32x4*>(yrow + i * 16) = v;
     }
   }
   if constexpr (kExt) {  // the ride-along block: rows 16 wm + 4 g4 .. + 3 and 64 + the same of the wave's half, token ext0 + r16
@@ -1040,7 +1029,7 @@ __device__ __forceinline__ void tail_finish(const Args& a, uint8_t* s_mem, f32x4
   if constexpr (kAct) {
     // ---- fused activation epilogue: waves 4-7 hand their up values (bf16-rounded like the GEMM output the separate kernel
     // would read) to the gate wave of the same columns; blockwise form: the 128-column abs-max of a token is the maximum
-    // over the four gate waves' 32 columns, through LDS.  Arithmetic of the full body's epilogue, value for value.
+    // over the four gate waves' 32 columns, through LDS.  The arithmetic is act_quant.h's, as in the full body's epilogue.
     __syncthreads();  // every wave is past its last LDS read; its last (empty) DMA has landed
     uint32_t* xch = reinterpret_cast<uint32_t*>(s_mem) + (((wave & 3) * 8) * 64 + lane) * 2;  // [gate wave][i * 4 + j][lane] of 8 B
     float* red = reinterpret_cast<float*>(s_mem + 16384);                                      // [gate wave][64 tokens]
@@ -1060,23 +1049,16 @@ __device__ __forceinline__ void tail_finish(const Args& a, uint8_t* s_mem, f32x4
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const u32x2 ov = *reinterpret_cast<const u32x2*>(xch + (i * 4 + j) * 128);
-          const uint32_t m01 = pack_bf16x2(tot[i][j][0], tot[i][j][1]), m23 = pack_bf16x2(tot[i][j][2], tot[i][j][3]);
-          const float gv[4] = {bf16lo_to_f32(m01), bf16hi_to_f32(m01), bf16lo_to_f32(m23), bf16hi_to_f32(m23)};
-          const float uv[4] = {bf16lo_to_f32(ov[0]), bf16hi_to_f32(ov[0]), bf16lo_to_f32(ov[1]), bf16hi_to_f32(ov[1])};
+          float gv[4], uv[4];
+          bf16x4_to_f32(pack_bf16x2(tot[i][j][0], tot[i][j][1]), pack_bf16x2(tot[i][j][2], tot[i][j][3]), gv);
+          bf16x4_to_f32(ov[0], ov[1], uv);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float g = gv[r], u = uv[r];
             float v;
-            if constexpr (kHasXs) {
-              v = g / (1.0f + __expf(-g)) * u;
-            } else {
-              float sv = g / (1.0f + __expf(-g));
-              if (a.use_bf16_mul)
-                sv = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(sv)) * u));
-              else
-                sv *= u;
-              v = sv * a.act_mul_scale[0];
-            }
+            if constexpr (kHasXs)
+              v = silu_mul(gv[r], uv[r]);
+            else  // silu_mul_scaled, with the scale read behind the use_bf16_mul branch
+              v = silu_mul_pt(gv[r], uv[r], a.use_bf16_mul) * a.act_mul_scale[0];
             tot[i][j][r] = v;
             amax = fmaxf(amax, fabsf(v));
           }
@@ -1097,8 +1079,8 @@ __device__ __forceinline__ void tail_finish(const Args& a, uint8_t* s_mem, f32x4
         if constexpr (kHasXs) {
           const int t = j * 16 + r16;
           const float amax = fmaxf(fmaxf(red[t], red[64 + t]), fmaxf(red[128 + t], red[192 + t]));
-          scale = amax / 448.0f;
-          inv = 1.0f / (scale + 1e-8f);
+          scale = e4m3_block_scale(amax);
+          inv = e4m3_block_inv(scale);
         }
         if (slot < m_cnt) {
           uint8_t* orow = a.act_out + static_cast<long>(m0 + slot) * inter + col0 + wave * 32 + g4 * 4;
@@ -1119,11 +1101,8 @@ __device__ __forceinline__ void tail_finish(const Args& a, uint8_t* s_mem, f32x4
   for (int j = 0; j < 4; ++j) {
     const int slot = mt0 + j * 16 + r16;
     uint16_t* yrow = a.y + static_cast<long>(m0 + slot) * a.N + n0 + wave * 32 + (g4 & 1) * 16 + (g4 >> 1) * 8;
-    const uint32_t a0 = pack_bf16x2(tot[0][j][0], tot[0][j][1]), a1 = pack_bf16x2(tot[0][j][2], tot[0][j][3]);
-    const uint32_t b0 = pack_bf16x2(tot[1][j][0], tot[1][j][1]), b1 = pack_bf16x2(tot[1][j][2], tot[1][j][3]);
-    const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-    const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-    if (slot < m_cnt) *reinterpret_cast<u32x4*>(yrow) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+    const u32x4 v = swap_row_pair(tot[0][j], tot[1][j]);
+    if (slot < m_cnt) *reinterpret_cast<u32x4*>(yrow) = v;
   }
 }
 

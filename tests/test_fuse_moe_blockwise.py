@@ -4,7 +4,7 @@ and tests/test_group_gemm_blockwise.py:50-120."""
 import pytest
 import torch
 
-from utils import allclose, dev_set, moe_allclose
+from utils import EPILOGUE_SITE_ROWS, allclose, dev_set, moe_allclose, topk1_ids_with_rows
 
 F8 = torch.float8_e4m3fn
 
@@ -197,6 +197,33 @@ def test_fused_activation_epilogue(num_tokens, num_expert, num_topk, hidden, int
         dev_set(19, 0)
     assert torch.equal(fused, apart)
     assert allclose(gt.float(), fused.cpu().float(), rtol=0.01, atol=0.01)
+
+
+@pytest.mark.dev
+@pytest.mark.gpu
+def test_fused_activation_epilogue_every_site():
+    """test_fused_activation_epilogue with constructed routing: num_topk = 1 and expert e receives exactly
+    EPILOGUE_SITE_ROWS[e] = 265 / 40 / 100 / 456 / 296 of the 1157 tokens (hidden 512, inter 256), which puts one group
+    through each site of the blockwise epilogue: 265 a full tile with a 9-row ride-along block, 40 the tail body as the
+    group's only tile, 100 the half-tile body, 456 a full tile and a 200-row last tile on the full body, 296 a full
+    tile and a 40-row tail body that is not the only tile (tests/utils.py states where each choice is made).  Every
+    site calls csrc/act_quant.h, as the separate activation kernel does: bit-equal with development key 19 at 0 and 1."""
+    import hpc
+
+    num_expert, hidden, inter = len(EPILOGUE_SITE_ROWS), 512, 256
+    args = list(_inputs(sum(EPILOGUE_SITE_ROWS), 1, hidden, inter, num_expert, 1, False, seed=5))
+    args[6] = topk1_ids_with_rows(EPILOGUE_SITE_ROWS)
+    dev = [t.cuda() if t is not None else None for t in args]
+    run = lambda: hpc.fuse_moe_blockwise_fp8(dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], 0, num_expert)  # noqa: E731
+    fused = run()
+    dev_set(19, 1)
+    try:
+        apart = run()
+        torch.cuda.synchronize()
+    finally:
+        dev_set(19, 0)
+    assert torch.equal(fused, apart)
+    assert bool(fused.float().abs().sum(-1).gt(0).all())  # every token got its expert's output
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ and tests/test_act.py:45-59."""
 import pytest
 import torch
 
-from utils import allclose, dev_set
+from utils import EPILOGUE_SITE_ROWS, allclose, dev_set, topk1_ids_with_rows
 
 F8 = torch.float8_e4m3fn
 
@@ -76,6 +76,41 @@ def test_fuse_moe_pertensor_activation_epilogue(use_bf16_mul, num_seq, hidden, i
         dev_set(19, 0)
     assert torch.equal(fused, apart)
     assert allclose(gt.float(), fused.cpu().float(), rtol=0.08, atol=0.1)
+
+
+@pytest.mark.dev
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_bf16_mul", [False, True])
+def test_fuse_moe_pertensor_activation_epilogue_every_site(use_bf16_mul):
+    """test_fuse_moe_pertensor_activation_epilogue with constructed routing: topk = 1 and expert e receives exactly
+    EPILOGUE_SITE_ROWS[e] = 265 / 40 / 100 / 456 / 296 of the 1157 tokens (hidden 512, inter 256), which puts one group
+    through each site of the per-tensor epilogue: 265 a full tile with a 9-row ride-along block, 40 the tail body as the
+    group's only tile, 100 the half-tile body, 456 a full tile and a 200-row last tile on the full body, 296 a full
+    tile and a 40-row tail body that is not the only tile (tests/utils.py states where each choice is made).  Every
+    site calls csrc/act_quant.h, as the separate activation kernel does: bit-equal with development key 19 at 0 and 1."""
+    import hpc
+
+    torch.manual_seed(11)
+    num_expert, hidden, inter = len(EPILOGUE_SITE_ROWS), 512, 256
+    num_seq = sum(EPILOGUE_SITE_ROWS)
+    ids = topk1_ids_with_rows(EPILOGUE_SITE_ROWS)
+    x = (torch.randn((num_seq, hidden)) / 100).to(F8)
+    guw = torch.randn((num_expert, inter * 2, hidden)).to(F8)
+    dw = torch.randn((num_expert, hidden, inter)).to(F8)
+    gus, ds, ams = torch.rand(num_expert) + 0.5, torch.rand(num_expert) + 0.5, torch.rand(1) + 0.5
+    sc = torch.rand((num_seq, 1)) + 0.5
+    c = lambda t: t.cuda()  # noqa: E731
+    run = lambda: hpc.fuse_moe_pertensor_fp8(c(x), c(guw), c(dw), c(gus), c(ds), c(ams), c(ids), c(sc), 0, num_expert,  # noqa: E731
+                                             use_bf16_mul=use_bf16_mul)
+    fused = run()
+    dev_set(19, 1)
+    try:
+        apart = run()
+        torch.cuda.synchronize()
+    finally:
+        dev_set(19, 0)
+    assert torch.equal(fused, apart)
+    assert bool(fused.float().abs().sum(-1).gt(0).all())  # every token got its expert's output
 
 
 @pytest.mark.dev

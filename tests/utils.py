@@ -1,5 +1,7 @@
 """Test helpers; `allclose` has the contract of reference tests/utils.py:176-189
 (dtype/device/shape asserts + torch.allclose in fp32, worst offenders printed on failure)."""
+import math
+
 import pytest
 import torch
 
@@ -98,3 +100,26 @@ def dev_set(key, value):
     elif value != 0:
         pytest.skip("pins a kernel variant through a development register: runs against the development build "
                     "(tests/test_dev_build.py)")
+
+
+# Rows per expert that put one group through every site of the 256 x 256 grouped GEMM's fused activation epilogue
+# (n = 2 * inter = 512, k = hidden = 512, 231 rows per group on average: csrc/group_gemm_route.h picks that kernel with the
+# epilogue; csrc/group_gemm_p8.hip, locate_item and the dispatch in gemm_fp8_p8_kernel, pick the body):
+#   265  one full tile that carries the 9 rows behind it as its ride-along block (9 <= 16 per full tile)
+#   40   the tail body, as the group's only tile
+#   100  the half-tile body (65 ... 128 rows)
+#   456  a full tile, then a 200-row last tile on the full body
+#   296  a full tile, then a 40-row tail body that is not the group's only tile (40 > 16: no ride-along)
+EPILOGUE_SITE_ROWS = [265, 40, 100, 456, 296]
+
+
+def topk1_ids_with_rows(rows):
+    """topk_ids [sum(rows), 1], constructed: expert e receives exactly rows[e] tokens, its tokens spread over the batch by
+    a fixed stride that is coprime with the token count."""
+    n = sum(rows)
+    stride = next(s for s in range(n // 3, n) if math.gcd(s, n) == 1)
+    ids = torch.repeat_interleave(torch.arange(len(rows), dtype=torch.int32), torch.tensor(rows))
+    out = torch.empty(n, dtype=torch.int32)
+    out[(torch.arange(n) * stride) % n] = ids
+    assert torch.bincount(out.long(), minlength=len(rows)).tolist() == list(rows)
+    return out.view(n, 1)

@@ -198,6 +198,11 @@ def test_hip_rope_vs_reference_golden(policy):
     assert allclose(bf(f"rope_q_p{policy}"), q.cpu(), atol=8e-2)
     assert allclose(bf(f"rope_k_p{policy}"), kc.cpu(), atol=8e-2)
     assert torch.equal(bf(f"rope_v_p{policy}"), vc.cpu())
+    # beside the reference's bar: one rounding of the float64 statement plus fp32 slack (tests/utils.py::rope_close)
+    from rope_cases import close_to_ref64
+
+    kc0, _, qkv0, cs0, ns0, qi0, ki0, qw0, kw0 = _rope_inputs()
+    assert close_to_ref64(q.cpu(), kc.cpu(), kc0, qkv0, cs0, ns0, qi0, ki0, qw0, kw0, policy)
 
 
 # ---------------------------------------------------------------------------- router GEMM

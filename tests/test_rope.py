@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import rope as orc
+from rope_cases import close_to_ref64
 from utils import allclose
 
 F8 = torch.float8_e4m3fn
@@ -108,6 +109,8 @@ def test_rope_norm_store_kv(hq, hkv, policy, num_req, is_prefill, mtp):
     assert allclose(ref_q, out_q[:rows].cpu(), atol=8e-2)
     assert allclose(kr, kc.cpu(), atol=8e-2)
     assert allclose(vr, vc.cpu(), atol=8e-2)
+    # beside the reference's bar: one rounding of the float64 statement plus fp32 slack (tests/utils.py::rope_close)
+    assert close_to_ref64(out_q.cpu(), kc.cpu(), inp[3], inp[0], inp[8], inp[1], inp[2], inp[5], inp[6], inp[7], policy)
     # V is a pure copy and untouched pages stay bit-identical
     assert torch.equal(vr.view(torch.int16), vc.cpu().view(torch.int16))
 
@@ -129,6 +132,7 @@ def test_rope_bypass_outputs():
     assert r.data_ptr() == oq.data_ptr()
     assert torch.equal(kc, k0) and torch.equal(vc, v0)
     assert allclose(ref_q, oq.cpu(), atol=8e-2)
+    assert close_to_ref64(oq.cpu(), None, inp[3], inp[0], inp[8], inp[1], inp[2], inp[5], inp[6], inp[7], 1, out_k=ok.cpu())
     assert torch.equal(ov.cpu().view(-1), qkv[:, 9 * 128 :].cpu().reshape(-1))
     # K rows: compare with what the oracle wrote into its cache at the token positions
     for req in range(5):

@@ -61,6 +61,75 @@ def attn_close(ref, real, tau, num_seq_q=1, floor=ATTN_FLOOR, label=""):
     return ok
 
 
+# fp32 slack of the rope + KV store bar (rope_excess / rope_close), as a fraction of the head's largest |value|.
+# Measured, not chosen: see rope_excess.
+ROPE_SLACK = 2.0 ** -20
+
+
+def _floor_log2(x, lowest):
+    """floor(log2 |x|) of a float64 tensor, exactly (frexp: |x| = m * 2^e with m in [0.5, 1)), not below `lowest`."""
+    a = x.double().abs()
+    e = torch.frexp(a)[1].long() - 1
+    return torch.where(a == 0, torch.full_like(e, lowest), e).clamp_min(lowest)
+
+
+def ulp_bf16(x):
+    """Spacing of bf16 at |x| (float64 tensor): 2^(floor(log2 |x|) - 7), the smallest normal's below it."""
+    return torch.exp2((_floor_log2(x, -126) - 7).double())
+
+
+def ulp_e4m3(x):
+    """Spacing of e4m3 at |x|: 2^(floor(log2 |x|) - 3), and the subnormal step 2^-9 below 2^-6."""
+    return torch.exp2((_floor_log2(x, -6) - 3).double())
+
+
+def rope_excess(ref64, got, mult=None):
+    """What a rope output misses the exact result by, beyond one rounding: per (row, head) of [rows, H, 128]
+        max_d (|got - t| - 0.5 ulp(t)) / max_d |t|
+    with t = ref64 and bf16's ulp for a bf16 output (mult None), and t = clamp(ref64 * mult, -448, 448) and e4m3's ulp for
+    an e4m3 output written as x * mult (mult: the fp32 multiplier the kernel uses, a scalar or [rows, H]).  NaN in `got`
+    counts as an infinite excess.  The kernel computes in fp32 and rounds once, so its excess is fp32 noise; the bar is
+    excess <= ROPE_SLACK.
+
+    Where ROPE_SLACK comes from: the fp32 oracle (oracle/rope.py rms_norm / rotary_neox in fp32, one rounding) against the
+    float64 statement (rope_norm_ref64) on 4096 rows x 16 heads, norm policies 0 / 1 / 2, inputs of scale 1 and 1e-3,
+    has a worst excess of about 1e-7 of the head maximum: 0.7e-7 ... 1.4e-7 for bf16 depending on the seed, up to 1.0e-7
+    for e4m3 with the dynamic scale's reciprocal, 1.4e-8 with a fixed multiplier of order 1 (tests/test_rope_bar.py
+    measures it again on its own inputs and prints it).  ROPE_SLACK = 2^-20 = 9.5e-7 is the 1.4e-7 with a margin of about
+    8 x (raised, it may reach 2^-18 at most: beyond that is a finding about the kernel), for what a correct
+    kernel may do differently: the order of the sum of squares, the hardware reciprocal square root, the reciprocal of
+    the scale, fused multiply-adds in the rotation."""
+    assert ref64.dtype == torch.float64 and ref64.shape == got.shape, (ref64.dtype, ref64.shape, got.shape)
+    if mult is None:
+        t, ulp = ref64, ulp_bf16(ref64)
+    else:
+        m = torch.as_tensor(mult, dtype=torch.float32).double()
+        t = (ref64 * (m.reshape(-1)[0] if m.numel() == 1 else m.unsqueeze(-1))).clamp(-448.0, 448.0)
+        ulp = ulp_e4m3(t)
+    over = ((got.float().double() - t).abs() - 0.5 * ulp).nan_to_num(nan=float("inf")).amax(-1)
+    return over / t.abs().amax(-1).clamp_min(1e-300)
+
+
+def rope_close(ref64, got, mult=None, slack=ROPE_SLACK, label=""):
+    """The rope bar: every (row, head) of `got` within half an ulp of the exact result plus `slack` x the head's largest
+    |value| (rope_excess).  Prints the worst excess in units of the slack; on failure the worst elements too: row, head,
+    element, value, reference."""
+    ex = rope_excess(ref64, got, mult)
+    worst = float(ex.max()) if ex.numel() else float("-inf")
+    ok = bool((ex <= slack).all())
+    print(f"rope_close {label}: worst excess {worst:.3g} of the head maximum = {worst / slack:.3g} x slack"
+          + ("" if ok else f"  FAILED: {int((ex > slack).sum())}/{ex.numel()} (row, head) over"))
+    if not ok:
+        m = None if mult is None else torch.as_tensor(mult, dtype=torch.float32).double()
+        for i in torch.topk(ex.reshape(-1), min(10, ex.numel())).indices.tolist():
+            r, h = (int(v) for v in torch.unravel_index(torch.tensor(i), ex.shape))
+            t = ref64[r, h] if m is None else (ref64[r, h] * (m.reshape(-1)[0] if m.numel() == 1 else m[r, h])).clamp(-448.0, 448.0)
+            d = int((got[r, h].float().double() - t).abs().nan_to_num(nan=float("inf")).argmax())
+            print(f"  row {r} head {h} element {d}: got {float(got[r, h, d]):.9g} ref {float(t[d]):.9g} "
+                  f"(excess {float(ex[r, h]):.3g}, head max {float(t.abs().max()):.4g})")
+    return ok
+
+
 def to_cpu(*ts):
     return [t.cpu() if t is not None else None for t in ts]
 

@@ -16,6 +16,7 @@
 // construction; the result layout is the reference's (csrc/sched_task_info.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/hpc_amd.h"
@@ -243,12 +244,21 @@ __global__ __launch_bounds__(kThreads) void assign_task_kernel(
 
 using namespace hpc::sched;
 
+namespace {
+// Records (kTaskStride ints = sizeof(TaskInfo) bytes each) of a plan of `grand_tiles` tiles on `bins` bins: the header, tiles per bin
+// + 1 records per bin (the terminator), the chunk table of `requests` = num_head_kv * num_batch ints (sched_task_info.h).
+int64_t plan_rows(int64_t grand_tiles, int64_t bins, int min_process_len, int64_t requests) {
+  const int64_t per = std::max<int64_t>((grand_tiles + bins - 1) / bins, min_process_len / kTileN);
+  return 1 + bins * (per + 1) + (requests + kTaskStride - 1) / kTaskStride;
+}
+}  // namespace
+
 extern "C" int hpc_attention_decode_num_bins(int num_seq_q, int device_id) {
   if (num_seq_q < 1 || num_seq_q > kMaxSeqQ) return HPC_ERR_INVALID;
   const int cus = hpc_get_cu_count(device_id);
   if (cus <= 0) return HPC_ERR_LAUNCH;
   const int dev_bins = hpc_dev_tuning_get(kDevSchedBins);  // development: bin count override (A/B of the bin size on small problems)
-  if (dev_bins > 0 && dev_bins <= 4 * cus) return dev_bins;
+  if (dev_bins > 0 && dev_bins <= kMaxCtaPerCu * cus) return dev_bins;
   return cus * cta_per_cu(num_seq_q);
 }
 
@@ -274,10 +284,24 @@ extern "C" int hpc_assign_attention_decode_task_rows(const int* num_seq_kvcache,
     const int n = num_seq_kvcache[b] + (new_kv_included ? 0 : num_seq_q);
     total += (n + kTileN - 1) / kTileN;
   }
-  const long grand = total * num_head_kv;
-  const int per = imax(static_cast<int>((grand + num_total_ctas - 1) / num_total_ctas),
-                       min_process_len / kTileN);
-  return 1 + num_total_ctas * (per + 1) + (num_head_kv * num_batch * 4 + 47) / 48;
+  return static_cast<int>(plan_rows(total * num_head_kv, num_total_ctas, min_process_len, static_cast<int64_t>(num_head_kv) * num_batch));
+}
+
+// Bytes of a task-map workspace that holds the plan of any batch of up to max_num_batch requests of up to max_seqlen KV tokens on
+// any bin count the library uses (1 ... kMaxCtaPerCu bins per CU; same sizes as the reference, hpc/attention.py:540-571): the
+// largest plan, then the finish flags and the tasks-per-bin counts at the largest bin count.  *sched_bytes (nullable): the plan's
+// part, what the allocator writes into header int 4.
+extern "C" int64_t hpc_attention_decode_task_workspace_bytes(int num_cu, int max_num_batch, int64_t max_seqlen, int num_head_kv,
+                                                             int min_process_len, int64_t* sched_bytes) {
+  if (num_cu <= 0 || max_num_batch < 0 || max_seqlen < 0 || num_head_kv <= 0) return HPC_ERR_INVALID;
+  const int64_t requests = static_cast<int64_t>(max_num_batch) * num_head_kv;
+  const int64_t grand = requests * ((max_seqlen + kTileN - 1) / kTileN);
+  int64_t rows = 0;
+  for (int per_cu = kMaxCtaPerCu; per_cu >= 1; --per_cu)
+    rows = std::max(rows, plan_rows(grand, static_cast<int64_t>(num_cu) * per_cu, min_process_len, requests));
+  const int64_t sched = rows * static_cast<int64_t>(sizeof(TaskInfo));
+  if (sched_bytes) *sched_bytes = sched;
+  return sched + 2 * static_cast<int64_t>(pad12(num_cu * kMaxCtaPerCu)) * static_cast<int64_t>(sizeof(int));
 }
 
 extern "C" int hpc_assign_attention_decode_task_sync(const int* num_seq_kvcache, int num_total_ctas,

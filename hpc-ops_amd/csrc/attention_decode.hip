@@ -740,28 +740,16 @@ int launch(Args a, const DecodeRoute& r, hipStream_t stream) {
 }  // namespace decode
 }  // namespace hpc
 
-namespace {
 using namespace hpc;
 
-int64_t v1_workspace_bytes(int num_bins, int num_batch, int num_head_kv, int num_seq_q, int heads_per_group) {
-  const int64_t rows = (static_cast<int64_t>(num_seq_q) * heads_per_group + 15) / 16 * 16;
-  const int64_t part_o = static_cast<int64_t>(num_bins) * 2 * rows * 128 * 4;
-  const int64_t part_lse = static_cast<int64_t>(num_bins) * 2 * rows * 4;
-  const int64_t first_bin = static_cast<int64_t>(num_batch) * num_head_kv * 4;
-  return part_o + part_lse + ((first_bin + 15) / 16) * 16;
-}
-}  // namespace
-
-// Scratch of one decode call: [arrival counters: hpc_attention_decode_workspace_zero_bytes() bytes that must be zero the first time
-// the buffer is used and are left zero by every call; shared by the two generations, one of which runs per call] [the first
-// generation's region: 2 partial slots per bin, first-bin table] [the second generation's partial slots: 2 per workgroup x 2 heads;
-// its grid never exceeds num_bins workgroups].
+// Scratch of one decode call: decode_ws_layout() (attention_decode_route.h) states where each piece sits.  Its first
+// hpc_attention_decode_workspace_zero_bytes() bytes (the arrival counters) must be zero the first time the buffer is used and are
+// left zero by every call.  Sized for a second-generation grid of num_bins workgroups, which no route exceeds.
 extern "C" int64_t hpc_attention_decode_workspace_bytes(int num_bins, int num_batch, int num_head_kv,
                                                         int num_seq_q, int heads_per_group) {
   if (num_bins <= 0 || num_batch <= 0 || num_head_kv <= 0 || num_seq_q <= 0 || heads_per_group <= 0)
     return HPC_ERR_INVALID;
-  return hpc::decode2::kCounterBytes + v1_workspace_bytes(num_bins, num_batch, num_head_kv, num_seq_q, heads_per_group) +
-         hpc::decode2::workspace_bytes(num_bins);
+  return decode_ws_layout(num_bins, num_batch, num_head_kv, num_seq_q, heads_per_group, num_bins).total;
 }
 extern "C" int64_t hpc_attention_decode_workspace_zero_bytes(void) { return hpc::decode2::kCounterBytes; }
 
@@ -818,6 +806,8 @@ struct Entry {
   hipStream_t stream;
   int eb() const { return fp8 ? 1 : 2; }  // bytes per element
   int g_shift() const { return __builtin_ctz(static_cast<unsigned>(num_head_q / num_head_kv)); }
+  // where the scratch of the call sits in `workspace` (num_wg: the second generation's grid)
+  DecodeWs ws_layout(int num_wg) const { return decode_ws_layout(num_bins, num_batch, num_head_kv, num_seq_q, num_head_q / num_head_kv, num_wg); }
 };
 constexpr float kScaleLog2 = 0.08838834764831845f * 1.4426950408889634f;  // 1/sqrt(128) * log2(e)
 
@@ -847,12 +837,12 @@ decode::Args fill_first(const Entry& e, const DecodeRoute& r) {
   a.block_ids = e.block_ids;
   a.task_map = e.task_map;
   a.y = static_cast<uint16_t*>(e.y);
-  // the workspace starts with the arrival counters of split requests (zero-once region)
-  a.arrive = r.combine_kernel ? nullptr : static_cast<int*>(e.workspace);
-  const int64_t rows = (e.num_seq_q * (e.num_head_q / e.num_head_kv) + 15) / 16 * 16;  // of the whole call, as v1_workspace_bytes()
-  a.part_o = reinterpret_cast<float*>(static_cast<char*>(e.workspace) + decode2::kCounterBytes);
-  a.part_lse = a.part_o + e.num_bins * 2 * rows * 128;
-  a.first_bin = reinterpret_cast<int*>(a.part_lse + e.num_bins * 2 * rows);
+  char* ws = static_cast<char*>(e.workspace);
+  const DecodeWs w = e.ws_layout(r.num_wg);
+  a.arrive = r.combine_kernel ? nullptr : reinterpret_cast<int*>(ws + w.counters);
+  a.part_o = reinterpret_cast<float*>(ws + w.part_o);
+  a.part_lse = reinterpret_cast<float*>(ws + w.part_lse);
+  a.first_bin = reinterpret_cast<int*>(ws + w.first_bin);
   a.qscale = e.qscale;
   a.kscale = static_cast<const float*>(e.kscale);
   a.vscale = e.vscale;
@@ -892,10 +882,10 @@ decode2::Args fill_second(const Entry& e, const DecodeRoute& r) {
   b.task_map = e.task_map;
   b.y = static_cast<uint16_t*>(e.y);
   char* ws = static_cast<char*>(e.workspace);
-  b.arrive = reinterpret_cast<int*>(ws);
-  b.part_o = reinterpret_cast<float*>(ws + decode2::kCounterBytes + v1_workspace_bytes(e.num_bins, e.num_batch, e.num_head_kv, e.num_seq_q,
-                                                                                      e.num_head_q / e.num_head_kv));
-  b.part_lse = b.part_o + static_cast<int64_t>(r.num_wg) * 2 * 2 * 16 * 128;
+  const DecodeWs w = e.ws_layout(r.num_wg);
+  b.arrive = reinterpret_cast<int*>(ws + w.counters);
+  b.part_o = reinterpret_cast<float*>(ws + w.part_o2);
+  b.part_lse = reinterpret_cast<float*>(ws + w.part_lse2);
   b.qscale = e.qscale;
   b.kscale = static_cast<const float*>(e.kscale);
   b.vscale = e.vscale;

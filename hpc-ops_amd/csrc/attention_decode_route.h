@@ -12,6 +12,34 @@ namespace decode2 {
 constexpr int64_t kCounterBytes = 64 * 1024;
 }  // namespace decode2
 
+// Where each piece of a decode call's scratch sits, in bytes from the start of the workspace: the one statement of it
+// (hpc_attention_decode_workspace_bytes sizes from it, the two generations' argument blocks are carved from it):
+//   [arrival counters: kCounterBytes, zero-once, shared by the two generations - one of which runs per call]
+//   [first generation: part_o [num_bins][2 slots][rows][128] f32, part_lse [num_bins][2][rows] f32 (rows = the call's q rows per kv
+//    head, padded to 16), first_bin [num_head_kv * num_batch] i32 (combine-kernel form only), padded to 16 bytes]
+//   [second generation: part_o [num_wg][2 slots][2 heads][16][128] f32, then part_lse [num_wg][2][2][16] f32 directly behind the
+//    num_wg slots in use]
+// num_wg is the second generation's grid.  Invariant: num_wg <= num_bins - decode_route() never routes a grid above the bin count
+// the workspace was sized with -, so a call's total never exceeds the size at num_wg = num_bins, which is what the sizer returns.
+struct DecodeWs {
+  int64_t counters, part_o, part_lse, first_bin;  // first generation (counters: either)
+  int64_t part_o2, part_lse2;                     // second generation
+  int64_t total;
+};
+static inline DecodeWs decode_ws_layout(int num_bins, int num_batch, int num_head_kv, int num_seq_q, int group, int num_wg) {
+  const int64_t rows = (static_cast<int64_t>(num_seq_q) * group + 15) / 16 * 16;
+  const int64_t first_bin_bytes = static_cast<int64_t>(num_batch) * num_head_kv * 4;
+  DecodeWs w{};
+  w.counters = 0;
+  w.part_o = decode2::kCounterBytes;
+  w.part_lse = w.part_o + static_cast<int64_t>(num_bins) * 2 * rows * 128 * 4;
+  w.first_bin = w.part_lse + static_cast<int64_t>(num_bins) * 2 * rows * 4;
+  w.part_o2 = w.first_bin + (first_bin_bytes + 15) / 16 * 16;
+  w.part_lse2 = w.part_o2 + static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 128 * 4;
+  w.total = w.part_lse2 + static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 4;
+  return w;
+}
+
 struct DecodeCall {  // what the call is; strides in BYTES
   bool bf16;         // else fp8 e4m3
   int quant_type;    // fp8: 1 = q per token and head, K / V per tensor; 0 = K per token (page tail rows), V per head

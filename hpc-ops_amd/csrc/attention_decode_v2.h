@@ -18,7 +18,7 @@ struct Args {
   const int* lens;       // num_seq_kvcache [B]
   const int* task_map;   // the scheduler's task map: only header int 6 (min_process_len) is read - the plan is in-kernel
   uint16_t* y;
-  float* part_o;         // [workgroups][2][2 heads][16][128]
+  float* part_o;         // [workgroups][2][2 heads][16][128]   (both: DecodeWs::part_o2 / part_lse2, attention_decode_route.h)
   float* part_lse;       // [workgroups][2][2 heads][16]
   int* arrive;           // [pairs * B] arrival counters of split requests (zero before the call, left zero)
   const float* qscale;   // [B * Sq, qscale_stride]
@@ -54,7 +54,6 @@ struct Args {
   void* prof;  // development: per-wave timing sums [workgroups][4][12] uint64 (null = off)
 };
 
-int64_t workspace_bytes(int num_wg);  // partial slots (2 per workgroup x 2 heads), after the first-generation region
 // Launches the form that `r` (generation 2) names on r.num_wg workgroups.  `a`: filled by the entry but for the members that follow
 // from the grid (pair_xor ... dev_slice); a.arrive is the workspace's counter region, left zero also when the launch fails.
 int launch(Args a, const DecodeRoute& r, hipStream_t stream);

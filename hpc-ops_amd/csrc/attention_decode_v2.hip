@@ -1489,15 +1489,6 @@ __global__ __launch_bounds__(kThreads, 2) void decode2_kernel(const Args a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Scratch layout of this kernel inside the call's workspace: the arrival counters sit in the first kCounterBytes of
-// the WHOLE workspace (fixed place and size whatever the shapes of the call, so a call with other shapes can never
-// land them on stale partials); partial slots follow the first-generation kernel's region.
-int64_t workspace_bytes(int num_wg) {
-  const int64_t part_o = static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 128 * 4;
-  const int64_t part_lse = static_cast<int64_t>(num_wg) * 2 * 2 * 16 * 4;
-  return part_o + part_lse;
-}
-
 #ifdef HPC_DEV
 int ticket_overruns(bool reset) {
   int v = 0;

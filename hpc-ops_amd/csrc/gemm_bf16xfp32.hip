@@ -20,6 +20,7 @@
 #include "hpc_common.h"
 #include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
+#include "gemm_bf16xfp32_route.h"
 
 namespace hpc {
 namespace rgemm {
@@ -499,39 +500,26 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16xfp32_skinny_kernel(const A
   if (t < a.m) emit(tot);
 }
 
-constexpr int kSkinnyMaxM = 256;
-inline int skinny_tm(int m) { return m <= 16 ? 16 : (m <= 32 ? 32 : 64); }
-
 }  // namespace rgemm
 }  // namespace hpc
 
-// Split count the launcher will use for (m, n, k): callers size split_y = splits * m * n floats and
-// (m <= 256) provide ceil(m / tm) * n / 16 zeroed counters, (m > 256) a [ceil(m/64)+, n/64+] counter grid (the tile kernel
-// counts on its first ceil(m / 128) rows).
-extern "C" int hpc_gemm_bf16xfp32_splits(int m, int n, int k, int use_splitk) {
-  using namespace hpc::rgemm;
-  if (m <= 0 || n <= 0 || k <= 0) return 1;
-  if (!use_splitk) return 1;
-  int s = 1;
+namespace {
+int current_cu_count() {
   int dev = 0;
-  const int cus = hipGetDevice(&dev) == hipSuccess && hpc_get_cu_count(dev) > 0 ? hpc_get_cu_count(dev) : 256;
-  if (m <= kSkinnyMaxM) {
-    const int tm = skinny_tm(m);
-    const long tiles = static_cast<long>((m + tm - 1) / tm) * (n / 16);
-    // ~one workgroup per CU; every wave keeps at least one 64-k step
-    while (s < 16 && tiles * s < cus && (k >> 6) / (s * 2) >= 4) s *= 2;
-    return s;
-  }
-  // m > 256: the tile kernel, 64 weight rows x 128 tokens.  Splits until there is ONE workgroup per CU, at most 8 (every split
-  // costs the hand-off of its fp32 partials: m = 4096 x n = 256 35.7 us with 4 splits = two workgroups per CU, 28.7 us with 2;
-  // m = 1024 29.2 us with 16 splits, 19.9 with 8 - profiles/round5_router_tile_ab.txt); a launch that has between one and two
-  // workgroups per CU without splitting is split once more (two resident workgroups per CU overlap each other's load phases).
-  const long tiles = static_cast<long>((m + 127) / 128) * (n / 64);
-  // development key kDevRouterGemmSplitCap: cap on the split count above m = 256 (never above the 16 planes the reduce sums)
-  const int cap = hpc_dev_tuning_get(kDevRouterGemmSplitCap) > 0 ? (hpc_dev_tuning_get(kDevRouterGemmSplitCap) < 16 ? hpc_dev_tuning_get(kDevRouterGemmSplitCap) : 16) : 8;
-  while (s < cap && tiles * s < cus && k / (s * 2) >= 256) s *= 2;
-  if (tiles >= cus && tiles < 2 * cus && s == 1 && k >= 512) s = 2;
-  return s;
+  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
+}
+}  // namespace
+
+// Split count the library picks for (m, n, k), and what the caller of hpc_gemm_bf16xfp32_async provides with it: rgemm_route()
+// (gemm_bf16xfp32_route.h).  split_y = splits * m * n floats; flag_rows x flag_ld zeroed int32 counters.
+extern "C" int hpc_gemm_bf16xfp32_splits(int m, int n, int k, int use_splitk) {
+  return hpc::rgemm_route(m, n, k, use_splitk, current_cu_count()).splits;
+}
+extern "C" int hpc_gemm_bf16xfp32_plan(int m, int n, int k, int use_splitk, int* splits, int* flag_rows, int* flag_ld) {
+  if (!splits || !flag_rows || !flag_ld) return HPC_ERR_INVALID;
+  const hpc::RgemmRoute r = hpc::rgemm_route(m, n, k, use_splitk, current_cu_count());
+  *splits = r.splits, *flag_rows = r.flag_rows, *flag_ld = r.flag_ld;
+  return r.code;
 }
 
 // reference: gemm_bf16xfp32_async (src/gemm/gemm.h:13-17, src/gemm/sm90/gemm_bf16xfp32.cu:488-557)
@@ -543,13 +531,13 @@ extern "C" int hpc_gemm_bf16xfp32_async(void* y_ptr, void* splitk_y_ptr, void* s
   if (!y_ptr || !x_ptr || !w_high_ptr || !w_low_ptr) return HPC_ERR_INVALID;
   if (m < 0 || n <= 0 || k <= 0 || splits < 1) return HPC_ERR_INVALID;
   if (m == 0) return HPC_OK;
-  if ((n & 63) || (k & 63)) return HPC_ERR_UNSUPPORTED;
-  if (static_cast<int64_t>(m) * k * 2 > 0xfffffff0ll || static_cast<int64_t>(n) * k * 2 > 0xfffffff0ll)
-    return HPC_ERR_UNSUPPORTED;  // 32-bit buffer offsets
+  // kernel and grid from the route; the split count is the caller's (any count up to the route's bound: grid_z)
+  const hpc::RgemmRoute r = hpc::rgemm_route(m, n, k, 0, 0);
+  if (r.code != HPC_OK) return r.code;
   if (splits > 1 && (!splitk_y_ptr || !split_flag_ptr)) return HPC_ERR_INVALID;
-  if (splits > (k >> 6)) return HPC_ERR_INVALID;
-  if (splits > 16) return HPC_ERR_INVALID;  // the last arriver of every kernel form sums at most 16 partial planes
+  if (splits > r.max_splits) return HPC_ERR_INVALID;
   if (splits > 1 && static_cast<int64_t>(splits) * m * n * 4 > 0xfffffff0ll) return HPC_ERR_UNSUPPORTED;
+  if (splits > 1 && flag_ld < r.flag_ld) return HPC_ERR_INVALID;
   Args a;
   a.x = static_cast<const uint16_t*>(x_ptr);
   a.wh = static_cast<const uint16_t*>(w_high_ptr);
@@ -565,34 +553,27 @@ extern "C" int hpc_gemm_bf16xfp32_async(void* y_ptr, void* splitk_y_ptr, void* s
   a.fp32_out = use_fp32_output;
   a.scale = scale;
   a.dev_skip = hpc_dev_tuning_get(kDevRouterGemmSkipLoads);
-  if (m <= kSkinnyMaxM) {
-    const int tm = skinny_tm(m);
-    dim3 grid(n / 16, (m + tm - 1) / tm, splits);
-    if (splits > 1 && flag_ld < n / 16) return HPC_ERR_INVALID;
-    if (tm == 16)
+  const dim3 grid(r.grid_x, r.grid_y, splits);
+  if (r.kernel == hpc::kRgemmSkinny) {
+    if (r.tm == 16)
       gemm_bf16xfp32_skinny_kernel<1><<<grid, kThreads, 0, stream>>>(a);
-    else if (tm == 32)
+    else if (r.tm == 32)
       gemm_bf16xfp32_skinny_kernel<2><<<grid, kThreads, 0, stream>>>(a);
     else
       gemm_bf16xfp32_skinny_kernel<4><<<grid, kThreads, 0, stream>>>(a);
     HPC_CHECK_LAUNCH();
     return HPC_OK;
   }
-  if (splits > 1 && flag_ld < n / 64) return HPC_ERR_INVALID;
   // Measured (profiles/round5_router_tile_ab.txt; n = 256, k = 4096 unless said, old -> new): m = 4096 94.7 -> 29.0 us, m = 1024
   // 32.5 -> 20.1, m = 304 23.6 -> 18.2, m = 8192 x k = 7168 304 -> 77.5 us (0.78 PFLOP/s), m = 16384 x n = 128 180 -> 51.5 us.  What is
   // left (timing-only variants, development key kDevRouterGemmSkipLoads): the loop with no loads at all takes 62 of the 77.5 us (eight 16-byte LDS
   // stores + sixteen operand reads per wave for 32 MFMAs, one barrier per step), and below m ~ 1024 the call is its fixed
   // cost (launch, eight steps, split hand-off: 18-19 us).
-  if (hpc_dev_tuning_get(kDevRouterGemm64) == 1) {  // development key kDevRouterGemm64 = 1: the 64 x 64 kernel of rounds 1-4 (operands straight from memory)
-    dim3 grid(n / 64, (m + 63) / 64, splits);
-    if (grid.y > 65535) return HPC_ERR_UNSUPPORTED;
+  if (r.kernel == hpc::kRgemmTile64) {  // development: the 64 x 64 kernel of rounds 1-4 (operands straight from memory)
     gemm_bf16xfp32_kernel<4><<<grid, kThreads, 0, stream>>>(a);
     HPC_CHECK_LAUNCH();
     return HPC_OK;
   }
-  dim3 grid(n / 64, (m + 127) / 128, splits);
-  if (grid.y > 65535) return HPC_ERR_UNSUPPORTED;
   gemm_bf16xfp32_tile_kernel<<<grid, kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   return HPC_OK;

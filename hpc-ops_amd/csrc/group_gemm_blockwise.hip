@@ -614,6 +614,9 @@ extern "C" int hpc_group_gemm_pertensor_fp8_async(void* y_ptr, const void* x_ptr
                                           row_index_ptr, num_group, m, x_rows, n, k, cu_tiles128_ptr, stream, nullptr);
 }
 
+// For the torch ops of the stand-alone grouped GEMMs: is the scan of ceil(seqlens / 128) worth computing for this call (1 / 0)?
+extern "C" int hpc_group_gemm_scan_wanted(int num_group, int m) { return hpc::ggemm_scan_wanted(num_group, m) ? 1 : 0; }
+
 #ifdef HPC_DEV
 // development (tests/test_ggemm_route.py): ggemm_route() on flat arrays, the members of GgemmCall and GgemmRoute in their order
 extern "C" int hpc_dev_ggemm_route(const int64_t* call, int n_in, int* route, int n_out) {

@@ -37,6 +37,13 @@ struct GgemmRoute {  // what runs
 //  * else n % 128 == 0 and avg > 20: a tiled kernel.  The ring kernel's condition (n % 256 == 0, k >= 128) is the 256 x 256 kernel's,
 //    which is asked first: with all keys 0 the ring kernel never runs, the 128 x 128 kernel takes these calls;
 //  * else the streaming kernel, its tokens per pass from avg.
+constexpr int kGgemmTiledAboveAvg = 20;  // rows per group above which the tiled branch below is asked
+
+// Whether a caller that does not have the scan of ceil(seqlens / 128) anyway (the torch ops of the stand-alone grouped GEMMs) should
+// compute it for a call: above kGgemmTiledAboveAvg rows per group.  Below, the call streams - also at 16 ... 20 rows per group, where
+// a call WITH the scan (the fused MoE always has it) takes the 256 x 256 kernel.
+static inline bool ggemm_scan_wanted(int num_group, int m) { return m / (num_group > 1 ? num_group : 1) > kGgemmTiledAboveAvg; }
+
 // (static: the product and the development library may sit in one process, and each must call its own)
 static inline GgemmRoute ggemm_route(const GgemmCall& c) {
   GgemmRoute r{};
@@ -98,7 +105,7 @@ static inline GgemmRoute ggemm_route(const GgemmCall& c) {
   // 128 tokens, 100 KB in flight per CU without staging registers; measured on E64 / top-8: T = 128 (16 per group) 1.61 vs
   // 1.50 ms for the streaming form, T = 192 1.63 vs 1.79, T = 256 1.73 vs 1.85, T = 384 1.75 ms), else the 128 x 128
   // register-staged one
-  if (c.has_scan && c.n % 128 == 0 && tiled_mode != 1 && (tiled_mode >= 2 || avg > 20)) {
+  if (c.has_scan && c.n % 128 == 0 && tiled_mode != 1 && (tiled_mode >= 2 || avg > kGgemmTiledAboveAvg)) {
     const long max_tiles = c.m / 128 + c.num_group;  // upper bound of sum_g ceil(len_g / 128)
     if (c.n % 256 || c.k < 128 || tiled_mode == 3) {
       r.kernel = 2;

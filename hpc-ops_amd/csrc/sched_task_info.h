@@ -26,6 +26,9 @@ namespace sched {
 constexpr int kTaskStride = 12;  // ints per record
 constexpr int kTileN = 64;       // KV tokens per scheduling tile (reference sm90 value)
 constexpr int kMaxSeqQ = 5;
+// No launch has more bins than this per CU: the task-map workspace (hpc_attention_decode_task_workspace_bytes) is sized for it and
+// hpc_attention_decode_num_bins never returns more (the reference's kMaxCtaPerSm, hpc/attention.py:540-571).
+constexpr int kMaxCtaPerCu = 4;
 
 // workgroups ("bins") per CU by num_seq_q (1..5): 256-thread workgroups, <=256 VGPRs each.
 __host__ __device__ inline int cta_per_cu(int num_seq_q) {

@@ -58,24 +58,6 @@ DecodeCommon decode_common_checks(const at::Tensor& q, const at::Tensor& kcache,
   return c;
 }
 
-// byte size + scheduler byte size of the task-map workspace (reference hpc/attention.py:540-571)
-std::pair<int64_t, int64_t> task_workspace_bytes(int num_cu, int64_t max_num_batch, int64_t max_seqlen, int64_t num_head_kv,
-                                                 int64_t min_process_len) {
-  const int64_t k_task = 48, k_max_cta = 4, k_tile = 64;
-  const int64_t max_cta = num_cu * k_max_cta;
-  const int64_t total_tiles = max_num_batch * num_head_kv * ((max_seqlen + k_tile - 1) / k_tile);
-  int64_t max_tasks = 0;
-  for (int cta_per_cu = 4; cta_per_cu >= 1; --cta_per_cu) {
-    const int64_t ctas = static_cast<int64_t>(num_cu) * cta_per_cu;
-    const int64_t per = std::max((total_tiles + ctas - 1) / ctas, min_process_len / k_tile);
-    max_tasks = std::max(max_tasks, (per + 1) * ctas + 1);
-  }
-  const int64_t chunk_bytes = (max_num_batch * num_head_kv * 4 + k_task - 1) / k_task * k_task;
-  const int64_t cta_pad = (max_cta + 11) / 12 * 12 * 4;
-  const int64_t sched = max_tasks * k_task + chunk_bytes;
-  return {sched + 2 * cta_pad, sched};
-}
-
 int num_bins_of(int num_seq_q, const at::Tensor& on) {
   const int n = hpc_attention_decode_num_bins(num_seq_q, on.is_cuda() ? on.device().index() : -1);
   TORCH_CHECK(n > 0, "we only support num_seq_q 1..5 (and a HIP device must be present)");
@@ -130,12 +112,15 @@ at::Tensor schedule_on_the_fly(const at::Tensor& num_seq_kvcache, const at::Tens
   const int num_cu = hpc_get_cu_count(num_seq_kvcache.device().index());
   TORCH_CHECK(num_cu > 0, "hpc_get_cu_count failed (no HIP device?)");
   const int64_t max_seq = block_ids.size(1) * block_size + num_seq_q;
-  const auto sz = task_workspace_bytes(num_cu, num_seq_kvcache.size(0), max_seq, num_head_kv, 512);
-  at::Tensor ws = at::zeros({sz.first}, num_seq_kvcache.options().dtype(at::kChar));
+  int64_t sched_bytes = 0;
+  const int64_t ws_bytes = hpc_attention_decode_task_workspace_bytes(num_cu, static_cast<int>(num_seq_kvcache.size(0)), max_seq,
+                                                                     static_cast<int>(num_head_kv), 512, &sched_bytes);
+  TORCH_CHECK(ws_bytes > 0, "attention_decode: invalid arguments");
+  at::Tensor ws = at::zeros({ws_bytes}, num_seq_kvcache.options().dtype(at::kChar));
   at::Tensor hdr = ws.view(at::kInt);  // header ints 2..4 (device-side fills: capturable in a hipGraph)
   hdr.narrow(0, 2, 1).fill_(num_head_kv);
   hdr.narrow(0, 3, 1).fill_(num_seq_kvcache.size(0));
-  hdr.narrow(0, 4, 1).fill_(sz.second);
+  hdr.narrow(0, 4, 1).fill_(sched_bytes);
   return assign_task_cuda(num_seq_kvcache, num_head_kv, num_seq_q, new_kv_included, 512, ws);
 }
 

@@ -29,19 +29,14 @@ at::Tensor gemm_bf16xfp32(const at::Tensor& x, const at::Tensor& w_high, const a
   const int64_t m = x.size(0), k = x.size(1), n = w_high.size(0);
   TORCH_CHECK(n % 64 == 0, "n must to be divided by 64.");
   TORCH_CHECK(w_high.size(1) == k && w_low.sizes() == w_high.sizes(), "weight planes must be [n, k]");
-  const int splits = hpc_gemm_bf16xfp32_splits(i32(m), i32(n), i32(k), use_splitk ? 1 : 0);
+  // split count and the counters that go with it: [rows, flag_ld] int32, flat for m <= 256 and a 2-D grid above (csrc/gemm_bf16xfp32_route.h)
+  int splits = 1, rows = 0, min_ld = 0;
+  HPC_LAUNCH_CHECK(hpc_gemm_bf16xfp32_plan(i32(m), i32(n), i32(k), use_splitk ? 1 : 0, &splits, &rows, &min_ld), "gemm_bf16xfp32");
   at::Tensor split_y, flag;
   int64_t flag_ld = 0;
   if (splits > 1) {
+    flag_ld = min_ld;
     split_y = at::empty({splits, m, n}, x.options().dtype(at::kFloat));
-    // counters: m <= 256 runs on 16-row tiles (flat [m_tiles, n / 16]), larger m on a [ceil(m / 64), n / 64] grid
-    int64_t rows;
-    if (m <= 256) {
-      const int64_t tm = m <= 16 ? 16 : (m <= 32 ? 32 : 64);
-      rows = (m + tm - 1) / tm, flag_ld = n / 16;
-    } else {
-      rows = (m + 63) / 64, flag_ld = n / 64;
-    }
     if (split_flag.has_value()) {
       TORCH_CHECK(split_flag->scalar_type() == at::kInt && split_flag->is_contiguous(), "split_flag must be a contiguous int32 tensor");
       if (m > 256) {
@@ -49,13 +44,13 @@ at::Tensor gemm_bf16xfp32(const at::Tensor& x, const at::Tensor& w_high, const a
                     "split_flag is too small for this problem");
         flag_ld = split_flag->size(1);
       } else {
-        TORCH_CHECK(split_flag->numel() >= rows * flag_ld, "split_flag is too small for this problem");
+        TORCH_CHECK(split_flag->numel() >= int64_t{rows} * flag_ld, "split_flag is too small for this problem");
       }
       flag = *split_flag;
     } else {
       // the tickets are zero again when the kernel exits (the last arriver of a tile resets its counter): a zero-once
       // buffer per (device, stream, capture) instead of an allocation + a zero-fill launch per call
-      flag = cached_scratch(kScratchGemmFlags, x, std::max<int64_t>(rows * flag_ld * 4, 1 << 16), 1 << 30).view(at::kInt);
+      flag = cached_scratch(kScratchGemmFlags, x, std::max<int64_t>(int64_t{rows} * flag_ld * 4, 1 << 16), 1 << 30).view(at::kInt);
     }
   }
   at::Tensor y = at::empty({m, n}, x.options().dtype(use_fp32_output ? at::kFloat : at::kBFloat16));

@@ -23,10 +23,10 @@ int aligned_size(int64_t avg) {
   return 64;
 }
 
-// Scan of ceil(seqlens / 128) for the tiled (large-group) GEMM kernels; an undefined tensor keeps the streaming one.
-// The caller holds the tensor until its GEMM launch has been enqueued.
+// Scan of ceil(seqlens / 128) for the tiled (large-group) GEMM kernels, where the library wants it (csrc/group_gemm_route.h); an
+// undefined tensor keeps the streaming one.  The caller holds the tensor until its GEMM launch has been enqueued.
 at::Tensor cu_tiles128(const at::Tensor& seqlens, int64_t m, int64_t num_group, hpc_stream_t stream) {
-  if (m / std::max<int64_t>(num_group, 1) <= 20) return at::Tensor();
+  if (!hpc_group_gemm_scan_wanted(i32(num_group), i32(m))) return at::Tensor();
   at::Tensor tiles = at::empty({num_group}, seqlens.options().dtype(at::kInt));
   at::Tensor cu = at::empty({num_group + 1}, seqlens.options().dtype(at::kInt));
   HPC_LAUNCH_CHECK(hpc_moe_tiles_async(ptr(seqlens), i32(num_group), 128, ptr(tiles), ptr(cu), stream), "group_gemm tiles");

@@ -53,6 +53,7 @@ _sig("hpc_attention_decode_num_bins", I, I, I)
 _sig("hpc_attention_decode_effective_bins", I, P, I, I, I, I, I)
 _sig("hpc_attention_decode_tile_n", I)
 _sig("hpc_assign_attention_decode_task_rows", I, IP, I, I, I, I, I, I)
+_sig("hpc_attention_decode_task_workspace_bytes", L, I, I, L, I, I, ctypes.POINTER(c_int64))
 _sig("hpc_assign_attention_decode_task_sync", I, IP, I, I, I, I, I, I, IP, I)
 _sig("hpc_assign_attention_decode_task_async", I, IP, IP, I, I, I, I, I, I, P)
 _sig("hpc_attention_decode_workspace_bytes", L, I, I, I, I, I)
@@ -64,6 +65,7 @@ _sig("hpc_attention_decode_fp8_async", I, P, P, IP, P, P, P, IP, IP, P, P, P, I,
      I, I, I, L, L, L, L, L, L, L, L, L, P)
 
 _sig("hpc_group_gemm_blockwise_fp8_async", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, L, L, P, P)
+_sig("hpc_group_gemm_scan_wanted", I, I, I)
 _sig("hpc_moe_count_and_slot_async", I, P, I, I, I, I, I, P, P, P, P, P, P, P)
 _sig("hpc_moe_tiles_async", I, P, I, I, P, P, P)
 _sig("hpc_moe_gather_blockwise_async", I, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P)
@@ -81,6 +83,7 @@ _sig("hpc_rope_norm_store_kv_async", I, P, P, P, P, P, P, P, P, P, P, P, P, L, L
 _sig("hpc_rope_norm_store_kv_fp8_async", I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, F, I, L, L,
      I, I, I, I, I, I, I, I, I, I, I, P)
 _sig("hpc_gemm_bf16xfp32_splits", I, I, I, I, I)
+_sig("hpc_gemm_bf16xfp32_plan", I, I, I, I, I, IP, IP, IP)
 _sig("hpc_gemm_bf16xfp32_async", I, P, P, P, P, P, P, I, I, I, F, I, I, I, P)
 _sig("hpc_topk_router_async", I, IP, P, P, I, I, L, I, I, P)
 _sig("hpc_attention_with_kvcache_prefill_fp8_async", I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I,

@@ -4,6 +4,7 @@ Same function names, argument names/defaults and semantics; the kernels behind t
 the gfx950 ones of libhpc_amd.so.  Prefill / block-sparse entry points of the reference are out of
 scope of this hot path and intentionally absent.
 """
+import ctypes
 from enum import Enum
 
 import torch
@@ -115,20 +116,13 @@ def get_attention_decode_task_workspace(
 
 
 def task_workspace_bytes(num_cu, max_num_batch, max_seqlen, num_head_kv, min_process_len):
-    """Byte size + scheduler byte size of the task-map workspace; same arithmetic as reference
-    hpc/attention.py:540-571 (sized for up to 4 bins per CU, so any gfx950 bin count fits)."""
-    k_task, k_max_cta, k_tile = 48, 4, 64
-    max_cta = num_cu * k_max_cta
-    total_tiles = max_num_batch * num_head_kv * ((max_seqlen + k_tile - 1) // k_tile)
-    max_tasks = 0
-    for cta_per_cu in (4, 3, 2, 1):
-        ctas = num_cu * cta_per_cu
-        per = max((total_tiles + ctas - 1) // ctas, min_process_len // k_tile)
-        max_tasks = max(max_tasks, (per + 1) * ctas + 1)
-    chunk_bytes = (max_num_batch * num_head_kv * 4 + k_task - 1) // k_task * k_task
-    cta_pad = (max_cta + 11) // 12 * 12 * 4
-    sched = max_tasks * k_task + chunk_bytes
-    return sched + 2 * cta_pad, sched
+    """Byte size + scheduler byte size of the task-map workspace (hpc_attention_decode_task_workspace_bytes: the sizes of
+    reference hpc/attention.py:540-571, for up to 4 bins per CU, so any gfx950 bin count fits)."""
+    sched = ctypes.c_int64(0)
+    total = _C.lib.hpc_attention_decode_task_workspace_bytes(num_cu, max_num_batch, max_seqlen, num_head_kv, min_process_len,
+                                                             ctypes.byref(sched))
+    _C.require(total > 0, "task_workspace_bytes: invalid arguments")
+    return total, sched.value
 
 
 def release_decode_workspaces():

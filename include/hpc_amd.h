@@ -63,7 +63,10 @@ int hpc_fused_rmsnorm_with_scale_async(const void* input, const void* weight, vo
  *   batch with little work is planned on fewer bins (hpc_attention_decode_effective_bins: at least 8 tiles per bin,
  *   at least 64 bins) and header int 1 of the map records the count used - consumers read it from there.  Byte-
  *   identical to the host scheduler run with that count.
- * hpc_attention_decode_effective_bins: that count from host lengths (what the CPU entry of the op passes to _sync). */
+ * hpc_attention_decode_effective_bins: that count from host lengths (what the CPU entry of the op passes to _sync).
+ * hpc_attention_decode_task_workspace_bytes: bytes of a task-map workspace for up to max_num_batch requests of up to
+ *   max_seqlen KV tokens on a device of num_cu CUs, whatever bin count (up to 4 per CU) a call plans on - the reference's
+ *   sizes (hpc/attention.py:540-571).  *sched_bytes (nullable): the part the allocator records in header int 4.  < 0: error. */
 int hpc_attention_decode_num_bins(int num_seq_q, int device_id);
 int hpc_attention_decode_effective_bins(const int* num_seq_kvcache, int num_batch, int num_head_kv, int num_seq_q,
                                         int new_kv_included, int max_bins);
@@ -71,6 +74,8 @@ int hpc_attention_decode_tile_n(void);
 int hpc_assign_attention_decode_task_rows(const int* num_seq_kvcache, int num_total_ctas,
                                           int num_batch, int num_head_kv, int num_seq_q,
                                           int new_kv_included, int min_process_len);
+int64_t hpc_attention_decode_task_workspace_bytes(int num_cu, int max_num_batch, int64_t max_seqlen, int num_head_kv,
+                                                  int min_process_len, int64_t* sched_bytes);
 int hpc_assign_attention_decode_task_sync(const int* num_seq_kvcache, int num_total_ctas,
                                           int num_batch, int num_head_kv, int num_seq_q,
                                           int new_kv_included, int min_process_len, int* task_map,
@@ -200,6 +205,9 @@ int hpc_group_gemm_blockwise_fp8_async(void* y_ptr, const void* x_ptr, const voi
                                        int tile_m, int64_t xscale_row_stride,
                                        int64_t xscale_kb_stride, const void* cu_tiles128_ptr,
                                        hpc_stream_t stream);
+/* 1 when a caller of the grouped GEMMs (either scale kind) that does not have cu_tiles128 should compute it for a call of m
+ * rows in num_group groups - groups long enough for a tiled kernel -, 0 when the call streams either way. */
+int hpc_group_gemm_scan_wanted(int num_group, int m);
 
 /* ---- fused MoE pieces ---------------------------------------------------------------------------
  * reference: src/fuse_moe/fuse_moe.h:15-62 (count_and_gather_async / blockwise_count_and_gather_async,
@@ -312,12 +320,13 @@ int hpc_rope_norm_store_kv_fp8_async(void* out_q, void* kcache, void* vcache, vo
 /* ---- router GEMM: y = x (w_high + scale * w_low)^T, bf16 operands, fp32 accumulate ----
  * reference: gemm_bf16xfp32_async, src/gemm/gemm.h:13-17 (kernel src/gemm/sm90/gemm_bf16xfp32.cu:88-410,
  * config src/gemm/sm90/entry.cc:23-84).  x [m,k] bf16, w_high / w_low [n,k] bf16, y [m,n] bf16 or fp32.
- * n % 64 == 0, k % 64 == 0.  splits = hpc_gemm_bf16xfp32_splits(m, n, k, use_splitk); when > 1 the
- * caller provides splitk_y (splits*m*n fp32) and zeroed int32 arrival counters split_flag: for
- * m <= 256 a flat [ceil(m/tm), flag_ld = n/16] array (tm = 16 / 32 / 64 for m <= 16 / 32 / 256), for
- * larger m a [ceil(m/64), flag_ld >= n/64] grid (the tile kernel counts on its first ceil(m/128) rows); the counters are zero
- * again when the call retires. */
+ * n % 64 == 0, k % 64 == 0.  hpc_gemm_bf16xfp32_plan(m, n, k, use_splitk, ...) gives the split count the library picks
+ * (hpc_gemm_bf16xfp32_splits returns the same number) and the arrival counters that go with it; when splits > 1 the
+ * caller provides splitk_y (splits*m*n fp32) and split_flag: zeroed int32 [*flag_rows, flag_ld >= *flag_ld] (*flag_ld:
+ * the smallest row stride); the counters are zero again when the call retires.  The plan returns the code the launch
+ * would refuse the shape with (0: none), its outputs are set either way. */
 int hpc_gemm_bf16xfp32_splits(int m, int n, int k, int use_splitk);
+int hpc_gemm_bf16xfp32_plan(int m, int n, int k, int use_splitk, int* splits, int* flag_rows, int* flag_ld);
 int hpc_gemm_bf16xfp32_async(void* y, void* splitk_y, void* split_flag, const void* x, const void* w_high,
                              const void* w_low, int m, int n, int k, float scale, int use_fp32_output,
                              int splits, int flag_ld, hpc_stream_t stream);

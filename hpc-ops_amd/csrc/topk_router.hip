@@ -17,6 +17,13 @@
 // (order-preserving key << 32 | ~expert id) followed by a wave-wide max through 6 shuffle steps; the
 // winner is struck out in its owner lane.  k rounds give the top-k in rank order; the row maximum is
 // round 0's winner, the softmax denominator one more shuffle reduction.
+//
+// The second kernel here, grouped_topk_router_kernel, is the group-limited router of DeepSeek-V3 / R1, Kimi-K2 and
+// DeepSeek-V2 (tests/grouped_router_ref.py states it in PyTorch): scores s = sigmoid or softmax of the logits, choice
+// scores c = s + correction bias, the experts in contiguous groups of which the `topk_group` best stay (group score =
+// sum of the group's two best c with a bias, its best c without), top-k on c among the experts that stay, weights
+// from the UNBIASED s, renormalised and scaled.  Same row-in-registers layout and the same composite-key rounds over
+// the experts; the groups are ranked by their composites (key of the score << 32 | ~group id) without rounds.
 #include "hpc_common.h"
 #include "../../include/hpc_amd.h"
 
@@ -126,6 +133,181 @@ __global__ __launch_bounds__(kThreads) void topk_router_kernel(const float* __re
   }
 }
 
+// ---- group-limited router -------------------------------------------------------------------------------------------
+// the two largest of {a1 >= a2} U {b1 >= b2}
+__device__ __forceinline__ void top2_merge(float& a1, float& a2, float b1, float b2) {
+  const float lo = fminf(a1, b1);
+  a1 = fmaxf(a1, b1);
+  a2 = fmaxf(lo, fmaxf(a2, b2));
+}
+
+// kVec and the element layout as above.  group_lanes: lanes per group when a group is an aligned power-of-two run of
+// lanes of one j (group_size = 4 * group_lanes <= 256: every group's score then comes out of the same log2(group_lanes)
+// xor-shuffle steps), 0 otherwise (a loop over the groups, each reduced across the whole wave).  select_groups = 0:
+// every group stays (one group, or topk_group == num_expert_group) and the group stage is skipped.
+template <int kVec>
+__global__ __launch_bounds__(kThreads) void grouped_topk_router_kernel(
+    const float* __restrict__ logits, const float* __restrict__ bias, int* __restrict__ ids,
+    float* __restrict__ weights, int num_tokens, int num_expert, long ld, int topk, int num_group, int topk_group,
+    int group_size, int group_lanes, int select_groups, int sigmoid, int renormalize, float scale) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  if (row >= num_tokens) return;
+  const float* src = logits + static_cast<long>(row) * ld;
+  const float ninf = -__builtin_inff();
+  float s[kVec][4];  // logits, then scores
+  float b[kVec][4];
+#pragma unroll
+  for (int j = 0; j < kVec; ++j) {
+    const int e0 = 256 * j + 4 * lane;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s[j][c] = ninf, b[j][c] = 0.f;
+    if (e0 < num_expert) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + e0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[j][c] = v[c];
+      if (bias) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(bias + e0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) b[j][c] = w[c];
+      }
+    }
+  }
+  if (sigmoid) {
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[j][c] = 1.f / (1.f + expf(-s[j][c]));  // -inf -> 0, +inf -> 1; 0 past num_expert
+  } else {
+    float row_max = ninf;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) row_max = fmaxf(row_max, s[j][c]);
+    row_max = wave_max(row_max);
+    float denom = 0.f;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        s[j][c] = expf(s[j][c] - row_max);  // 0 past num_expert
+        denom += s[j][c];
+      }
+    denom = wave_sum(denom);
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[j][c] = s[j][c] / denom;
+  }
+  // choice scores and their composites; 0 = struck out / not an expert
+  float ch[kVec][4];
+  uint64_t comp[kVec][4];
+#pragma unroll
+  for (int j = 0; j < kVec; ++j)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = 256 * j + 4 * lane + c;
+      ch[j][c] = e < num_expert ? s[j][c] + b[j][c] : ninf;
+      comp[j][c] = e < num_expert ? (static_cast<uint64_t>(key_of(ch[j][c])) << 32) | (0xffffffffu - e) : 0ull;
+    }
+
+  if (select_groups) {
+    // this lane's two best of each vector (a float4 never straddles a group) and the group the vector belongs to
+    float m1[kVec], m2[kVec];
+    int gid[kVec];
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      m1[j] = fmaxf(ch[j][0], ch[j][1]);
+      m2[j] = fminf(ch[j][0], ch[j][1]);
+      top2_merge(m1[j], m2[j], fmaxf(ch[j][2], ch[j][3]), fminf(ch[j][2], ch[j][3]));
+      const int e0 = 256 * j + 4 * lane;
+      gid[j] = e0 < num_expert ? e0 / group_size : -1;
+    }
+    if (group_lanes) {
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1)
+        if (o < group_lanes) {
+#pragma unroll
+          for (int j = 0; j < kVec; ++j) top2_merge(m1[j], m2[j], __shfl_xor(m1[j], o, 64), __shfl_xor(m2[j], o, 64));
+        }
+    } else {
+      for (int g = 0; g < num_group; ++g) {
+        float g1 = ninf, g2 = ninf;
+#pragma unroll
+        for (int j = 0; j < kVec; ++j)
+          if (gid[j] == g) top2_merge(g1, g2, m1[j], m2[j]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) top2_merge(g1, g2, __shfl_xor(g1, o, 64), __shfl_xor(g2, o, 64));
+#pragma unroll
+        for (int j = 0; j < kVec; ++j)
+          if (gid[j] == g) m1[j] = g1, m2[j] = g2;
+      }
+    }
+    // group composites (every lane of a group holds the same one): key of the score high, inverted group id low
+    uint64_t gcomp[kVec];
+    int beaten[kVec];
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const float score = bias ? m1[j] + m2[j] : m1[j];
+      gcomp[j] = gid[j] >= 0 ? (static_cast<uint64_t>(key_of(score)) << 32) | (0xffffffffu - gid[j]) : 0ull;
+      beaten[j] = 0;
+    }
+    // a group stays when fewer than topk_group groups beat it (the composites of two groups differ).  Group g's
+    // composite is read from the first lane that holds it; the reads do not wait for one another, unlike selection
+    // rounds, each of which needs the one before.
+    for (int g = 0; g < num_group; ++g) {
+      const int e0 = g * group_size;
+      uint64_t v = gcomp[0];
+#pragma unroll
+      for (int j = 1; j < kVec; ++j) v = (e0 >> 8) == j ? gcomp[j] : v;
+      const int from = (e0 & 255) >> 2;
+      const uint32_t lo = __builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(v)), from);
+      const uint32_t hi = __builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(v >> 32)), from);
+      const uint64_t other = (static_cast<uint64_t>(hi) << 32) | lo;
+#pragma unroll
+      for (int j = 0; j < kVec; ++j) beaten[j] += other > gcomp[j] ? 1 : 0;
+    }
+    bool keep[kVec];
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) keep[j] = gid[j] >= 0 && beaten[j] < topk_group;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) comp[j][c] = keep[j] ? comp[j][c] : 0ull;
+  }
+
+  uint64_t mine = 0;  // lane r keeps the winner of round r
+  for (int r = 0; r < topk; ++r) {
+    uint64_t best = 0;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) best = comp[j][c] > best ? comp[j][c] : best;
+    const uint64_t win = wave_max_u64(best);
+#pragma unroll
+    for (int j = 0; j < kVec; ++j)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) comp[j][c] = comp[j][c] == win ? 0ull : comp[j][c];  // composites are unique
+    if (lane == r) mine = win;
+  }
+  // the winner's UNBIASED score, from the lane that holds it (a lane past topk asks lane 63 and drops the answer)
+  const uint32_t e = 0xffffffffu - static_cast<uint32_t>(mine);
+  const int owner = (e >> 2) & 63;
+  float w = 0.f;
+#pragma unroll
+  for (int j = 0; j < kVec; ++j)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float v = __shfl(s[j][c], owner, 64);
+      if (lane < topk && static_cast<int>(e >> 8) == j && static_cast<int>(e & 3) == c) w = v;
+    }
+  if (renormalize) w = w / (wave_sum(w) + 1e-20f);
+  if (lane < topk) {
+    ids[static_cast<long>(row) * topk + lane] = static_cast<int>(e);
+    weights[static_cast<long>(row) * topk + lane] = w * scale;
+  }
+}
+
 }  // namespace router
 }  // namespace hpc
 
@@ -144,6 +326,45 @@ extern "C" int hpc_topk_router_async(int* topk_ids, float* topk_scale, const flo
 #define HPC_ROUTER_LAUNCH(V)                                                                              \
   topk_router_kernel<V><<<grid, kThreads, 0, stream>>>(logits, topk_ids, topk_scale, num_tokens, num_expert, \
                                                        ld_logits, topk, renormalize)
+  if (vec == 1) {
+    HPC_ROUTER_LAUNCH(1);
+  } else if (vec == 2) {
+    HPC_ROUTER_LAUNCH(2);
+  } else {
+    HPC_ROUTER_LAUNCH(4);
+  }
+#undef HPC_ROUTER_LAUNCH
+  HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+
+extern "C" int hpc_grouped_topk_router_async(int* topk_ids, float* topk_scale, const float* logits,
+                                             const float* correction_bias, int num_tokens, int num_expert,
+                                             int64_t ld_logits, int topk, int num_expert_group, int topk_group,
+                                             int scoring_func, int renormalize, float routed_scaling_factor,
+                                             hipStream_t stream) {
+  using namespace hpc::router;
+  if (!topk_ids || !topk_scale || !logits) return HPC_ERR_INVALID;
+  if (num_tokens < 0 || topk < 1 || num_expert_group < 1 || topk_group < 1) return HPC_ERR_INVALID;
+  if (topk_group > num_expert_group || topk > num_expert || (scoring_func != 0 && scoring_func != 1)) return HPC_ERR_INVALID;
+  if (num_expert % num_expert_group != 0) return HPC_ERR_INVALID;
+  const int group_size = num_expert / num_expert_group;
+  if (num_expert > 1024 || (num_expert & 3) || (group_size & 3) || topk > kMaxTopk) return HPC_ERR_UNSUPPORTED;
+  if (topk > static_cast<int64_t>(topk_group) * group_size) return HPC_ERR_UNSUPPORTED;  // not enough candidates
+  if ((ld_logits & 3) || ld_logits < num_expert) return HPC_ERR_UNSUPPORTED;  // 16-byte row segments
+  if ((reinterpret_cast<uintptr_t>(logits) & 15) != 0 || (reinterpret_cast<uintptr_t>(correction_bias) & 15) != 0)
+    return HPC_ERR_UNSUPPORTED;
+  if (num_tokens == 0) return HPC_OK;
+  const int grid = (num_tokens + kWavesPerBlock - 1) / kWavesPerBlock;
+  const int vec = (num_expert + 255) / 256;
+  // a group that is an aligned power-of-two run of lanes of one vector: 4, 8, ... 256 experts
+  const int lanes = group_size / 4;
+  const int group_lanes = (group_size <= 256 && (lanes & (lanes - 1)) == 0) ? lanes : 0;
+  const int select_groups = topk_group < num_expert_group;
+#define HPC_ROUTER_LAUNCH(V)                                                                                         \
+  grouped_topk_router_kernel<V><<<grid, kThreads, 0, stream>>>(                                                      \
+      logits, correction_bias, topk_ids, topk_scale, num_tokens, num_expert, ld_logits, topk, num_expert_group,     \
+      topk_group, group_size, group_lanes, select_groups, scoring_func, renormalize, routed_scaling_factor)
   if (vec == 1) {
     HPC_ROUTER_LAUNCH(1);
   } else if (vec == 2) {

@@ -86,6 +86,49 @@ std::tuple<at::Tensor, at::Tensor> topk_router(const at::Tensor& logits, int64_t
   return std::make_tuple(ids, sc);
 }
 
+// ---- group-limited top-k router (no reference op: pinned to the PyTorch statement tests/grouped_router_ref.py) --------
+std::tuple<at::Tensor, at::Tensor> grouped_topk_router(const at::Tensor& logits, const c10::optional<at::Tensor>& correction_bias,
+                                                       int64_t topk, int64_t num_expert_group, int64_t topk_group,
+                                                       c10::string_view scoring_func, bool renormalize, double routed_scaling_factor,
+                                                       const c10::optional<at::Tensor>& topk_ids_in,
+                                                       const c10::optional<at::Tensor>& topk_scale_in) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32 (the router GEMM's fp32 output)");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [num_tokens, num_expert] with unit expert stride");
+  const int64_t m = logits.size(0), n = logits.size(1);
+  TORCH_CHECK(n % 4 == 0 && n <= 1024, "num_expert must be a multiple of 4 and <= 1024");
+  TORCH_CHECK(scoring_func == "sigmoid" || scoring_func == "softmax", "scoring_func must be \"sigmoid\" or \"softmax\"");
+  TORCH_CHECK(1 <= num_expert_group && 1 <= topk_group && topk_group <= num_expert_group,
+              "topk_group must be in 1..num_expert_group");
+  TORCH_CHECK(n % num_expert_group == 0 && (n / num_expert_group) % 4 == 0,
+              "num_expert must split into num_expert_group groups of a multiple of 4 experts");
+  TORCH_CHECK(1 <= topk && topk <= std::min<int64_t>(n, 64), "topk must be in 1..min(num_expert, 64)");
+  TORCH_CHECK(topk <= topk_group * (n / num_expert_group), "topk must not exceed the experts of topk_group groups");
+  TORCH_CHECK(logits.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logits rows must be 16-byte aligned");
+  const float* bias = nullptr;
+  if (correction_bias.has_value()) {
+    const at::Tensor& cb = *correction_bias;
+    TORCH_CHECK(cb.is_cuda() && cb.device() == logits.device(), "correction_bias must be on the device of logits");
+    TORCH_CHECK(cb.scalar_type() == at::kFloat && cb.is_contiguous() && cb.dim() == 1 && cb.size(0) == n,
+                "correction_bias must be a contiguous float32 [num_expert] tensor");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(cb.data_ptr()) % 16 == 0, "correction_bias must be 16-byte aligned");
+    bias = static_cast<const float*>(cb.data_ptr());
+  }
+  at::Tensor ids = topk_ids_in.has_value() ? *topk_ids_in : at::empty({m, topk}, logits.options().dtype(at::kInt));
+  at::Tensor sc = topk_scale_in.has_value() ? *topk_scale_in : at::empty({m, topk}, logits.options());
+  TORCH_CHECK(ids.scalar_type() == at::kInt && ids.is_contiguous() && ids.dim() == 2 && ids.size(0) == m && ids.size(1) == topk,
+              "topk_ids must be a contiguous int32 [num_tokens, topk] tensor");
+  TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == m && sc.size(1) == topk,
+              "topk_scale must be a contiguous float32 [num_tokens, topk] tensor");
+  const int rc = hpc_grouped_topk_router_async(static_cast<int*>(ids.data_ptr()), static_cast<float*>(sc.data_ptr()),
+                                               static_cast<const float*>(logits.data_ptr()), bias, i32(m), i32(n), logits.stride(0),
+                                               i32(topk), i32(num_expert_group), i32(topk_group), scoring_func == "sigmoid" ? 1 : 0,
+                                               renormalize ? 1 : 0, static_cast<float>(routed_scaling_factor), stream_of(logits));
+  HPC_LAUNCH_CHECK(rc, "grouped_topk_router");
+  return std::make_tuple(ids, sc);
+}
+
 // ---- RoPE + QK-norm + paged KV store (reference src/rope/entry.cc:14-222) ---------------------------------------------
 struct RopeDims {
   int64_t num_q, num_kv;
@@ -462,4 +505,15 @@ TORCH_LIBRARY_IMPL(hpc, CUDA, m) {
   m.impl("fused_sampler_temperature_sample", &fused_sampler_temperature_sample);
   m.impl("fuse_allreduce_rmsnorm_high_throughput", &fuse_allreduce_rmsnorm_high_throughput);
   m.impl("fuse_allreduce_rmsnorm_low_latency", &fuse_allreduce_rmsnorm_low_latency);
+}
+
+// ours only, like topk_router, and under its own namespace: torch.ops.hpc_router.* (hpc:: holds the reference's surface)
+TORCH_LIBRARY(hpc_router, m) {
+  m.def(
+      "grouped_topk_router(Tensor logits, Tensor? correction_bias, int topk, int num_expert_group, int topk_group, "
+      "str scoring_func, bool renormalize, float routed_scaling_factor, Tensor? topk_ids, Tensor? topk_scale) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(hpc_router, CUDA, m) {
+  m.impl("grouped_topk_router", &grouped_topk_router);
 }

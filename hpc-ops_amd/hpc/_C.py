@@ -86,6 +86,7 @@ _sig("hpc_gemm_bf16xfp32_splits", I, I, I, I, I)
 _sig("hpc_gemm_bf16xfp32_plan", I, I, I, I, I, IP, IP, IP)
 _sig("hpc_gemm_bf16xfp32_async", I, P, P, P, P, P, P, I, I, I, F, I, I, I, P)
 _sig("hpc_topk_router_async", I, IP, P, P, I, I, L, I, I, P)
+_sig("hpc_grouped_topk_router_async", I, IP, P, P, P, I, I, L, I, I, I, I, I, F, P)
 _sig("hpc_attention_with_kvcache_prefill_fp8_async", I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I,
      I, I, L, L, L, L, L, L, L, L, L, P)
 _sig("hpc_attention_with_kvcache_blocksparse_prefill_fp8_async", I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I,

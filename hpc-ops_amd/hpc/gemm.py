@@ -52,3 +52,32 @@ def _topk_router_fake(logits, topk, renormalize=True, topk_ids=None, topk_scale=
     m = logits.shape[0]
     return (torch.empty((m, topk), dtype=torch.int32, device=logits.device),
             torch.empty((m, topk), dtype=torch.float32, device=logits.device))
+
+
+def grouped_topk_router(logits: Tensor, topk: int, num_expert_group: int = 1, topk_group: int = 1,
+                        correction_bias: Tensor = None, scoring_func: str = "sigmoid", renormalize: bool = True,
+                        routed_scaling_factor: float = 1.0, topk_ids: Tensor = None, topk_scale: Tensor = None):
+    """Group-limited top-k router (DeepSeek-V3 / R1 and Kimi-K2: sigmoid + correction bias; DeepSeek-V2: softmax, no
+    bias) over the fp32 output of gemm_bf16xfp32: returns (topk_ids int32 [m, topk], topk_scale float32 [m, topk]) -
+    what fuse_moe / fuse_moe_blockwise_fp8 take.
+
+    No reference counterpart; semantics = PyTorch, in fp32:
+    s = sigmoid(logits) or softmax(logits, -1) (scoring_func "sigmoid" / "softmax"); c = s + correction_bias (c = s
+    without one).  Group g is the contiguous expert range [g * gs, (g + 1) * gs), gs = num_expert // num_expert_group;
+    its score is the sum of its two best c with a bias, its best c without.  The topk_group best groups stay (ties ->
+    smaller group id), ids = argsort(c over the experts of those groups, descending, stable)[:, :topk] (ties -> smaller
+    expert id, best first), scale = s[ids] - the UNBIASED scores -, divided by (scale.sum(-1) + 1e-20) with
+    renormalize, times routed_scaling_factor.  num_expert_group == topk_group keeps every group.  A row that holds a
+    NaN has an unspecified result with ids in range.
+    logits [m, num_expert] float32 with 16-byte aligned rows, num_expert % 4 == 0 and <= 1024, gs % 4 == 0,
+    topk <= min(64, topk_group * gs); correction_bias contiguous float32 [num_expert]."""
+    return torch.ops.hpc_router.grouped_topk_router(logits, correction_bias, topk, num_expert_group, topk_group,
+                                                    scoring_func, renormalize, routed_scaling_factor, topk_ids, topk_scale)
+
+
+@torch.library.register_fake("hpc_router::grouped_topk_router")
+def _grouped_topk_router_fake(logits, correction_bias, topk, num_expert_group, topk_group, scoring_func, renormalize,
+                              routed_scaling_factor, topk_ids=None, topk_scale=None):
+    m = logits.shape[0]
+    return (torch.empty((m, topk), dtype=torch.int32, device=logits.device),
+            torch.empty((m, topk), dtype=torch.float32, device=logits.device))

@@ -342,6 +342,25 @@ int hpc_gemm_bf16xfp32_async(void* y, void* splitk_y, void* split_flag, const vo
 int hpc_topk_router_async(int* topk_ids, float* topk_scale, const float* logits, int num_tokens, int num_expert,
                           int64_t ld_logits, int topk, int renormalize, hpc_stream_t stream);
 
+/* ---- group-limited top-k router (DeepSeek-V3 / R1, Kimi-K2, DeepSeek-V2 routing; same place in the chain) ----
+ * No reference kernel exists; the semantics are the PyTorch statement tests/grouped_router_ref.py:
+ *   s = sigmoid(logits) (scoring_func 1) or softmax(logits) (0), fp32;  c = s + correction_bias (c = s when NULL);
+ *   the experts form num_expert_group contiguous groups of group_size = num_expert / num_expert_group; a group's
+ *   score is the sum of its two best c with a bias and its best c without; the topk_group best groups stay (ties ->
+ *   smaller group id);  ids = the first `topk` entries of a STABLE descending sort of c over the experts of the
+ *   groups that stay (ties -> smaller expert id), best first;  topk_scale = s[ids] - the UNBIASED scores -, divided
+ *   by (their sum + 1e-20) when renormalize, times routed_scaling_factor.
+ * num_expert_group == topk_group keeps every group (one group: plain top-k on c).  A NaN in a row leaves that row's
+ * result unspecified, its ids still in [0, num_expert).
+ * logits f32 [num_tokens, ld_logits >= num_expert], 16-byte aligned rows; correction_bias f32 [num_expert], 16-byte
+ * aligned, or NULL; num_expert % 4 == 0, <= 1024; group_size % 4 == 0; topk <= 64 and <= topk_group * group_size.
+ * topk_ids int32 [num_tokens, topk], topk_scale f32 [num_tokens, topk] - the tensors hpc_fuse_moe_*_async take. */
+int hpc_grouped_topk_router_async(int* topk_ids, float* topk_scale, const float* logits,
+                                  const float* correction_bias /* may be NULL */, int num_tokens, int num_expert,
+                                  int64_t ld_logits, int topk, int num_expert_group, int topk_group,
+                                  int scoring_func /* 0 softmax, 1 sigmoid */, int renormalize,
+                                  float routed_scaling_factor, hpc_stream_t stream);
+
 /* bf16 causal prefill: paged KV cache, and contiguous varlen K/V [total_seq, Hkv, 128] (row strides ldK / ldV
  * elements; every q token attends the keys of its request up to itself).
  * reference: attention_with_kvcache_prefill_bf16_async / attention_prefill_bf16_async (src/attention/prefill/prefill.h,

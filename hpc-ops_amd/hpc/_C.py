@@ -96,6 +96,8 @@ _sig("hpc_attention_with_kvcache_prefill_bf16_async", I, P, P, P, P, P, P, P, I,
 _sig("hpc_attention_prefill_bf16_async", I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P)
 _sig("hpc_masked_act_mul_and_quant_async", I, P, P, P, P, I, I, I, P)
 _sig("hpc_masked_act_mul_and_blockwise_quant_async", I, P, P, P, P, I, I, I, P)
+_sig("hpc_blockwise_fp8_quant_async", I, P, P, P, I, I, I, P)
+_sig("hpc_fused_rmsnorm_blockwise_quant_async", I, P, P, P, P, P, P, F, I, I, P)
 _sig("hpc_reformat_x_scale_async", I, P, P, P, P, I, I, I, I, P)
 _sig("hpc_stem_oam_prep_paged_kv_async", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, L, L, L, L, L, L,
      L, L, L, P)

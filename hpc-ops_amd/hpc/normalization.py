@@ -1,5 +1,6 @@
-"""hpc.normalization — fused RMSNorm + FP8 quantisation (public surface of reference hpc/normalization.py:6-53)."""
-from typing import Tuple, Union
+"""hpc.normalization — fused RMSNorm + FP8 quantisation (public surface of reference hpc/normalization.py:6-53), and the
+form with one scale per 128 columns in front of the blockwise fused MoE (fused_rmsnorm_blockwise_quant, ours)."""
+from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -30,3 +31,44 @@ def fused_rmsnorm_with_scale_fake(a, weight, scale, eps, is_moe):
     # schema order (input, weight, scale, eps, is_moe) - the reference's fake swaps eps / scale
     # (hpc/normalization.py:44-53); the op always has three outputs
     return (torch.empty_like(a, dtype=_F8), torch.empty_like(a, dtype=torch.float32), torch.empty_like(a, dtype=_F8))
+
+
+def fused_rmsnorm_blockwise_quant(a: Tensor, weight: Tensor, eps: float = 1e-6, residual: Optional[Tensor] = None,
+                                  return_normed: bool = False, output: Optional[Tensor] = None,
+                                  output_scale: Optional[Tensor] = None,
+                                  output_normed: Optional[Tensor] = None) -> Tuple[Tensor, ...]:
+    """Residual add + RMSNorm + 128-block e4m3 quantisation in one kernel: returns (q float8_e4m3fn [T, H], scale float32
+    [T, H/128]) - the (x, x_scale) pair fuse_moe_blockwise* takes - or (q, scale, y) with return_normed, y the bfloat16
+    [T, H] normed rows the router GEMM (gemm_bf16xfp32) consumes.  No reference counterpart
+    (torch.ops.hpc_quant.fused_rmsnorm_blockwise_quant); semantics = PyTorch:
+        h = a, or with residual h = bf16(a.float() + residual.float()), stored to residual IN PLACE and normed as rounded
+            (the order of fuse_allreduce_rmsnorm_*)
+        y = bf16(h.float() * rsqrt(mean(h.float()^2) + eps) * weight.float())     fp32 throughout, rounded once
+        q, scale = blockwise_fp8_quant(y)                                          of the bf16-ROUNDED y, bit for bit
+    so this op and "norm to bf16, then blockwise_fp8_quant" hand the MoE identically quantised rows.
+
+    a: bfloat16 [T, H], contiguous, H % 128 == 0, 128 <= H <= 16384, never written; weight: bfloat16 [H] or [1, H];
+    residual: bfloat16 [T, H].  output / output_scale / output_normed (the last with return_normed only), when given, are
+    written and returned as the same objects; with all of them given nothing is allocated and the call captures into a
+    hipGraph.  The buffers must not overlap.  T == 0 returns empty tensors without a launch."""
+    q, scale, y = torch.ops.hpc_quant.fused_rmsnorm_blockwise_quant(a, weight, eps, residual, return_normed, output,
+                                                                    output_scale, output_normed)
+    q = q if output is None else output
+    scale = scale if output_scale is None else output_scale
+    if return_normed:
+        return q, scale, (y if output_normed is None else output_normed)
+    return q, scale
+
+
+@torch.library.register_fake("hpc_quant::fused_rmsnorm_blockwise_quant")
+def _fused_rmsnorm_blockwise_quant_fake(a, weight, eps, residual, return_normed, output=None, output_scale=None,
+                                        output_normed=None):
+    # the op always has three outputs: the third is an empty [0] tensor without return_normed
+    t, h = a.shape
+    q = output if output is not None else torch.empty((t, h), dtype=_F8, device=a.device)
+    sc = output_scale if output_scale is not None else torch.empty((t, h // 128), dtype=torch.float32, device=a.device)
+    if not return_normed:
+        y = torch.empty((0,), dtype=a.dtype, device=a.device)
+    else:
+        y = output_normed if output_normed is not None else torch.empty_like(a)
+    return q, sc, y

@@ -401,6 +401,35 @@ int hpc_masked_act_mul_and_blockwise_quant_async(void* out, void* out_scale, con
                                                  int intermediate_size, int num_tokens_per_expert,
                                                  hpc_stream_t stream);
 
+/* ---- 128-block e4m3 activation quantisation, alone and behind residual add + RMSNorm: the producers of the
+ * (x e4m3 [T, H], x_scale f32 [T, H/128]) pair hpc_fuse_moe_blockwise_async / hpc_group_gemm_blockwise_fp8_async take ----
+ * No reference kernel exists; the semantics are the PyTorch statement tests/blockwise_quant_ref.py.  For a row a (values
+ * taken to fp32) and each block b of 128 consecutive columns - the arithmetic of the blockwise activation above:
+ *   amax = max |a[b*128 : (b+1)*128]|;  scale = amax / 448 (fp32 division) -> output_scale[t, b];
+ *   q = e4m3fn(a * (1 / (scale + 1e-8f))), one fp32 multiply, round to nearest even -> output_fp8[t, b*128 ...].
+ * An all-zero block gives scale 0 and q 0.  A NaN or Inf in a block leaves that block's q and scale unspecified, other
+ * blocks and rows unaffected; fp32 denormal inputs are unspecified.
+ *
+ * hpc_blockwise_fp8_quant_async: input [num_tokens, hidden] contiguous, in_dtype 0 = bf16, 1 = fp16, 2 = fp32.
+ *
+ * hpc_fused_rmsnorm_blockwise_quant_async: input bf16 [num_tokens, hidden], weight bf16 [hidden].
+ *   h = input, or with residual (bf16 [num_tokens, hidden], IN/OUT) h = bf16(float(input) + float(residual)), stored to
+ *   residual and normed as rounded (the order of the fused all-reduce ops);
+ *   y = bf16(float(h) * rsqrt(mean(float(h)^2) + eps) * float(weight)), fp32 throughout, rounded once;
+ *   (output_fp8, output_scale) = the block quantisation above of the bf16-ROUNDED y, i.e. bit for bit what
+ *   hpc_blockwise_fp8_quant_async gives on y;  output_normed (bf16 [num_tokens, hidden], may be NULL) = y, the input of
+ *   the router GEMM.  input is never written; the buffers must not overlap.
+ *
+ * Both: hidden % 128 == 0, 128 <= hidden <= 16384 (-1 otherwise); num_tokens >= 0, 0 launches nothing; input, weight,
+ * residual and output_normed 16-byte aligned, output_fp8 8-byte aligned (-1 otherwise); output_fp8 e4m3
+ * [num_tokens, hidden], output_scale f32 [num_tokens, hidden / 128] row-major.  Every check is made on the host. */
+int hpc_blockwise_fp8_quant_async(void* output_fp8, float* output_scale, const void* input, int in_dtype, int num_tokens,
+                                  int hidden, hpc_stream_t stream);
+int hpc_fused_rmsnorm_blockwise_quant_async(void* output_fp8, float* output_scale, void* output_normed /* may be NULL */,
+                                            const void* input, const void* weight,
+                                            void* residual /* in/out, may be NULL */, float eps, int num_tokens,
+                                            int hidden, hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

@@ -19,6 +19,8 @@
 //     penalty bit.
 // The fast path (temperature only) is a two-step arg-max of logits / T + Gumbel noise.
 // Self-drawn noise: Philox-4x32-10 keyed by the caller's seed, counter = (token, row, launch offset).
+// Draft-token verification of a speculative step (hpc_speculative_verify_async) is the fast path's segment pass plus the
+// segment's softmax statistics, and a one-wave accept scan per request.
 #include "hpc_common.h"
 #include "../../include/hpc_amd.h"
 
@@ -391,6 +393,189 @@ __global__ __launch_bounds__(64) void temperature_final_kernel(const Args a) {
   if (lane == 0) a.out[b] = static_cast<int>(0xffffffffu - static_cast<uint32_t>(best));
 }
 
+// ---- draft-token verification of a speculative decode step (ours: no reference counterpart) -------------------------
+// Rows are positions: row r = b * (K + 1) + j is position j of request b, and the temperature is per REQUEST.  Phase 1 is
+// the fast path's segment pass - the same composite of the same expression x / T + noise, the row's draft at -inf - that
+// also keeps the segment's softmax statistics of x / T and the scaled logit at the draft; phase 2, one wave per request,
+// folds the segments of every position, forms p = softmax(x / T)[draft] and finds the first rejection.  No atomics, no
+// scratch, LDS only for the cross-wave reduction.
+struct VerifyStat {  // one per (row, segment)
+  uint64_t best;     // fast-path composite of the best score, draft masked
+  float m, sum;      // max of x / T, sum exp(x / T - m)
+};
+struct VerifyArgs {
+  Args a;                 // logits, dtype, row_stride, B = rows, V, S, seg, t_arr / t_val, noise, seed, offset, out
+  const int64_t* draft;   // [requests][K]
+  const float* uniform;   // [requests][K], null: drawn
+  int K;
+  int* num_accepted;      // [requests]
+  VerifyStat* stat;       // [rows][S]
+  float* xd;              // [rows]: x / T at the row's draft (x when greedy), written by the segment that owns it
+};
+
+// the uniform of row r: counter word 0 is all ones, a token id (< 2^20) never is
+__device__ __forceinline__ float own_uniform(const Args& a, int r) {
+  const uint32_t w = philox_word0(a.seed, 0xffffffffu, static_cast<uint32_t>(r), static_cast<uint32_t>(a.offset),
+                                  static_cast<uint32_t>(a.offset >> 32));
+  return static_cast<float>(w >> 8) * (1.0f / 16777216.0f);  // [0, 1)
+}
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
+  const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), o, 64);
+  const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), o, 64);
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+// (m, s) <- the softmax statistics of the union of two sets; an empty set is (-inf, 0)
+__device__ __forceinline__ void stat_merge(float& m, float& s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  const float sub = mx == kNegInf ? 0.f : mx;
+  s = s * __expf(m - sub) + s2 * __expf(m2 - sub);
+  m = mx;
+}
+
+__global__ __launch_bounds__(kThreads) void verify_segment_kernel(const VerifyArgs v) {
+  __shared__ uint64_t s_best[4];
+  __shared__ float s_m[4], s_s[4];
+  const Args& a = v.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x, r = blockIdx.y;
+  const int b = r / (v.K + 1), j = r - b * (v.K + 1);
+  // a row past the request's first invalid draft is not read (block-uniform)
+  const int64_t* drow = v.draft + static_cast<long>(b) * v.K;
+  for (int t = 0; t < j; ++t) {
+    const int64_t d = drow[t];
+    if (d < 0 || d >= a.V) return;
+  }
+  int64_t dr = -1;  // the bonus row (j == n_b) has no mask
+  if (j < v.K) {
+    const int64_t d = drow[j];
+    if (d >= 0 && d < a.V) dr = d;
+  }
+  const float temp = a.t_arr ? a.t_arr[b] : a.t_val;
+  const bool greedy = !(temp > 0.f);
+  const int i0 = s * a.seg, i1 = min(a.V, i0 + a.seg);
+
+  // every load of the segment is issued before the first use: a decode step has few rows, and a thread that waited for
+  // each element in turn would spend the pass on memory latency.  Out-of-range slots read the segment's last element
+  // (an empty segment reads nothing) and are set to -inf.
+  float xs[kElems];
+  const int last = i1 - 1;
+  if (i0 >= i1) {
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = 0.f;
+  } else if (a.dtype == 0) {  // one branch per dtype, so that no load waits for a conversion
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = load_logit(a, r, min(i0 + e * kThreads + tid, last));
+  } else {
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = load_logit(a, r, min(i0 + e * kThreads + tid, last));
+  }
+  float m = kNegInf;
+  uint64_t best = 0;
+  float xd = 0.f;
+  bool owns = false;
+#pragma unroll
+  for (int e = 0; e < kElems; ++e) {
+    const int i = i0 + e * kThreads + tid;
+    float x = greedy ? xs[e] : xs[e] / temp;
+    xs[e] = i < i1 ? x : kNegInf;
+    if (i < i1) {
+      m = fmaxf(m, x);
+      if (static_cast<int64_t>(i) == dr) {
+        xd = x;
+        owns = true;
+        x = kNegInf;
+      }
+      if (!greedy) x += a.noise ? a.noise[static_cast<long>(r) * a.V + i] : own_gumbel(a, r, i);
+      const uint64_t c = (static_cast<uint64_t>(key_of(x)) << 32) | (0xffffffffu - static_cast<uint32_t>(i));
+      best = c > best ? c : best;
+    }
+  }
+  if (owns) v.xd[r] = xd;  // one thread of one segment
+  float sum = 0.f;
+  if (!greedy) {
+    const float sub = m == kNegInf ? 0.f : m;
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) sum += __expf(xs[e] - sub);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t c = shfl_xor_u64(best, o);
+    best = c > best ? c : best;
+    stat_merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
+  }
+  if (lane == 0) {
+    s_best[wave] = best;
+    s_m[wave] = m;
+    s_s[wave] = sum;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) {
+      best = s_best[w] > best ? s_best[w] : best;
+      stat_merge(m, sum, s_m[w], s_s[w]);
+    }
+    VerifyStat* st = v.stat + static_cast<long>(r) * a.S + s;
+    st->best = best;
+    st->m = m;
+    st->sum = sum;
+  }
+}
+
+// One wave per request.  Position j (K + 1 <= 16 of them) belongs to the four lanes 4 j .. 4 j + 3: they fold its segments,
+// lane 4 j decides it, and two ballots replace the scan: the leading valid drafts give n_b, the leading accepted ones the
+// position of the sampled token.
+__global__ __launch_bounds__(64) void verify_final_kernel(const VerifyArgs v) {
+  constexpr uint64_t kHeads = 0x1111111111111111ull;  // lane 4 j of every position
+  const Args& a = v.a;
+  const int b = blockIdx.x, lane = threadIdx.x, K = v.K;
+  const int j = lane >> 2, sub = lane & 3;
+  const float temp = a.t_arr ? a.t_arr[b] : a.t_val;
+  const bool greedy = !(temp > 0.f);
+  const int r = b * (K + 1) + j;
+  int64_t d = -1;
+  if (j < K) {
+    d = v.draft[static_cast<long>(b) * K + j];
+    if (d < 0 || d >= a.V) d = -1;
+  }
+  // positions K .. 15 count as invalid, so a clear bit exists; rows past n_b were not written by the segment pass
+  const int nb = __builtin_ctzll(~__ballot(d >= 0) & kHeads) >> 2;
+  const bool live = j <= nb;
+  float m = kNegInf, sum = 0.f;
+  uint64_t best = 0;
+  if (live) {
+    for (int s = sub; s < a.S; s += 4) {
+      const VerifyStat st = v.stat[static_cast<long>(r) * a.S + s];
+      best = st.best > best ? st.best : best;
+      stat_merge(m, sum, st.m, st.sum);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o <= 2; o <<= 1) {
+    const uint64_t c = shfl_xor_u64(best, o);
+    best = c > best ? c : best;
+    stat_merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
+  }
+  bool accept = false;
+  if (live && d >= 0) {
+    const float xd = v.xd[r];
+    if (greedy) {  // d is the arg-max iff its composite beats the best of the others
+      accept = ((static_cast<uint64_t>(key_of(xd)) << 32) | (0xffffffffu - static_cast<uint32_t>(d))) > best;
+    } else {
+      const float p = __expf(xd - m) / sum;
+      const float u = v.uniform ? v.uniform[static_cast<long>(b) * K + j] : own_uniform(a, r);
+      accept = u < p;
+    }
+  }
+  // only lane 4 j's verdict counts (the lanes of a position add their statistics in different orders); position n_b has
+  // no draft and is never accepted, so the first clear bit is at most n_b
+  const int jr = __builtin_ctzll(~__ballot(accept) & kHeads) >> 2;
+  if (sub == 0 && j <= K) {
+    int* out = a.out + static_cast<long>(b) * (K + 1);
+    out[j] = j < jr ? static_cast<int>(d) : (j == jr ? static_cast<int>(0xffffffffu - static_cast<uint32_t>(best)) : -1);
+  }
+  if (lane == 0) v.num_accepted[b] = jr;
+}
+
 // launch counter: the same seed gives fresh noise on every launch (reference sampler_rng.cuh:41-52)
 std::atomic<uint64_t> g_launch_offset{0};
 inline uint64_t next_offset() { return g_launch_offset.fetch_add(128, std::memory_order_relaxed); }
@@ -495,6 +680,60 @@ extern "C" int hpc_fused_sampler_temperature_async(void* token_ids, void* worksp
   temperature_segment_kernel<<<dim3(a.S, batch_size), kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   temperature_final_kernel<<<batch_size, 64, 0, stream>>>(a);
+  HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+
+// workspace: segment statistics [rows][S] of 16 bytes + the scaled logit at each row's draft [rows] f32
+extern "C" int64_t hpc_speculative_verify_workspace_bytes(int batch_size, int num_draft, int vocab_size) {
+  if (batch_size < 0 || num_draft < 0 || vocab_size <= 0) return 0;
+  const int64_t rows = static_cast<int64_t>(batch_size) * (num_draft + 1);
+  return rows * hpc::sampler::segments_of(vocab_size) * static_cast<int64_t>(sizeof(hpc::sampler::VerifyStat)) + rows * 4;
+}
+
+// semantics: include/hpc_amd.h.  Every check runs before the batch_size == 0 return, so none can reach a launch.
+extern "C" int hpc_speculative_verify_async(void* output_token_ids, void* num_accepted, void* workspace, const void* logits,
+                                            int logits_dtype, int64_t logits_row_stride, const void* draft_token_ids,
+                                            const void* temperature, float temperature_val, const void* uniform_samples,
+                                            const void* gumbel_noise, int batch_size, int num_draft, int vocab_size,
+                                            uint64_t rng_seed, hipStream_t stream) {
+  using namespace hpc::sampler;
+  if (!output_token_ids || !num_accepted || !workspace || !logits) return HPC_ERR_INVALID;
+  if (batch_size < 0 || num_draft < 0 || vocab_size <= 0 || (logits_dtype != 0 && logits_dtype != 1)) return HPC_ERR_INVALID;
+  if (num_draft > 0 && !draft_token_ids) return HPC_ERR_INVALID;
+  if (logits_row_stride < vocab_size) return HPC_ERR_INVALID;
+  // no draft, no uniform: with num_draft == 0 uniform_samples is [batch_size, 0] and is not looked at
+  if (num_draft > 0 && (uniform_samples == nullptr) != (gumbel_noise == nullptr)) return HPC_ERR_INVALID;
+  if (!gumbel_noise && rng_seed == 0) return HPC_ERR_INVALID;
+  if (num_draft > 15) return HPC_ERR_UNSUPPORTED;
+  if ((vocab_size & 7) || vocab_size >= (1 << kIdxBits)) return HPC_ERR_UNSUPPORTED;
+  const int64_t rows = static_cast<int64_t>(batch_size) * (num_draft + 1);
+  if (rows > 65535) return HPC_ERR_UNSUPPORTED;
+  if (batch_size == 0) return HPC_OK;
+  VerifyArgs v{};
+  Args& a = v.a;
+  a.logits = logits;
+  a.dtype = logits_dtype;
+  a.row_stride = logits_row_stride;
+  a.B = static_cast<int>(rows);
+  a.V = vocab_size;
+  a.S = segments_of(vocab_size);
+  a.seg = (vocab_size + a.S - 1) / a.S;  // <= kSegMax: the segment pass keeps a thread's kElems elements in registers
+  a.t_arr = static_cast<const float*>(temperature);
+  a.t_val = temperature_val;
+  a.noise = static_cast<const float*>(gumbel_noise);
+  a.seed = rng_seed;
+  a.offset = gumbel_noise ? 0 : next_offset();
+  a.out = static_cast<int*>(output_token_ids);
+  v.draft = static_cast<const int64_t*>(draft_token_ids);
+  v.uniform = static_cast<const float*>(uniform_samples);
+  v.K = num_draft;
+  v.num_accepted = static_cast<int*>(num_accepted);
+  v.stat = static_cast<VerifyStat*>(workspace);
+  v.xd = reinterpret_cast<float*>(v.stat + rows * a.S);
+  verify_segment_kernel<<<dim3(a.S, static_cast<unsigned>(rows)), kThreads, 0, stream>>>(v);
+  HPC_CHECK_LAUNCH();
+  verify_final_kernel<<<batch_size, 64, 0, stream>>>(v);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }

@@ -108,6 +108,8 @@ _sig("hpc_sampler_segments", I, I)
 _sig("hpc_fused_sampler_workspace_bytes", L, I, I, I)
 _sig("hpc_fused_sampler_async", I, P, P, P, I, P, L, P, P, F, P, F, I, P, I, I, P, F, P, I, I, L, I, ctypes.c_uint64, P)
 _sig("hpc_fused_sampler_temperature_async", I, P, P, P, I, L, P, F, P, P, I, I, ctypes.c_uint64, P)
+_sig("hpc_speculative_verify_workspace_bytes", L, I, I, I)
+_sig("hpc_speculative_verify_async", I, P, P, P, P, I, L, P, P, F, P, P, I, I, I, ctypes.c_uint64, P)
 PP = ctypes.POINTER(c_void_p)
 _sig("hpc_comm_create", I, I, I, I, c_char_p)
 _sig("hpc_comm_destroy", I, I)

@@ -104,3 +104,57 @@ def _fused_sampler_fake(logits, penalty_mask, slot_id, repetition_penalty, repet
 def _fused_sampler_temperature_fake(logits, temperature, temperature_val, gumbel_noise=None, draft_token_ids=None,
                                     seed=0):
     return torch.empty((logits.shape[0], 1), dtype=torch.int32, device=logits.device)
+
+
+def speculative_verify(
+    logits: Tensor,
+    draft_token_ids: Tensor,
+    *,
+    temperature: Union[Tensor, float] = 1.0,
+    uniform_samples: Optional[Tensor] = None,
+    gumbel_noise: Optional[Tensor] = None,
+    seed: int = 0,
+    output_token_ids: Optional[Tensor] = None,
+    num_accepted: Optional[Tensor] = None,
+) -> Tuple[Tensor, Tensor]:
+    """Draft-token verification at the end of a speculative (MTP) decode step, in one pass over the logits: how many
+    of a request's K drafts are accepted, the recovered token at the first rejection, or the bonus token when all are
+    accepted.  No reference counterpart (torch.ops.hpc_spec.speculative_verify); semantics = PyTorch
+    (tests/spec_verify_ref.py).
+
+    logits [B * (K + 1), V] float32 / bfloat16 (inner stride 1, row stride >= V, V % 8 == 0, V < 2^20, never written):
+    row b * (K + 1) + j is the target model's distribution for position j of request b.  draft_token_ids int64 [B, K],
+    0 <= K <= 15: the first entry < 0 or >= V ends the request's drafts, n_b = number of leading valid entries; logits rows
+    past n_b are not read.  temperature: scalar or float32 [B], one per request; 0 = greedy for that request (negative or
+    NaN: unspecified).  Per request, with T its temperature, for j = 0 .. n_b - 1, r = b * (K + 1) + j, d = draft[b, j]:
+        T > 0:  accept iff uniform_samples[b, j] < softmax(logits[r].float() / T)[d]
+        T == 0: accept iff d == argmax(logits[r]), ties -> smaller token id
+    First rejection at j: out[b, j] = argmax(logits[r].float() / T + gumbel_noise[r]) with entry d at -inf, ties -> smaller
+    id - exactly what fused_sampler(row, temperature=T, gumbel_noise=..., draft_token_ids=d) returns - or argmax(logits[r])
+    when T == 0; out[b, :j] are the accepted drafts, out[b, j+1:] = -1, num_accepted[b] = j.  All accepted:
+    out[b, n_b] is sampled from row b * (K + 1) + n_b without a mask (arg-max when T == 0), num_accepted[b] = n_b, later
+    entries are -1.
+
+    This is rejection sampling against a draft distribution that puts probability 1 on d: accept with probability
+    min(1, p(d) / 1) = p(d), and the residual max(0, p - q) renormalised is the target with d removed - which is what
+    Gumbel-max with d at -inf draws - so every out[b, 0] (and every emitted token, given its prefix) is distributed
+    exactly as the target model's softmax(logits / T).
+
+    uniform_samples float32 [B, K] in [0, 1) and gumbel_noise float32 [B * (K + 1), V]: together (the call is then
+    deterministic) or not at all; absent, both are drawn from Philox keyed by ``seed`` (> 0) under fused_sampler's
+    launch-offset rule, the uniform from a counter no Gumbel draw can take.  output_token_ids int32 [B, K + 1] and
+    num_accepted int32 [B], when given, are written and returned as the same objects.  B == 0 returns empty tensors
+    without a launch; B * (K + 1) <= 65535.  There is no host sync.
+    Returns (output_token_ids, num_accepted)."""
+    temp_tensor, temp_scalar = (temperature, 0.0) if isinstance(temperature, Tensor) else (None, float(temperature))
+    out, acc = torch.ops.hpc_spec.speculative_verify(logits, draft_token_ids, temp_tensor, temp_scalar, uniform_samples,
+                                                     gumbel_noise, seed, output_token_ids, num_accepted)
+    return (out if output_token_ids is None else output_token_ids, acc if num_accepted is None else num_accepted)
+
+
+@torch.library.register_fake("hpc_spec::speculative_verify")
+def _speculative_verify_fake(logits, draft_token_ids, temperature, temperature_val, uniform_samples=None, gumbel_noise=None,
+                             seed=0, output_token_ids=None, num_accepted=None):
+    b, k = draft_token_ids.shape
+    return (torch.empty((b, k + 1), dtype=torch.int32, device=logits.device),
+            torch.empty((b,), dtype=torch.int32, device=logits.device))

@@ -527,6 +527,34 @@ int hpc_fused_sampler_temperature_async(void* token_ids, void* workspace, const 
                                         const void* draft_token_ids, int batch_size, int vocab_size,
                                         uint64_t rng_seed, hpc_stream_t stream);
 
+/* ---- draft-token verification at the end of a speculative (MTP) decode step (ours: no reference counterpart) ----
+ * Rejection sampling of num_draft = K draft tokens per request against the target model's logits, with a draft that
+ * puts probability 1 on its token.  logits [batch_size * (K + 1), V] as for the sampler above (dtype 0 fp32 / 1 bf16,
+ * inner stride 1, row stride >= V in elements, V % 8 == 0, V < 2^20, never written); row b * (K + 1) + j is position j
+ * of request b.  draft_token_ids int64 [batch_size, K], 0 <= K <= 15 (may be NULL when K == 0): the first entry < 0 or
+ * >= V ends the request's drafts, n_b = number of leading valid entries; logits rows past n_b are not read.
+ * temperature f32 [batch_size] or NULL (then temperature_val); T = 0 is greedy for that request.
+ * For j < n_b, d = draft[b][j], x = fp32 row b * (K + 1) + j:
+ *   T > 0: accept iff uniform[b][j] < softmax(x / T)[d];   T == 0: accept iff d == argmax(x), ties -> smaller id.
+ * First rejection at j: out[b][j] = argmax(x / T + gumbel) with entry d at -inf (T == 0: argmax(x)) - the token
+ *   hpc_fused_sampler_temperature_async gives that row with draft d -, num_accepted[b] = j.
+ * All n_b accepted: out[b][n_b] = argmax(x / T + gumbel) of row b * (K + 1) + n_b, no mask; num_accepted[b] = n_b.
+ * out[b][:num_accepted[b]] are the accepted drafts, entries after the sampled one are -1.
+ * uniform_samples f32 [batch_size, K] in [0, 1) and gumbel_noise f32 [batch_size * (K + 1), V]: both or neither
+ * (uniform_samples is not looked at when K == 0); with
+ * neither both are drawn from Philox keyed by rng_seed (> 0) at the sampler's launch offset, the uniform at a counter
+ * no Gumbel draw takes.  output_token_ids int32 [batch_size, K + 1], num_accepted int32 [batch_size].
+ * workspace: hpc_speculative_verify_workspace_bytes.  batch_size * (K + 1) <= 65535.  Every check runs on the host before
+ * the batch_size == 0 return and before any launch: HPC_ERR_INVALID for null pointers, negative sizes, K < 0, a row
+ * stride below V, one noise tensor without the other and rng_seed == 0 without noise; HPC_ERR_UNSUPPORTED for K > 15,
+ * V % 8 != 0, V >= 2^20 and more than 65535 rows. */
+int64_t hpc_speculative_verify_workspace_bytes(int batch_size, int num_draft, int vocab_size);
+int hpc_speculative_verify_async(void* output_token_ids, void* num_accepted, void* workspace, const void* logits,
+                                 int logits_dtype, int64_t logits_row_stride, const void* draft_token_ids,
+                                 const void* temperature, float temperature_val, const void* uniform_samples,
+                                 const void* gumbel_noise, int batch_size, int num_draft, int vocab_size,
+                                 uint64_t rng_seed, hpc_stream_t stream);
+
 /* ---- communicator: socket rendezvous + symmetric device buffers (HIP IPC over xGMI) ---------------
  * reference: src/communicator/{communicator,channel,listener,connector,protocol}.cc (rank-0 star over
  *            an abstract unix socket "unix://name" / bare name, or "tcp://ip:port"),

@@ -7,6 +7,7 @@
 // Both forms are HBM-bound.  A 16-byte vector of bf16 is 8 columns, so 16 consecutive lanes - one DPP row - own one
 // 128-column block and its abs-max is four steps inside the row (block128_amax).
 #include "act_quant.h"
+#include "rmsnorm_row.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
@@ -117,8 +118,7 @@ int launch_quant(const void* in, void* out, float* out_scale, int64_t chunks, hi
 }
 
 // ---- residual add + RMSNorm + quant ----------------------------------------------------------------------------------
-// The row layout of rmsnorm.hip's rmsnorm_scale_kernel: kTPR threads cooperate on one row (kTPR in {64,128,256}), kNV
-// 16-byte vectors per thread stay in registers, vector i of thread t is vector t + i * kTPR of the row.  kTPR % 16 == 0
+// The row layout is rmsnorm.hip's rmsnorm_scale_kernel's (RowMap, rmsnorm_row.h), and so is the pass up to `rms`.  kTPR % 16 == 0
 // and H / 8 % 16 == 0, so the 16 lanes of a group hold one 128-column block in every i and are in range together.
 // kRes: h = bf16(x + residual) is stored back to residual and normed; kNormed: the bf16 y is stored too.  The codes
 // and scales are those of the bf16-ROUNDED y, i.e. of blockwise_quant_kernel on the normed output.
@@ -129,16 +129,14 @@ __global__ __launch_bounds__(256, (kNV >= 8 ? 4 : 1)) void rmsnorm_blockwise_qua
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, uint16_t* __restrict__ residual,
     uint8_t* __restrict__ out_fp8, float* __restrict__ out_scale, uint16_t* __restrict__ out_normed, float eps, int rows,
     int hidden) {
-  constexpr int kRowsPerBlock = 256 / kTPR;
   constexpr int kWavesPerRow = kTPR / kWave;
   __shared__ float red[4];
 
   const int tid = threadIdx.x;
-  const int row_in_block = tid / kTPR;
-  const int t = tid % kTPR;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kRowsPerBlock + row_in_block;
-  const bool row_ok = row < rows;
-  const int nvec = hidden >> 3;
+  const RowMap<kTPR> m(rows, hidden);
+  const int t = m.t, nvec = m.nvec;
+  const int64_t row = m.row;
+  const bool row_ok = m.row_ok;
 
   u32x4 xv[kNV];
 #pragma unroll
@@ -212,7 +210,7 @@ __global__ __launch_bounds__(256, (kNV >= 8 ? 4 : 1)) void rmsnorm_blockwise_qua
 template <int kTPR, int kNV>
 int launch_norm(const void* x, const void* w, void* residual, void* o8, float* os, void* on, float eps, int rows,
                 int hidden, hipStream_t stream) {
-  constexpr int kRowsPerBlock = 256 / kTPR;
+  constexpr int kRowsPerBlock = RowMap<kTPR>::kRowsPerBlock;
   const int grid = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
 #define HPC_BQ_LAUNCH(RES, NORMED)                                                                               \
   rmsnorm_blockwise_quant_kernel<kTPR, kNV, RES, NORMED><<<grid, 256, 0, stream>>>(                              \
@@ -263,12 +261,7 @@ extern "C" int hpc_fused_rmsnorm_blockwise_quant_async(void* output_fp8, float* 
   const int nvec = hidden / 8;
 #define HPC_BQ_CASE(TPR, NV) \
   return launch_norm<TPR, NV>(input, weight, residual, output_fp8, output_scale, output_normed, eps, num_tokens, hidden, stream)
-  if (nvec <= 64) HPC_BQ_CASE(64, 1);
-  if (nvec <= 128) HPC_BQ_CASE(128, 1);
-  if (nvec <= 256) HPC_BQ_CASE(256, 1);
-  if (nvec <= 512) HPC_BQ_CASE(256, 2);
-  if (nvec <= 768) HPC_BQ_CASE(256, 3);
-  if (nvec <= 1024) HPC_BQ_CASE(256, 4);
-  HPC_BQ_CASE(256, 8);
+  HPC_RMS_LADDER(nvec, HPC_BQ_CASE);  // one case is taken: hidden <= 16384 above
 #undef HPC_BQ_CASE
+  return HPC_ERR_UNSUPPORTED;
 }

@@ -4,28 +4,26 @@
 // Replaces reference src/normalization/fused_rmsnorm_with_scale.cu:14-225 (kernel + launcher).
 // HBM-bound: one pass, 16-byte loads, row held in registers, wave64 shuffle
 // reduce + one LDS exchange between the waves that share a row.
-#include "hpc_common.h"
+#include "rmsnorm_row.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
 namespace {
 
-// kTPR threads cooperate on one row (kTPR in {64,128,256}); kNV 16-byte vectors per thread.
+// The row layout (kTPR threads per row, kNV 16-byte vectors per thread): RowMap, rmsnorm_row.h.
 template <int kTPR, int kNV, bool kMoe>
 __global__ __launch_bounds__(256) void rmsnorm_scale_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, uint8_t* __restrict__ out_fp8,
     float* __restrict__ out_f32, uint8_t* __restrict__ out_fp8_2, const float* __restrict__ scale,
     float eps, int rows, int hidden) {
-  constexpr int kRowsPerBlock = 256 / kTPR;
   constexpr int kWavesPerRow = kTPR / kWave;
   __shared__ float red[4];
 
   const int tid = threadIdx.x;
-  const int row_in_block = tid / kTPR;
-  const int t = tid % kTPR;
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kRowsPerBlock + row_in_block;
-  const bool row_ok = row < rows;
-  const int nvec = hidden >> 3;
+  const RowMap<kTPR> m(rows, hidden);
+  const int t = m.t, nvec = m.nvec;
+  const int64_t row = m.row;
+  const bool row_ok = m.row_ok;
 
   u32x4 xv[kNV];
   float ss = 0.f;
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(256) void rmsnorm_scale_kernel(
 template <int kTPR, int kNV>
 int launch(const void* x, const void* w, void* o8, void* of, void* o8b, const void* scale,
            float eps, int rows, int hidden, bool moe, hipStream_t stream) {
-  constexpr int kRowsPerBlock = 256 / kTPR;
+  constexpr int kRowsPerBlock = RowMap<kTPR>::kRowsPerBlock;
   const int grid = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
   if (moe) {
     rmsnorm_scale_kernel<kTPR, kNV, true><<<grid, 256, 0, stream>>>(
@@ -117,13 +115,7 @@ extern "C" int hpc_fused_rmsnorm_with_scale_async(const void* input, const void*
 #define HPC_RMS_CASE(TPR, NV)                                                                  \
   return launch<TPR, NV>(input, weight, output_fp8, output_fp32, output_fp8_scale2, scale, eps, \
                          batch_size, hidden_state, moe, stream)
-  if (nvec <= 64) HPC_RMS_CASE(64, 1);
-  if (nvec <= 128) HPC_RMS_CASE(128, 1);
-  if (nvec <= 256) HPC_RMS_CASE(256, 1);
-  if (nvec <= 512) HPC_RMS_CASE(256, 2);
-  if (nvec <= 768) HPC_RMS_CASE(256, 3);
-  if (nvec <= 1024) HPC_RMS_CASE(256, 4);
-  if (nvec <= 2048) HPC_RMS_CASE(256, 8);
+  HPC_RMS_LADDER(nvec, HPC_RMS_CASE);
 #undef HPC_RMS_CASE
   return HPC_ERR_UNSUPPORTED;
 }

@@ -20,8 +20,10 @@
 // The fast path (temperature only) is a two-step arg-max of logits / T + Gumbel noise.
 // Self-drawn noise: Philox-4x32-10 keyed by the caller's seed, counter = (token, row, launch offset).
 // Draft-token verification of a speculative step (hpc_speculative_verify_async) is the fast path's segment pass plus the
-// segment's softmax statistics, and a one-wave accept scan per request.
-#include "hpc_common.h"
+// segment's softmax statistics, and a one-wave accept scan per request.  Both passes score a token with score_composite,
+// so speculative_verify returns bit for bit the token the fast path returns for the same row, noise and draft.
+// Ordered keys, (key, index) composites and the 64-bit wave operations: ordered_key.h.
+#include "ordered_key.h"
 #include "../../include/hpc_amd.h"
 
 #include <atomic>
@@ -63,13 +65,6 @@ struct Args {
   float* seg_stat;   // [B][S][2]: max, sum exp(x - max)   (softmax-before-topk only)
 };
 
-__device__ __forceinline__ uint32_t key_of(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float val_of(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 __device__ __forceinline__ uint64_t comp_of(uint32_t key, uint32_t idx) {
   return (static_cast<uint64_t>(key) << kIdxBits) | (kIdxMask - idx);
 }
@@ -102,6 +97,16 @@ __device__ __forceinline__ float load_logit(const Args& a, int b, int i) {
   if (a.dtype == 0) return static_cast<const float*>(a.logits)[static_cast<long>(b) * a.row_stride + i];
   const uint16_t h = static_cast<const uint16_t*>(a.logits)[static_cast<long>(b) * a.row_stride + i];
   return __uint_as_float(static_cast<uint32_t>(h) << 16);
+}
+
+// The fast path's score of token i of row `row` as a composite: x = logit / T (the logit itself when greedy), the row's
+// draft at -inf, plus Gumbel noise unless greedy.  temperature_segment_kernel and verify_segment_kernel both take their
+// arg-max over THIS function, which is what makes speculative_verify return exactly the token that
+// fused_sampler_temperature_sample(..., draft_token_ids = d) returns.
+__device__ __forceinline__ void score_composite(const Args& a, int row, int i, float x, bool is_draft, bool greedy, uint64_t& c) {
+  if (is_draft) x = kNegInf;
+  if (!greedy) x += a.noise ? a.noise[static_cast<long>(row) * a.V + i] : own_gumbel(a, row, i);
+  c = composite_of(ieee_key(x), static_cast<uint32_t>(i));
 }
 
 // ---- byte-wise radix select: the K-th largest of n distinct composites in `list` (LDS) ---------------
@@ -179,14 +184,14 @@ __global__ __launch_bounds__(kThreads) void sampler_segment_kernel(const Args a)
       float x = load_logit(a, b, i);
       if (has_rp && ((mrow[i >> 3] >> (i & 7)) & 1)) x = x > 0.f ? x * inv_rp : x * rp;
       if (temp > 0.f) x = x / temp;
-      key[j] = key_of(x);
+      key[j] = ieee_key(x);
       best = max(best, key[j]);
     }
   }
 
   // softmax-before-topk statistics of the segment (max, sum exp(x - max))
   if (a.policy == 1) {
-    float m = best ? val_of(best) : kNegInf;
+    float m = best ? ieee_key_value(best) : kNegInf;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     if (lane == 0) s_red[wave] = m;
@@ -198,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void sampler_segment_kernel(const Args a)
     float e = 0.f;
 #pragma unroll
     for (int j = 0; j < kElems; ++j)
-      if (key[j]) e += expf(val_of(key[j]) - m_sub);
+      if (key[j]) e += expf(ieee_key_value(key[j]) - m_sub);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
     if (lane == 0) s_red[4 + wave] = e;
@@ -272,9 +277,7 @@ __global__ __launch_bounds__(kThreads) void sampler_final_kernel(const Args a) {
   for (int k = 2; k <= 64; k <<= 1)
 #pragma unroll
     for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint32_t lo = __shfl_xor(static_cast<uint32_t>(c), j, 64);
-      const uint32_t hi = __shfl_xor(static_cast<uint32_t>(c >> 32), j, 64);
-      const uint64_t o = (static_cast<uint64_t>(hi) << 32) | lo;
+      const uint64_t o = shfl_xor_u64(c, j);
       const bool up = (lane & k) != 0;       // this block sorts ascending
       const bool lower = (lane & j) == 0;    // lane holds the lower position of the pair
       const bool take_max = (lower != up);   // descending blocks keep the max in the lower lane
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void sampler_final_kernel(const Args a) {
   const uint32_t key = static_cast<uint32_t>(c >> kIdxBits);
   const int tok = static_cast<int>(kIdxMask - (c & kIdxMask));
   const bool real = key != 0;
-  const float x = real ? val_of(key) : kNegInf;
+  const float x = real ? ieee_key_value(key) : kNegInf;
 
   int kb = a.topk_ptr ? (a.topk_bytes == 8 ? static_cast<int>(static_cast<const int64_t*>(a.topk_ptr)[b])
                                            : static_cast<const int*>(a.topk_ptr)[b])
@@ -344,7 +347,7 @@ __global__ __launch_bounds__(kThreads) void sampler_final_kernel(const Args a) {
 }
 
 // ---- temperature-only fast path: argmax(logits / T + gumbel) ---------------------------------------------
-// composite = key(score) << 32 | ~index  -> max picks the highest score, first index on ties
+// The wave maxima of these two kernels are wave_max_u64 spelled out: as a call the registers are allocated differently.
 __global__ __launch_bounds__(kThreads) void temperature_segment_kernel(const Args a) {
   __shared__ uint64_t s_red[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -354,10 +357,8 @@ __global__ __launch_bounds__(kThreads) void temperature_segment_kernel(const Arg
   const int64_t dr = a.draft ? a.draft[b] : -1;
   uint64_t best = 0;
   for (int i = i0 + tid; i < i1; i += kThreads) {
-    float x = load_logit(a, b, i) / temp;
-    if (static_cast<int64_t>(i) == dr) x = kNegInf;
-    x += a.noise ? a.noise[static_cast<long>(b) * a.V + i] : own_gumbel(a, b, i);
-    const uint64_t c = (static_cast<uint64_t>(key_of(x)) << 32) | (0xffffffffu - static_cast<uint32_t>(i));
+    uint64_t c;
+    score_composite(a, b, i, load_logit(a, b, i) / temp, static_cast<int64_t>(i) == dr, false, c);
     best = c > best ? c : best;
   }
 #pragma unroll
@@ -390,12 +391,12 @@ __global__ __launch_bounds__(64) void temperature_final_kernel(const Args a) {
     const uint64_t v = (static_cast<uint64_t>(hi) << 32) | lo;
     best = v > best ? v : best;
   }
-  if (lane == 0) a.out[b] = static_cast<int>(0xffffffffu - static_cast<uint32_t>(best));
+  if (lane == 0) a.out[b] = static_cast<int>(index_of(best));
 }
 
 // ---- draft-token verification of a speculative decode step (ours: no reference counterpart) -------------------------
 // Rows are positions: row r = b * (K + 1) + j is position j of request b, and the temperature is per REQUEST.  Phase 1 is
-// the fast path's segment pass - the same composite of the same expression x / T + noise, the row's draft at -inf - that
+// the fast path's segment pass - score_composite of x / T, the row's draft masked - that
 // also keeps the segment's softmax statistics of x / T and the scaled logit at the draft; phase 2, one wave per request,
 // folds the segments of every position, forms p = softmax(x / T)[draft] and finds the first rejection.  No atomics, no
 // scratch, LDS only for the cross-wave reduction.
@@ -418,11 +419,6 @@ __device__ __forceinline__ float own_uniform(const Args& a, int r) {
   const uint32_t w = philox_word0(a.seed, 0xffffffffu, static_cast<uint32_t>(r), static_cast<uint32_t>(a.offset),
                                   static_cast<uint32_t>(a.offset >> 32));
   return static_cast<float>(w >> 8) * (1.0f / 16777216.0f);  // [0, 1)
-}
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
-  const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), o, 64);
-  const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), o, 64);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 // (m, s) <- the softmax statistics of the union of two sets; an empty set is (-inf, 0)
 __device__ __forceinline__ void stat_merge(float& m, float& s, float m2, float s2) {
@@ -480,13 +476,13 @@ __global__ __launch_bounds__(kThreads) void verify_segment_kernel(const VerifyAr
     xs[e] = i < i1 ? x : kNegInf;
     if (i < i1) {
       m = fmaxf(m, x);
-      if (static_cast<int64_t>(i) == dr) {
+      const bool is_draft = static_cast<int64_t>(i) == dr;
+      if (is_draft) {
         xd = x;
         owns = true;
-        x = kNegInf;
       }
-      if (!greedy) x += a.noise ? a.noise[static_cast<long>(r) * a.V + i] : own_gumbel(a, r, i);
-      const uint64_t c = (static_cast<uint64_t>(key_of(x)) << 32) | (0xffffffffu - static_cast<uint32_t>(i));
+      uint64_t c;
+      score_composite(a, r, i, x, is_draft, greedy, c);
       best = c > best ? c : best;
     }
   }
@@ -559,7 +555,7 @@ __global__ __launch_bounds__(64) void verify_final_kernel(const VerifyArgs v) {
   if (live && d >= 0) {
     const float xd = v.xd[r];
     if (greedy) {  // d is the arg-max iff its composite beats the best of the others
-      accept = ((static_cast<uint64_t>(key_of(xd)) << 32) | (0xffffffffu - static_cast<uint32_t>(d))) > best;
+      accept = composite_of(ieee_key(xd), static_cast<uint32_t>(d)) > best;
     } else {
       const float p = __expf(xd - m) / sum;
       const float u = v.uniform ? v.uniform[static_cast<long>(b) * K + j] : own_uniform(a, r);
@@ -571,7 +567,7 @@ __global__ __launch_bounds__(64) void verify_final_kernel(const VerifyArgs v) {
   const int jr = __builtin_ctzll(~__ballot(accept) & kHeads) >> 2;
   if (sub == 0 && j <= K) {
     int* out = a.out + static_cast<long>(b) * (K + 1);
-    out[j] = j < jr ? static_cast<int>(d) : (j == jr ? static_cast<int>(0xffffffffu - static_cast<uint32_t>(best)) : -1);
+    out[j] = j < jr ? static_cast<int>(d) : (j == jr ? static_cast<int>(index_of(best)) : -1);
   }
   if (lane == 0) v.num_accepted[b] = jr;
 }
@@ -583,6 +579,35 @@ inline uint64_t next_offset() { return g_launch_offset.fetch_add(128, std::memor
 inline int segments_of(int V) {
   const int s = (V + kSegMax - 1) / kSegMax;
   return s < 16 ? 16 : s;
+}
+
+// The refusals the fast path and verification share, wrong arguments (INVALID) before the sizes the kernels do not cover (UNSUPPORTED:
+// a vocabulary that is no multiple of 8 or has token ids of 2^20 and up, more logits rows than a grid's y extent).
+inline int check_common(bool pointers, int dtype, int64_t rows, int V) {
+  if (!pointers) return HPC_ERR_INVALID;
+  if (rows < 0 || V <= 0 || (dtype != 0 && dtype != 1)) return HPC_ERR_INVALID;
+  if ((V & 7) || V >= (1 << kIdxBits)) return HPC_ERR_UNSUPPORTED;
+  if (rows > 65535) return HPC_ERR_UNSUPPORTED;
+  return HPC_OK;
+}
+
+// The part of Args every entry fills.  A segment is ceil(V / S) elements rounded up to seg_round: kThreads for the top-k
+// path (its threads stride the segment), 1 for the fast path and verification (<= kSegMax, the kElems registers of a thread).
+inline void fill_common(Args& a, const void* logits, int dtype, int64_t row_stride, int rows, int V, int seg_round,
+                        const void* temp_arr, float temp_val, const void* gumbel_noise, uint64_t seed, void* out) {
+  a.logits = logits;
+  a.dtype = dtype;
+  a.row_stride = row_stride;
+  a.B = rows;
+  a.V = V;
+  a.S = segments_of(V);
+  a.seg = ((V + a.S - 1) / a.S + seg_round - 1) / seg_round * seg_round;
+  a.t_arr = static_cast<const float*>(temp_arr);
+  a.t_val = temp_val;
+  a.noise = static_cast<const float*>(gumbel_noise);
+  a.seed = seed;
+  a.offset = gumbel_noise ? 0 : next_offset();
+  a.out = static_cast<int*>(out);
 }
 
 }  // namespace sampler
@@ -604,6 +629,8 @@ extern "C" int hpc_fused_sampler_async(
     const void* topp_arr, float topp_val, const void* gumbel_noise, int batch_size, int vocab_size,
     int64_t logits_row_stride, int max_topk, uint64_t rng_seed, hipStream_t stream) {
   using namespace hpc::sampler;
+  // check_common's checks in this entry's own order (the dtype after the vocabulary, the batch limit last): an input that
+  // is wrong in two ways keeps the code it has always got
   if (!token_ids || !workspace || !logits) return HPC_ERR_INVALID;
   if (batch_size < 0 || vocab_size <= 0 || (max_topk != 32 && max_topk != 64)) return HPC_ERR_INVALID;
   if (batch_size == 0) return HPC_OK;
@@ -612,32 +639,20 @@ extern "C" int hpc_fused_sampler_async(
   if (softmax_policy < 0 || softmax_policy > 2 || (logits_dtype != 0 && logits_dtype != 1)) return HPC_ERR_INVALID;
   if (batch_size > 65535) return HPC_ERR_UNSUPPORTED;
   Args a{};
-  a.logits = logits;
-  a.dtype = logits_dtype;
-  a.row_stride = logits_row_stride;
-  a.B = batch_size;
-  a.V = vocab_size;
-  a.S = segments_of(vocab_size);
-  a.seg = ((vocab_size + a.S - 1) / a.S + kThreads - 1) / kThreads * kThreads;
+  fill_common(a, logits, logits_dtype, logits_row_stride, batch_size, vocab_size, kThreads, temp_arr, temp_val, gumbel_noise,
+              rng_seed, token_ids);
   a.mask = static_cast<uint8_t*>(penalty_mask);
   a.mask_stride = penalty_mask_row_bytes;
   a.slot = static_cast<const int*>(slot_id);
   a.rp_arr = static_cast<const float*>(rp_arr);
   a.rp_val = rp_val;
-  a.t_arr = static_cast<const float*>(temp_arr);
-  a.t_val = temp_val;
   a.policy = softmax_policy;
   a.topk_ptr = topk_ptr;
   a.topk_bytes = topk_int_bytes;
   a.topk_val = topk_val;
   a.topp_arr = static_cast<const float*>(topp_arr);
   a.topp_val = topp_val;
-  a.noise = static_cast<const float*>(gumbel_noise);
-  a.draft = nullptr;
   a.max_topk = max_topk;
-  a.seed = rng_seed;
-  a.offset = gumbel_noise ? 0 : next_offset();
-  a.out = static_cast<int*>(token_ids);
   a.cand = static_cast<uint64_t*>(workspace);
   a.seg_stat = reinterpret_cast<float*>(a.cand + static_cast<int64_t>(batch_size) * a.S * max_topk);
   sampler_segment_kernel<<<dim3(a.S, batch_size), kThreads, 0, stream>>>(a);
@@ -656,26 +671,14 @@ extern "C" int hpc_fused_sampler_temperature_async(void* token_ids, void* worksp
                                                    int batch_size, int vocab_size, uint64_t rng_seed,
                                                    hipStream_t stream) {
   using namespace hpc::sampler;
-  if (!token_ids || !workspace || !logits) return HPC_ERR_INVALID;
-  if (batch_size < 0 || vocab_size <= 0 || (logits_dtype != 0 && logits_dtype != 1)) return HPC_ERR_INVALID;
-  if (batch_size == 0) return HPC_OK;
-  if ((vocab_size & 7) || vocab_size >= (1 << kIdxBits)) return HPC_ERR_UNSUPPORTED;
-  if (batch_size > 65535) return HPC_ERR_UNSUPPORTED;
+  const int rc = check_common(token_ids && workspace && logits, logits_dtype, batch_size, vocab_size);
+  if (rc == HPC_ERR_INVALID) return rc;
+  if (batch_size == 0) return HPC_OK;  // an empty batch is accepted ahead of the size limits
+  if (rc != HPC_OK) return rc;
   Args a{};
-  a.logits = logits;
-  a.dtype = logits_dtype;
-  a.row_stride = logits_row_stride;
-  a.B = batch_size;
-  a.V = vocab_size;
-  a.S = segments_of(vocab_size);
-  a.seg = (vocab_size + a.S - 1) / a.S;
-  a.t_arr = static_cast<const float*>(temp_arr);
-  a.t_val = temp_val;
-  a.noise = static_cast<const float*>(gumbel_noise);
+  fill_common(a, logits, logits_dtype, logits_row_stride, batch_size, vocab_size, 1, temp_arr, temp_val, gumbel_noise, rng_seed,
+              token_ids);
   a.draft = static_cast<const int64_t*>(draft_token_ids);
-  a.seed = rng_seed;
-  a.offset = gumbel_noise ? 0 : next_offset();
-  a.out = static_cast<int*>(token_ids);
   a.cand = static_cast<uint64_t*>(workspace);
   temperature_segment_kernel<<<dim3(a.S, batch_size), kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
@@ -698,33 +701,21 @@ extern "C" int hpc_speculative_verify_async(void* output_token_ids, void* num_ac
                                             const void* gumbel_noise, int batch_size, int num_draft, int vocab_size,
                                             uint64_t rng_seed, hipStream_t stream) {
   using namespace hpc::sampler;
-  if (!output_token_ids || !num_accepted || !workspace || !logits) return HPC_ERR_INVALID;
-  if (batch_size < 0 || num_draft < 0 || vocab_size <= 0 || (logits_dtype != 0 && logits_dtype != 1)) return HPC_ERR_INVALID;
+  if (batch_size < 0 || num_draft < 0) return HPC_ERR_INVALID;
+  const int64_t rows = static_cast<int64_t>(batch_size) * (num_draft + 1);
+  const int rc = check_common(output_token_ids && num_accepted && workspace && logits, logits_dtype, rows, vocab_size);
+  if (rc == HPC_ERR_INVALID) return rc;
   if (num_draft > 0 && !draft_token_ids) return HPC_ERR_INVALID;
   if (logits_row_stride < vocab_size) return HPC_ERR_INVALID;
   // no draft, no uniform: with num_draft == 0 uniform_samples is [batch_size, 0] and is not looked at
   if (num_draft > 0 && (uniform_samples == nullptr) != (gumbel_noise == nullptr)) return HPC_ERR_INVALID;
   if (!gumbel_noise && rng_seed == 0) return HPC_ERR_INVALID;
-  if (num_draft > 15) return HPC_ERR_UNSUPPORTED;
-  if ((vocab_size & 7) || vocab_size >= (1 << kIdxBits)) return HPC_ERR_UNSUPPORTED;
-  const int64_t rows = static_cast<int64_t>(batch_size) * (num_draft + 1);
-  if (rows > 65535) return HPC_ERR_UNSUPPORTED;
+  if (num_draft > 15 || rc != HPC_OK) return HPC_ERR_UNSUPPORTED;
   if (batch_size == 0) return HPC_OK;
   VerifyArgs v{};
   Args& a = v.a;
-  a.logits = logits;
-  a.dtype = logits_dtype;
-  a.row_stride = logits_row_stride;
-  a.B = static_cast<int>(rows);
-  a.V = vocab_size;
-  a.S = segments_of(vocab_size);
-  a.seg = (vocab_size + a.S - 1) / a.S;  // <= kSegMax: the segment pass keeps a thread's kElems elements in registers
-  a.t_arr = static_cast<const float*>(temperature);
-  a.t_val = temperature_val;
-  a.noise = static_cast<const float*>(gumbel_noise);
-  a.seed = rng_seed;
-  a.offset = gumbel_noise ? 0 : next_offset();
-  a.out = static_cast<int*>(output_token_ids);
+  fill_common(a, logits, logits_dtype, logits_row_stride, static_cast<int>(rows), vocab_size, 1, temperature, temperature_val,
+              gumbel_noise, rng_seed, output_token_ids);
   v.draft = static_cast<const int64_t*>(draft_token_ids);
   v.uniform = static_cast<const float*>(uniform_samples);
   v.K = num_draft;

@@ -24,7 +24,7 @@
 // sum of the group's two best c with a bias, its best c without), top-k on c among the experts that stay, weights
 // from the UNBIASED s, renormalised and scaled.  Same row-in-registers layout and the same composite-key rounds over
 // the experts; the groups are ranked by their composites (key of the score << 32 | ~group id) without rounds.
-#include "hpc_common.h"
+#include "ordered_key.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
@@ -34,25 +34,9 @@ constexpr int kThreads = 256;
 constexpr int kWavesPerBlock = kThreads / 64;
 constexpr int kMaxTopk = 64;
 
-// Order-preserving integer key with torch.topk's conventions: -0.0 and +0.0 are EQUAL (the tie goes to the smaller
-// expert id, like every other tie) and every NaN - whatever its sign bit - ranks above +inf.
-__device__ __forceinline__ uint32_t key_of(float x) {
-  uint32_t u = __float_as_uint(x + 0.0f);  // -0.0 + 0.0 = +0.0
-  if (x != x) u = 0x7fc00000u;             // canonical positive NaN
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotonic: larger float <-> larger key
-}
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), o, 64);
-    const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), o, 64);
-    const uint64_t other = (static_cast<uint64_t>(hi) << 32) | lo;
-    v = other > v ? other : v;
-  }
-  return v;
-}
-
+// Keys are torch_topk_key, composites and wave_max_u64 as in ordered_key.h.  The row load and the selection rounds are
+// written in both kernels below: as shared functions they compile to other listings (a branch the other way round in
+// the grouped kernel, other registers in this one), and the softmax kernel decodes its row maximum inside round 0.
 // kVec: float4 vectors per lane (experts <= 256 * kVec); element c of vector j of lane l is expert
 // 256 j + 4 l + c, so a wave reads whole 1 KB row segments.
 template <int kVec>
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void topk_router_kernel(const float* __re
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int e = 256 * j + 4 * lane + c;
-      comp[j][c] = e < num_expert ? (static_cast<uint64_t>(key_of(x[j][c])) << 32) | (0xffffffffu - e) : 0ull;
+      comp[j][c] = e < num_expert ? composite_of(torch_topk_key(x[j][c]), e) : 0ull;
     }
 
   uint64_t mine = 0;  // lane r keeps the winner of round r (two rounds per lane when topk > 64: not supported)
@@ -102,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void topk_router_kernel(const float* __re
 #pragma unroll
       for (int c = 0; c < 4; ++c) comp[j][c] = comp[j][c] == win ? 0ull : comp[j][c];  // composites are unique
     if (lane == r) mine = win;
-    if (r == 0) {
+    if (r == 0) {  // ieee_key_value, spelled out here and below: as a call it moves an instruction in the listing
       const uint32_t k32 = static_cast<uint32_t>(win >> 32);
       const uint32_t bits = (k32 & 0x80000000u) ? (k32 & 0x7fffffffu) : ~k32;
       row_max = __uint_as_float(bits);
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void topk_router_kernel(const float* __re
   float p = 0.f;
   int id = 0;
   if (lane < topk) {
-    id = static_cast<int>(0xffffffffu - static_cast<uint32_t>(mine));
+    id = static_cast<int>(index_of(mine));
     const uint32_t k32 = static_cast<uint32_t>(mine >> 32);
     const uint32_t bits = (k32 & 0x80000000u) ? (k32 & 0x7fffffffu) : ~k32;
     p = expf(__uint_as_float(bits) - row_max);
@@ -208,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void grouped_topk_router_kernel(
     for (int c = 0; c < 4; ++c) {
       const int e = 256 * j + 4 * lane + c;
       ch[j][c] = e < num_expert ? s[j][c] + b[j][c] : ninf;
-      comp[j][c] = e < num_expert ? (static_cast<uint64_t>(key_of(ch[j][c])) << 32) | (0xffffffffu - e) : 0ull;
+      comp[j][c] = e < num_expert ? composite_of(torch_topk_key(ch[j][c]), e) : 0ull;
     }
 
   if (select_groups) {
@@ -249,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void grouped_topk_router_kernel(
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
       const float score = bias ? m1[j] + m2[j] : m1[j];
-      gcomp[j] = gid[j] >= 0 ? (static_cast<uint64_t>(key_of(score)) << 32) | (0xffffffffu - gid[j]) : 0ull;
+      gcomp[j] = gid[j] >= 0 ? composite_of(torch_topk_key(score), gid[j]) : 0ull;
       beaten[j] = 0;
     }
     // a group stays when fewer than topk_group groups beat it (the composites of two groups differ).  Group g's
@@ -291,7 +275,7 @@ __global__ __launch_bounds__(kThreads) void grouped_topk_router_kernel(
     if (lane == r) mine = win;
   }
   // the winner's UNBIASED score, from the lane that holds it (a lane past topk asks lane 63 and drops the answer)
-  const uint32_t e = 0xffffffffu - static_cast<uint32_t>(mine);
+  const uint32_t e = 0xffffffffu - static_cast<uint32_t>(mine);  // index_of, spelled out: as a call the compares below compile differently
   const int owner = (e >> 2) & 63;
   float w = 0.f;
 #pragma unroll
@@ -308,6 +292,32 @@ __global__ __launch_bounds__(kThreads) void grouped_topk_router_kernel(
   }
 }
 
+// The refusals the two C entries share, wrong arguments (INVALID) before the limits of the row-in-registers layout
+// (UNSUPPORTED: 16-byte row segments, one winner per lane).
+inline int check_router(const void* topk_ids, const void* topk_scale, const float* logits, int num_tokens, int num_expert,
+                        int64_t ld_logits, int topk) {
+  if (!topk_ids || !topk_scale || !logits) return HPC_ERR_INVALID;
+  if (num_tokens < 0 || num_expert <= 0 || topk <= 0 || topk > num_expert) return HPC_ERR_INVALID;
+  if (topk > kMaxTopk || num_expert > 1024 || (num_expert & 3) || (ld_logits & 3) || ld_logits < num_expert)
+    return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(logits) & 15) != 0) return HPC_ERR_UNSUPPORTED;
+  return HPC_OK;
+}
+
+// LAUNCH(kVec) with the float4 vectors per lane that num_expert needs; `grid` is one wave per token row
+#define HPC_ROUTER_LADDER(num_tokens, num_expert, LAUNCH)                  \
+  do {                                                                     \
+    const int grid = ((num_tokens) + kWavesPerBlock - 1) / kWavesPerBlock; \
+    const int vec = ((num_expert) + 255) / 256;                            \
+    if (vec == 1) {                                                        \
+      LAUNCH(1);                                                           \
+    } else if (vec == 2) {                                                 \
+      LAUNCH(2);                                                           \
+    } else {                                                               \
+      LAUNCH(4);                                                           \
+    }                                                                      \
+  } while (0)
+
 }  // namespace router
 }  // namespace hpc
 
@@ -315,24 +325,12 @@ extern "C" int hpc_topk_router_async(int* topk_ids, float* topk_scale, const flo
                                      int num_expert, int64_t ld_logits, int topk, int renormalize,
                                      hipStream_t stream) {
   using namespace hpc::router;
-  if (!topk_ids || !topk_scale || !logits) return HPC_ERR_INVALID;
-  if (num_tokens < 0 || num_expert <= 0 || topk <= 0 || topk > num_expert) return HPC_ERR_INVALID;
-  if (topk > kMaxTopk || num_expert > 1024 || (num_expert & 3) || (ld_logits & 3) || ld_logits < num_expert)
-    return HPC_ERR_UNSUPPORTED;  // 16-byte row segments; one winner per lane
-  if ((reinterpret_cast<uintptr_t>(logits) & 15) != 0) return HPC_ERR_UNSUPPORTED;
-  if (num_tokens == 0) return HPC_OK;
-  const int grid = (num_tokens + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int vec = (num_expert + 255) / 256;
+  const int rc = check_router(topk_ids, topk_scale, logits, num_tokens, num_expert, ld_logits, topk);
+  if (rc != HPC_OK || num_tokens == 0) return rc;
 #define HPC_ROUTER_LAUNCH(V)                                                                              \
   topk_router_kernel<V><<<grid, kThreads, 0, stream>>>(logits, topk_ids, topk_scale, num_tokens, num_expert, \
                                                        ld_logits, topk, renormalize)
-  if (vec == 1) {
-    HPC_ROUTER_LAUNCH(1);
-  } else if (vec == 2) {
-    HPC_ROUTER_LAUNCH(2);
-  } else {
-    HPC_ROUTER_LAUNCH(4);
-  }
+  HPC_ROUTER_LADDER(num_tokens, num_expert, HPC_ROUTER_LAUNCH);
 #undef HPC_ROUTER_LAUNCH
   HPC_CHECK_LAUNCH();
   return HPC_OK;
@@ -344,19 +342,17 @@ extern "C" int hpc_grouped_topk_router_async(int* topk_ids, float* topk_scale, c
                                              int scoring_func, int renormalize, float routed_scaling_factor,
                                              hipStream_t stream) {
   using namespace hpc::router;
-  if (!topk_ids || !topk_scale || !logits) return HPC_ERR_INVALID;
-  if (num_tokens < 0 || topk < 1 || num_expert_group < 1 || topk_group < 1) return HPC_ERR_INVALID;
-  if (topk_group > num_expert_group || topk > num_expert || (scoring_func != 0 && scoring_func != 1)) return HPC_ERR_INVALID;
+  // this entry's own wrong arguments go before the layout limits of either
+  const int rc = check_router(topk_ids, topk_scale, logits, num_tokens, num_expert, ld_logits, topk);
+  if (rc == HPC_ERR_INVALID) return rc;
+  if (num_expert_group < 1 || topk_group < 1 || topk_group > num_expert_group || (scoring_func != 0 && scoring_func != 1))
+    return HPC_ERR_INVALID;
   if (num_expert % num_expert_group != 0) return HPC_ERR_INVALID;
   const int group_size = num_expert / num_expert_group;
-  if (num_expert > 1024 || (num_expert & 3) || (group_size & 3) || topk > kMaxTopk) return HPC_ERR_UNSUPPORTED;
+  if (rc != HPC_OK || (group_size & 3)) return HPC_ERR_UNSUPPORTED;
   if (topk > static_cast<int64_t>(topk_group) * group_size) return HPC_ERR_UNSUPPORTED;  // not enough candidates
-  if ((ld_logits & 3) || ld_logits < num_expert) return HPC_ERR_UNSUPPORTED;  // 16-byte row segments
-  if ((reinterpret_cast<uintptr_t>(logits) & 15) != 0 || (reinterpret_cast<uintptr_t>(correction_bias) & 15) != 0)
-    return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(correction_bias) & 15) != 0) return HPC_ERR_UNSUPPORTED;
   if (num_tokens == 0) return HPC_OK;
-  const int grid = (num_tokens + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int vec = (num_expert + 255) / 256;
   // a group that is an aligned power-of-two run of lanes of one vector: 4, 8, ... 256 experts
   const int lanes = group_size / 4;
   const int group_lanes = (group_size <= 256 && (lanes & (lanes - 1)) == 0) ? lanes : 0;
@@ -365,13 +361,7 @@ extern "C" int hpc_grouped_topk_router_async(int* topk_ids, float* topk_scale, c
   grouped_topk_router_kernel<V><<<grid, kThreads, 0, stream>>>(                                                      \
       logits, correction_bias, topk_ids, topk_scale, num_tokens, num_expert, ld_logits, topk, num_expert_group,     \
       topk_group, group_size, group_lanes, select_groups, scoring_func, renormalize, routed_scaling_factor)
-  if (vec == 1) {
-    HPC_ROUTER_LAUNCH(1);
-  } else if (vec == 2) {
-    HPC_ROUTER_LAUNCH(2);
-  } else {
-    HPC_ROUTER_LAUNCH(4);
-  }
+  HPC_ROUTER_LADDER(num_tokens, num_expert, HPC_ROUTER_LAUNCH);
 #undef HPC_ROUTER_LAUNCH
   HPC_CHECK_LAUNCH();
   return HPC_OK;

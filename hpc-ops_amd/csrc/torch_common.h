@@ -40,6 +40,67 @@ inline void cuda_contig(const at::Tensor& t, const char* name) {
 }
 inline int i32(int64_t v) { return static_cast<int>(v); }
 
+const auto kF8 = at::kFloat8_e4m3fn;
+
+// An output given by the caller, or a fresh one on `like`'s device: dtype, device, contiguity and shape are checked either
+// way.  off_device: the message's words for a tensor elsewhere, which name `like` as its op does.  An int32 output is
+// named the way speculative_verify's always were, every other dtype by its ATen name.
+constexpr const char* kOnLogitsDevice = " must be on the logits' device";
+constexpr const char* kOnInputDevice = " must be on the input's device";
+inline at::Tensor out_or_new(const c10::optional<at::Tensor>& given, const at::Tensor& like, at::IntArrayRef shape,
+                             at::ScalarType dtype, const char* name, const char* off_device) {
+  if (!given.has_value()) return at::empty(shape, like.options().dtype(dtype));
+  const at::Tensor& o = *given;
+  TORCH_CHECK(o.is_cuda() && o.device() == like.device(), name, off_device);
+  if (dtype == at::kInt) {
+    TORCH_CHECK(o.scalar_type() == dtype, name, " dtype must be int32");
+  } else {
+    TORCH_CHECK(o.scalar_type() == dtype, name, " dtype must be ", dtype);
+  }
+  TORCH_CHECK(o.is_contiguous() && o.sizes() == shape, name, " must be a contiguous tensor of shape ", shape);
+  return o;
+}
+
+// ---- argument checks of the ops that take [rows, vocab] logits (fused samplers, speculative_verify) ------------------
+// Messages as in the reference (src/sampler/entry.cc:13-255).  The stricter forms are speculative_verify's: a vocabulary
+// that is not empty, and optional tensors on the logits' device (same_device_as).
+struct LogitsDims {
+  int64_t b, v;
+};
+inline LogitsDims check_logits(const at::Tensor& logits, const char* who, bool nonempty_vocab = false) {
+  TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
+  TORCH_CHECK(logits.dim() == 2, "logits tensor must be dim == 2");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "logits dtype must be float32 or bfloat16");
+  const int64_t b = logits.size(0), v = logits.size(1);
+  TORCH_CHECK(logits.stride(1) == 1, who, ": logits must have contiguous inner dim (stride(1)=1), got stride(1)=", logits.stride(1));
+  TORCH_CHECK(logits.stride(0) >= v, who, ": logits stride(0)=", logits.stride(0), " must be >= vocab_size=", v);
+  TORCH_CHECK((v > 0 || !nonempty_vocab) && v % 8 == 0 && v < (1 << 20), who, ": unsupported vocab_size ", v,
+              " (must be a multiple of 8, < 2^20)");
+  return {b, v};
+}
+inline void check_same_device(const at::Tensor& t, const char* name, const at::Tensor* same_device_as) {
+  if (same_device_as) {
+    TORCH_CHECK(t.is_cuda() && t.device() == same_device_as->device(), name, kOnLogitsDevice);
+  }
+}
+inline void check_1d_float(const c10::optional<at::Tensor>& t, const char* name, int64_t b,
+                           const at::Tensor* same_device_as = nullptr) {
+  if (!t.has_value()) return;
+  check_same_device(*t, name, same_device_as);
+  TORCH_CHECK(t->is_contiguous(), name, " tensor must be contiguous");
+  TORCH_CHECK(t->scalar_type() == at::kFloat, name, " dtype must be float32");
+  TORCH_CHECK(t->dim() == 1, name, " tensor must be 1D");
+  TORCH_CHECK(t->size(0) == b, name, " size must be [batch_size=", b, "], got [", t->size(0), "]");
+}
+inline void check_noise(const c10::optional<at::Tensor>& g, int64_t b, int64_t v, const at::Tensor* same_device_as = nullptr) {
+  if (!g.has_value()) return;
+  check_same_device(*g, "gumbel_noise", same_device_as);
+  TORCH_CHECK(g->is_contiguous(), "gumbel_noise tensor must be contiguous");
+  TORCH_CHECK(g->scalar_type() == at::kFloat, "gumbel_noise dtype must be float32");
+  TORCH_CHECK(g->dim() == 2, "gumbel_noise must be 2D");
+  TORCH_CHECK(g->size(0) == b && g->size(1) == v, "gumbel_noise shape must be [", b, ", ", v, "]");
+}
+
 // ---- zero-once scratch --------------------------------------------------------------------------------------------
 // Some kernels keep arrival counters in caller scratch that must be ZERO the first time a buffer is used and that
 // every call leaves zero again (decode: the counters of split requests; router GEMM: its split-K tickets).  Instead of

@@ -14,8 +14,6 @@ using namespace hpc_torch;
 
 namespace {
 
-const auto kF8 = at::kFloat8_e4m3fn;
-
 // ---- router GEMM (reference gemm_bf16xfp32_entry, src/gemm/sm90/entry.cc:86-147) ------------------------------------
 at::Tensor gemm_bf16xfp32(const at::Tensor& x, const at::Tensor& w_high, const at::Tensor& w_low, double scale, bool use_fp32_output,
                           bool use_splitk, const c10::optional<at::Tensor>& split_flag) {
@@ -61,10 +59,14 @@ at::Tensor gemm_bf16xfp32(const at::Tensor& x, const at::Tensor& w_high, const a
   return y;
 }
 
-// ---- fused softmax + top-k router (no reference op: pinned to stable torch semantics, oracle/router.py) ----------------
-std::tuple<at::Tensor, at::Tensor> topk_router(const at::Tensor& logits, int64_t topk, bool renormalize,
-                                               const c10::optional<at::Tensor>& topk_ids_in,
-                                               const c10::optional<at::Tensor>& topk_scale_in) {
+// ---- the two top-k routers (no reference op) ------------------------------------------------------------------------
+// what both check of the logits and of topk, and their two outputs, given or new
+struct RouterIo {
+  int64_t m, n;
+  at::Tensor ids, sc;
+};
+RouterIo router_io(const at::Tensor& logits, int64_t topk, const c10::optional<at::Tensor>& topk_ids_in,
+                   const c10::optional<at::Tensor>& topk_scale_in) {
   TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
   TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32 (the router GEMM's fp32 output)");
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [num_tokens, num_expert] with unit expert stride");
@@ -79,33 +81,35 @@ std::tuple<at::Tensor, at::Tensor> topk_router(const at::Tensor& logits, int64_t
               "topk_ids must be a contiguous int32 [num_tokens, topk] tensor");
   TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == m && sc.size(1) == topk,
               "topk_scale must be a contiguous float32 [num_tokens, topk] tensor");
-  const int rc = hpc_topk_router_async(static_cast<int*>(ids.data_ptr()), static_cast<float*>(sc.data_ptr()),
-                                       static_cast<const float*>(logits.data_ptr()), i32(m), i32(n), logits.stride(0), i32(topk),
-                                       renormalize ? 1 : 0, stream_of(logits));
-  HPC_LAUNCH_CHECK(rc, "topk_router");
-  return std::make_tuple(ids, sc);
+  return {m, n, ids, sc};
 }
 
-// ---- group-limited top-k router (no reference op: pinned to the PyTorch statement tests/grouped_router_ref.py) --------
+// fused softmax + top-k router: pinned to stable torch semantics, oracle/router.py
+std::tuple<at::Tensor, at::Tensor> topk_router(const at::Tensor& logits, int64_t topk, bool renormalize,
+                                               const c10::optional<at::Tensor>& topk_ids_in,
+                                               const c10::optional<at::Tensor>& topk_scale_in) {
+  const RouterIo io = router_io(logits, topk, topk_ids_in, topk_scale_in);
+  const int rc = hpc_topk_router_async(static_cast<int*>(io.ids.data_ptr()), static_cast<float*>(io.sc.data_ptr()),
+                                       static_cast<const float*>(logits.data_ptr()), i32(io.m), i32(io.n), logits.stride(0),
+                                       i32(topk), renormalize ? 1 : 0, stream_of(logits));
+  HPC_LAUNCH_CHECK(rc, "topk_router");
+  return std::make_tuple(io.ids, io.sc);
+}
+
+// group-limited top-k router: pinned to the PyTorch statement tests/grouped_router_ref.py
 std::tuple<at::Tensor, at::Tensor> grouped_topk_router(const at::Tensor& logits, const c10::optional<at::Tensor>& correction_bias,
                                                        int64_t topk, int64_t num_expert_group, int64_t topk_group,
                                                        c10::string_view scoring_func, bool renormalize, double routed_scaling_factor,
                                                        const c10::optional<at::Tensor>& topk_ids_in,
                                                        const c10::optional<at::Tensor>& topk_scale_in) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32 (the router GEMM's fp32 output)");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [num_tokens, num_expert] with unit expert stride");
-  const int64_t m = logits.size(0), n = logits.size(1);
-  TORCH_CHECK(n % 4 == 0 && n <= 1024, "num_expert must be a multiple of 4 and <= 1024");
+  const RouterIo io = router_io(logits, topk, topk_ids_in, topk_scale_in);
+  const int64_t n = io.n;
   TORCH_CHECK(scoring_func == "sigmoid" || scoring_func == "softmax", "scoring_func must be \"sigmoid\" or \"softmax\"");
   TORCH_CHECK(1 <= num_expert_group && 1 <= topk_group && topk_group <= num_expert_group,
               "topk_group must be in 1..num_expert_group");
   TORCH_CHECK(n % num_expert_group == 0 && (n / num_expert_group) % 4 == 0,
               "num_expert must split into num_expert_group groups of a multiple of 4 experts");
-  TORCH_CHECK(1 <= topk && topk <= std::min<int64_t>(n, 64), "topk must be in 1..min(num_expert, 64)");
   TORCH_CHECK(topk <= topk_group * (n / num_expert_group), "topk must not exceed the experts of topk_group groups");
-  TORCH_CHECK(logits.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "logits rows must be 16-byte aligned");
   const float* bias = nullptr;
   if (correction_bias.has_value()) {
     const at::Tensor& cb = *correction_bias;
@@ -115,18 +119,12 @@ std::tuple<at::Tensor, at::Tensor> grouped_topk_router(const at::Tensor& logits,
     TORCH_CHECK(reinterpret_cast<uintptr_t>(cb.data_ptr()) % 16 == 0, "correction_bias must be 16-byte aligned");
     bias = static_cast<const float*>(cb.data_ptr());
   }
-  at::Tensor ids = topk_ids_in.has_value() ? *topk_ids_in : at::empty({m, topk}, logits.options().dtype(at::kInt));
-  at::Tensor sc = topk_scale_in.has_value() ? *topk_scale_in : at::empty({m, topk}, logits.options());
-  TORCH_CHECK(ids.scalar_type() == at::kInt && ids.is_contiguous() && ids.dim() == 2 && ids.size(0) == m && ids.size(1) == topk,
-              "topk_ids must be a contiguous int32 [num_tokens, topk] tensor");
-  TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == m && sc.size(1) == topk,
-              "topk_scale must be a contiguous float32 [num_tokens, topk] tensor");
-  const int rc = hpc_grouped_topk_router_async(static_cast<int*>(ids.data_ptr()), static_cast<float*>(sc.data_ptr()),
-                                               static_cast<const float*>(logits.data_ptr()), bias, i32(m), i32(n), logits.stride(0),
+  const int rc = hpc_grouped_topk_router_async(static_cast<int*>(io.ids.data_ptr()), static_cast<float*>(io.sc.data_ptr()),
+                                               static_cast<const float*>(logits.data_ptr()), bias, i32(io.m), i32(n), logits.stride(0),
                                                i32(topk), i32(num_expert_group), i32(topk_group), scoring_func == "sigmoid" ? 1 : 0,
                                                renormalize ? 1 : 0, static_cast<float>(routed_scaling_factor), stream_of(logits));
   HPC_LAUNCH_CHECK(rc, "grouped_topk_router");
-  return std::make_tuple(ids, sc);
+  return std::make_tuple(io.ids, io.sc);
 }
 
 // ---- RoPE + QK-norm + paged KV store (reference src/rope/entry.cc:14-222) ---------------------------------------------
@@ -243,34 +241,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> rope_norm_store_kv_fp8(
 }
 
 // ---- fused samplers (reference src/sampler/entry.cc:13-255) -----------------------------------------------------------
-struct LogitsDims {
-  int64_t b, v;
-};
-LogitsDims check_logits(const at::Tensor& logits, const char* who) {
-  TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
-  TORCH_CHECK(logits.dim() == 2, "logits tensor must be dim == 2");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "logits dtype must be float32 or bfloat16");
-  const int64_t b = logits.size(0), v = logits.size(1);
-  TORCH_CHECK(logits.stride(1) == 1, who, ": logits must have contiguous inner dim (stride(1)=1), got stride(1)=", logits.stride(1));
-  TORCH_CHECK(logits.stride(0) >= v, who, ": logits stride(0)=", logits.stride(0), " must be >= vocab_size=", v);
-  TORCH_CHECK(v % 8 == 0 && v < (1 << 20), who, ": unsupported vocab_size ", v, " (must be a multiple of 8, < 2^20)");
-  return {b, v};
-}
-void check_1d_float(const c10::optional<at::Tensor>& t, const char* name, int64_t b) {
-  if (!t.has_value()) return;
-  TORCH_CHECK(t->is_contiguous(), name, " tensor must be contiguous");
-  TORCH_CHECK(t->scalar_type() == at::kFloat, name, " dtype must be float32");
-  TORCH_CHECK(t->dim() == 1, name, " tensor must be 1D");
-  TORCH_CHECK(t->size(0) == b, name, " size must be [batch_size=", b, "], got [", t->size(0), "]");
-}
-void check_noise(const c10::optional<at::Tensor>& g, int64_t b, int64_t v) {
-  if (!g.has_value()) return;
-  TORCH_CHECK(g->is_contiguous(), "gumbel_noise tensor must be contiguous");
-  TORCH_CHECK(g->scalar_type() == at::kFloat, "gumbel_noise dtype must be float32");
-  TORCH_CHECK(g->dim() == 2, "gumbel_noise must be 2D");
-  TORCH_CHECK(g->size(0) == b && g->size(1) == v, "gumbel_noise shape must be [", b, ", ", v, "]");
-}
-
+// check_logits, check_1d_float, check_noise: torch_common.h (shared with torch_spec.cpp)
 at::Tensor fused_sampler(const at::Tensor& logits, const c10::optional<at::Tensor>& penalty_mask, const c10::optional<at::Tensor>& slot_id,
                          const c10::optional<at::Tensor>& repetition_penalty, double repetition_penalty_val,
                          const c10::optional<at::Tensor>& temperature, double temperature_val, int64_t softmax_policy,

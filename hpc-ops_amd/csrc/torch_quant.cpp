@@ -9,8 +9,6 @@ using namespace hpc_torch;
 
 namespace {
 
-const auto kF8 = at::kFloat8_e4m3fn;
-
 // [T, H] with H % 128 == 0 and 128 <= H <= 16384
 void check_rows(const at::Tensor& t, const char* name) {
   cuda_contig(t, name);
@@ -20,25 +18,14 @@ void check_rows(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.size(0) <= INT32_MAX, "too many rows");
 }
 
-// an output given by the caller, or a fresh one: dtype, device, contiguity and shape are checked either way
-at::Tensor out_or_new(const c10::optional<at::Tensor>& given, const at::Tensor& like, at::IntArrayRef shape, at::ScalarType dtype,
-                      const char* name) {
-  if (!given.has_value()) return at::empty(shape, like.options().dtype(dtype));
-  const at::Tensor& o = *given;
-  TORCH_CHECK(o.is_cuda() && o.device() == like.device(), name, " must be on the input's device");
-  TORCH_CHECK(o.scalar_type() == dtype, name, " dtype must be ", dtype);
-  TORCH_CHECK(o.is_contiguous() && o.sizes() == shape, name, " must be a contiguous tensor of shape ", shape);
-  return o;
-}
-
 std::tuple<at::Tensor, at::Tensor> blockwise_fp8_quant(const at::Tensor& input, const c10::optional<at::Tensor>& output,
                                                        const c10::optional<at::Tensor>& output_scale) {
   check_rows(input, "input");
   const auto st = input.scalar_type();
   TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, "input dtype must be float32, float16, or bfloat16");
   const int64_t t = input.size(0), h = input.size(1);
-  at::Tensor q = out_or_new(output, input, {t, h}, kF8, "output");
-  at::Tensor sc = out_or_new(output_scale, input, {t, h / 128}, at::kFloat, "output_scale");
+  at::Tensor q = out_or_new(output, input, {t, h}, kF8, "output", kOnInputDevice);
+  at::Tensor sc = out_or_new(output_scale, input, {t, h / 128}, at::kFloat, "output_scale", kOnInputDevice);
   if (t == 0) return std::make_tuple(q, sc);
   const int in_dtype = st == at::kBFloat16 ? 0 : (st == at::kHalf ? 1 : 2);
   const int rc = hpc_blockwise_fp8_quant_async(ptr(q), static_cast<float*>(sc.data_ptr()), ptr(input), in_dtype, i32(t), i32(h),
@@ -68,9 +55,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> fused_rmsnorm_blockwise_quant(
     TORCH_CHECK(r.sizes() == a.sizes(), "residual shape must match a");
   }
   TORCH_CHECK(return_normed || !output_normed.has_value(), "output_normed needs return_normed");
-  at::Tensor q = out_or_new(output, a, {t, h}, kF8, "output");
-  at::Tensor sc = out_or_new(output_scale, a, {t, h / 128}, at::kFloat, "output_scale");
-  at::Tensor y = return_normed ? out_or_new(output_normed, a, {t, h}, at::kBFloat16, "output_normed")
+  at::Tensor q = out_or_new(output, a, {t, h}, kF8, "output", kOnInputDevice);
+  at::Tensor sc = out_or_new(output_scale, a, {t, h / 128}, at::kFloat, "output_scale", kOnInputDevice);
+  at::Tensor y = return_normed ? out_or_new(output_normed, a, {t, h}, at::kBFloat16, "output_normed", kOnInputDevice)
                                : at::empty({0}, a.options());
   if (t == 0) return std::make_tuple(q, sc, y);
   const int rc = hpc_fused_rmsnorm_blockwise_quant_async(ptr(q), static_cast<float*>(sc.data_ptr()),

@@ -8,16 +8,6 @@ using namespace hpc_torch;
 
 namespace {
 
-// an output given by the caller, or a fresh one: dtype, device, contiguity and shape are checked either way
-at::Tensor out_or_new(const c10::optional<at::Tensor>& given, const at::Tensor& like, at::IntArrayRef shape, const char* name) {
-  if (!given.has_value()) return at::empty(shape, like.options().dtype(at::kInt));
-  const at::Tensor& o = *given;
-  TORCH_CHECK(o.is_cuda() && o.device() == like.device(), name, " must be on the logits' device");
-  TORCH_CHECK(o.scalar_type() == at::kInt, name, " dtype must be int32");
-  TORCH_CHECK(o.is_contiguous() && o.sizes() == shape, name, " must be a contiguous tensor of shape ", shape);
-  return o;
-}
-
 std::tuple<at::Tensor, at::Tensor> speculative_verify(const at::Tensor& logits, const at::Tensor& draft_token_ids,
                                                       const c10::optional<at::Tensor>& temperature, double temperature_val,
                                                       const c10::optional<at::Tensor>& uniform_samples,
@@ -25,13 +15,8 @@ std::tuple<at::Tensor, at::Tensor> speculative_verify(const at::Tensor& logits, 
                                                       const c10::optional<at::Tensor>& output_token_ids,
                                                       const c10::optional<at::Tensor>& num_accepted) {
   const char* who = "speculative_verify";
-  TORCH_CHECK(logits.is_cuda(), "logits must be a device tensor");
-  TORCH_CHECK(logits.dim() == 2, "logits tensor must be dim == 2");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "logits dtype must be float32 or bfloat16");
-  const int64_t rows = logits.size(0), v = logits.size(1);
-  TORCH_CHECK(logits.stride(1) == 1, who, ": logits must have contiguous inner dim (stride(1)=1), got stride(1)=", logits.stride(1));
-  TORCH_CHECK(logits.stride(0) >= v, who, ": logits stride(0)=", logits.stride(0), " must be >= vocab_size=", v);
-  TORCH_CHECK(v > 0 && v % 8 == 0 && v < (1 << 20), who, ": unsupported vocab_size ", v, " (must be a multiple of 8, < 2^20)");
+  const LogitsDims d = check_logits(logits, who, /*nonempty_vocab=*/true);
+  const int64_t rows = d.b, v = d.v;
 
   TORCH_CHECK(draft_token_ids.is_cuda() && draft_token_ids.device() == logits.device(), "draft_token_ids must be on the logits' device");
   TORCH_CHECK(draft_token_ids.is_contiguous(), "draft_token_ids tensor must be contiguous");
@@ -42,35 +27,25 @@ std::tuple<at::Tensor, at::Tensor> speculative_verify(const at::Tensor& logits, 
   TORCH_CHECK(rows == b * (k + 1), who, ": logits rows must be batch_size * (num_draft + 1) = ", b * (k + 1), ", got ", rows);
   TORCH_CHECK(rows <= 65535, who, ": batch_size * (num_draft + 1) must be <= 65535, got ", rows);
 
-  if (temperature.has_value()) {
-    TORCH_CHECK(temperature->is_cuda() && temperature->device() == logits.device(), "temperature must be on the logits' device");
-    TORCH_CHECK(temperature->is_contiguous(), "temperature tensor must be contiguous");
-    TORCH_CHECK(temperature->scalar_type() == at::kFloat, "temperature dtype must be float32");
-    TORCH_CHECK(temperature->dim() == 1, "temperature tensor must be 1D");
-    TORCH_CHECK(temperature->size(0) == b, "temperature size must be [batch_size=", b, "], got [", temperature->size(0), "]");
-  } else {
+  check_1d_float(temperature, "temperature", b, &logits);
+  if (!temperature.has_value())
     TORCH_CHECK(temperature_val >= 0.0, who, ": scalar temperature must be >= 0, got ", temperature_val);
-  }
 
   TORCH_CHECK(uniform_samples.has_value() == gumbel_noise.has_value(),
               "uniform_samples and gumbel_noise must both be provided or both be omitted");
   if (gumbel_noise.has_value()) {
-    const at::Tensor &u = *uniform_samples, &g = *gumbel_noise;
+    const at::Tensor& u = *uniform_samples;
     TORCH_CHECK(u.is_cuda() && u.device() == logits.device(), "uniform_samples must be on the logits' device");
     TORCH_CHECK(u.is_contiguous(), "uniform_samples tensor must be contiguous");
     TORCH_CHECK(u.scalar_type() == at::kFloat, "uniform_samples dtype must be float32");
     TORCH_CHECK(u.dim() == 2 && u.size(0) == b && u.size(1) == k, "uniform_samples shape must be [", b, ", ", k, "]");
-    TORCH_CHECK(g.is_cuda() && g.device() == logits.device(), "gumbel_noise must be on the logits' device");
-    TORCH_CHECK(g.is_contiguous(), "gumbel_noise tensor must be contiguous");
-    TORCH_CHECK(g.scalar_type() == at::kFloat, "gumbel_noise dtype must be float32");
-    TORCH_CHECK(g.dim() == 2, "gumbel_noise must be 2D");
-    TORCH_CHECK(g.size(0) == rows && g.size(1) == v, "gumbel_noise shape must be [", rows, ", ", v, "]");
+    check_noise(gumbel_noise, rows, v, &logits);
   } else {
     TORCH_CHECK(seed > 0, who, ": seed must be > 0 when uniform_samples and gumbel_noise are not provided, got seed=", seed);
   }
 
-  at::Tensor out = out_or_new(output_token_ids, logits, {b, k + 1}, "output_token_ids");
-  at::Tensor acc = out_or_new(num_accepted, logits, {b}, "num_accepted");
+  at::Tensor out = out_or_new(output_token_ids, logits, {b, k + 1}, at::kInt, "output_token_ids", kOnLogitsDevice);
+  at::Tensor acc = out_or_new(num_accepted, logits, {b}, at::kInt, "num_accepted", kOnLogitsDevice);
   if (b == 0) return std::make_tuple(out, acc);
   at::Tensor ws = at::empty({hpc_speculative_verify_workspace_bytes(i32(b), i32(k), i32(v))}, logits.options().dtype(at::kByte));
   const int rc = hpc_speculative_verify_async(

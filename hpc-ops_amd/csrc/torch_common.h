@@ -103,7 +103,8 @@ inline void check_noise(const c10::optional<at::Tensor>& g, int64_t b, int64_t v
 
 // ---- zero-once scratch --------------------------------------------------------------------------------------------
 // Some kernels keep arrival counters in caller scratch that must be ZERO the first time a buffer is used and that
-// every call leaves zero again (decode: the counters of split requests; router GEMM: its split-K tickets).  Instead of
+// every call leaves zero again (decode: the counters of split requests; router GEMM: its split-K tickets; dense FP8 linear:
+// its split-K tickets in front of its partial planes).  Instead of
 // an allocation + a zero-fill launch per call, such scratch is one buffer per (purpose, device, stream, hipGraph
 // capture), allocated once with its first `zero_bytes` bytes zeroed.  Calls on one stream are ordered, so sharing the
 // buffer between them is safe; different streams get different buffers.  A buffer first used while a hipGraph is being
@@ -111,7 +112,7 @@ inline void check_noise(const c10::optional<at::Tensor>& g, int64_t b, int64_t v
 // serves the calls of that capture and nothing else, the entries of earlier (ended) captures on the stream are dropped on
 // the next call (their memory stays with their graph's pool), and a buffer cached by eager calls is not used inside a capture - every graph
 // owns its buffer and its zero node.
-enum ScratchPurpose { kScratchDecode = 0, kScratchGemmFlags = 1 };
+enum ScratchPurpose { kScratchDecode = 0, kScratchGemmFlags = 1, kScratchLinear = 2 };
 using ScratchKey = std::tuple<int, int, void*, long long>;
 inline std::mutex& scratch_mutex() {
   static std::mutex mu;
@@ -148,8 +149,8 @@ inline at::Tensor cached_scratch(int purpose, const at::Tensor& like, int64_t nb
   }
   return it->second;
 }
-// Drops EVERY cached scratch buffer of every purpose: the decode workspaces AND the router GEMM's split-K ticket
-// buffers (hpc.release_decode_workspaces documents both).
+// Drops EVERY cached scratch buffer of every purpose: the decode workspaces, the router GEMM's split-K ticket buffers AND
+// the dense FP8 linear's tickets + planes (hpc.release_decode_workspaces documents them).
 inline void release_cached_scratch() {
   std::lock_guard<std::mutex> lock(scratch_mutex());
   scratch_cache().clear();

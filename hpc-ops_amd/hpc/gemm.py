@@ -1,4 +1,5 @@
-"""hpc.gemm — router GEMM with an fp32 weight carried as two bf16 planes (reference hpc/gemm.py:7-80)."""
+"""hpc.gemm — router GEMM with an fp32 weight carried as two bf16 planes (reference hpc/gemm.py:7-80), the top-k routers
+and the dense FP8 linear with 128-block scales."""
 import torch
 from torch import Tensor
 
@@ -81,3 +82,50 @@ def _grouped_topk_router_fake(logits, correction_bias, topk, num_expert_group, t
     m = logits.shape[0]
     return (torch.empty((m, topk), dtype=torch.int32, device=logits.device),
             torch.empty((m, topk), dtype=torch.float32, device=logits.device))
+
+
+def gemm_blockwise_fp8(x: Tensor, x_scale: Tensor, weight: Tensor, weight_scale: Tensor, *, output: Tensor = None,
+                       splits: int = 0) -> Tensor:
+    """Dense FP8 linear with 128-block scales for decode batches: the Q/KV/O projections, dense and shared-expert MLPs
+    and the LM head of a block-scaled FP8 model (DeepSeek-V3, Qwen3 FP8 checkpoints).  Returns y bf16 [M, N].
+
+    No reference counterpart; semantics = the PyTorch statement tests/linear_fp8_ref.py, in fp32 or better:
+
+        y[m, n] = bf16( sum_kb x_scale[m, kb] * weight_scale[n // 128, kb]
+                               * sum_{k in block kb} float(x[m, k]) * float(weight[n, k]) )
+
+    with kb running over the K / 128 blocks of 128 consecutive k.
+
+    Layouts:
+      x             float8_e4m3fn [M, K], contiguous;
+      x_scale       float32 [M, K / 128], contiguous - (x, x_scale) is what blockwise_fp8_quant and
+                    fused_rmsnorm_blockwise_quant return, as they return it;
+      weight        float8_e4m3fn [N, K], contiguous;
+      weight_scale  float32 [ceil(N / 128), K / 128], stride(1) == 1 and stride(0) >= K / 128: the checkpoint's layout
+                    and rows padded to a multiple of four floats are both taken;
+      output        bfloat16 [M, N], contiguous.  When given it is written and returned (the same object) and nothing
+                    is allocated per call beyond the cached scratch, so the call captures into a hipGraph.
+
+    Limits: K % 128 == 0, K >= 128; N % 64 == 0 (an N that ends inside a 128-row scale block, such as 576 or 2112, is
+    fine); N * K <= 0xfffffff0 bytes; 1 <= M <= 256 - decode batches and speculative steps.  M == 0 returns an empty
+    [0, N] tensor without a launch; M > 256 is refused: use group_gemm_blockwise_fp8 for prefill-sized calls.  NaN / Inf
+    inputs: unspecified.
+
+    splits: the number of K slices the weight stream is cut into, each slice a workgroup of its own per 64 weight rows
+    and 64 tokens.  0 = the library chooses (enough to give every CU one to two workgroups, every slice at least four
+    k-blocks); 1 .. max = the caller's count, max = min(16, K / 128) - what torch.ops / hpc_gemm_blockwise_fp8_plan
+    reports; beyond it the call is refused.  With more than one slice the partial sums go through a cached scratch buffer
+    per (device, stream, hipGraph capture) that hpc.release_decode_workspaces() drops.
+
+    Determinism: the result for a given (M, N, K, splits, CU count) is bit-identical from call to call - the slices of
+    a tile are summed in slice order 0 .. S - 1 by whichever arrives last, never in arrival order, and no float atomics
+    are used.  Different split counts may differ in the last bit of the fp32 sum."""
+    y = torch.ops.hpc_linear.gemm_blockwise_fp8(x, x_scale, weight, weight_scale, output, splits)
+    return y if output is None else output
+
+
+@torch.library.register_fake("hpc_linear::gemm_blockwise_fp8")
+def _gemm_blockwise_fp8_fake(x, x_scale, weight, weight_scale, output=None, splits=0):
+    if output is not None:
+        return output
+    return torch.empty((x.shape[0], weight.shape[0]), dtype=torch.bfloat16, device=x.device)

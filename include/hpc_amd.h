@@ -430,6 +430,31 @@ int hpc_fused_rmsnorm_blockwise_quant_async(void* output_fp8, float* output_scal
                                             void* residual /* in/out, may be NULL */, float eps, int num_tokens,
                                             int hidden, hpc_stream_t stream);
 
+/* ---- dense FP8 linear with 128-block scales for decode batches (ours: no reference counterpart) ----
+ * The Q/KV/O projections, dense and shared-expert MLPs and the LM head of a block-scaled FP8 model; the statement is
+ * tests/linear_fp8_ref.py, in fp32 or better:
+ *   y[m, n] = bf16( sum_kb x_scale[m, kb] * weight_scale[n / 128, kb] * sum_{k in block kb} float(x[m, k]) * float(weight[n, k]) )
+ * x e4m3 [m, k] and x_scale f32 [m, k / 128], both row-major (the pair hpc_blockwise_fp8_quant_async writes); weight e4m3
+ * [n, k] row-major; weight_scale f32 [ceil(n / 128), k / 128] with ws_row_stride >= k / 128 floats between rows; y bf16
+ * [m, n].  k % 128 == 0, n % 64 == 0, 0 <= m <= 256 (prefill-sized calls: hpc_group_gemm_blockwise_fp8_async), n * k and
+ * m * k <= 0xfffffff0; x and weight 16-byte, y 8-byte, workspace 16-byte aligned.  m == 0 launches nothing.
+ * splits: 0 = the library chooses for the current device, 1 .. max_splits = the caller's count of K slices (every slice keeps
+ * a k-block; max_splits = min(16, k / 128)).  With more than one split every slice writes an fp32 partial plane to
+ * workspace ([splits, m, n], workspace_bytes >= the plan's) and the last slice to arrive at a (64-token, 64-row) tile - counted
+ * on counters, int32 [plan's count], ZERO on entry and zero again on exit - sums the planes in split order: the result for
+ * a given (m, n, k, splits, CU count) is bit-identical from call to call.  No workgroup waits for another.
+ * hpc_gemm_blockwise_fp8_plan(m, n, k, splits_wanted, cu_count (<= 0: the current device's), ...) gives the split count such
+ * a call runs with, max_splits, the workspace bytes and the counter count (both 0 without a split) and returns what the call
+ * would: HPC_ERR_UNSUPPORTED for k % 128, n % 64, m > 256, operands beyond 32-bit offsets or planes beyond 0xfffffff0 bytes,
+ * HPC_ERR_INVALID for negative sizes and splits beyond max_splits.  hpc_gemm_blockwise_fp8_async adds HPC_ERR_INVALID for
+ * null pointers, ws_row_stride < k / 128 and a workspace that is missing or too small, HPC_ERR_UNSUPPORTED for alignment.
+ * Every check is made on the host before any device call. */
+int hpc_gemm_blockwise_fp8_plan(int m, int n, int k, int splits_wanted, int cu_count, int* splits, int* max_splits,
+                                int64_t* workspace_bytes, int* counters);
+int hpc_gemm_blockwise_fp8_async(void* y, const void* x, const float* x_scale, const void* weight, const float* weight_scale,
+                                 int m, int n, int k, int64_t ws_row_stride, int splits, void* workspace,
+                                 int64_t workspace_bytes, void* counters, hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

@@ -1,0 +1,412 @@
+// MLA decode attention (weight-absorbed form) over the paged latent KV cache, bf16, gfx950.
+//
+//   z_j = scale * sum_{d < 576} q[row, d] * c[j, d]      out[row, :512] = sum_j softmax(z)_j * c[j, :512]
+//
+// One latent row of 576 bf16 per token is K (all 576 columns) and V (the first 512) of every head, so a KV tile is gathered
+// through the page table ONCE into one LDS image and read twice: by rows (ds_read_b128) as the A operand of S^T = C Q^T, and
+// through the transposing read (ds_read_b64_tr_b16) as the A operand of O^T = C^T P^T.  Computing S^T puts a q row on a lane
+// (column l & 15) and four tokens in its accumulator registers, which after exp2 and a pack to bf16 ARE the B operand of the
+// second product: the eight k-slots of lane group g hold tokens 16 tb + 4 g + 0..3 of two token blocks, and the transposing read
+// fetches exactly those rows for the other operand, so the token permutation is the same on both sides and no lane moves.
+//
+// Workgroup = 256 threads = (request, row tile, piece).  Rows of a request are r = s * num_head + h.
+//   wide   (rows > 16): a tile of 64 rows, wave w owns rows 16 w .. 16 w + 15 and all 64 tokens of every KV tile; a wave whose
+//          rows do not exist (a 48-row tile) only helps to gather.
+//   narrow (rows == 16: 16 heads at mtp 0): the four waves own the SAME 16 rows and wave w takes tokens 16 w .. 16 w + 15 of
+//          every KV tile (the upper half of its k-slots is zero); the four (max, sum, O) states are merged through LDS at the end.
+// KV tile: 64 tokens x 1,152 B in rows of kRowBytes = 1,184 B (296 dwords = 8 * 37: the 16 x 16-byte row read and the 8 rows x
+// 32 bytes a 32-lane half takes in a transposing read both touch every bank once), two images = 148 KiB.  The next tile's rows
+// are loaded into registers (18 x 16 B per thread) before the current tile is computed and stored to the other image after it;
+// their page ids are looked up one tile ahead, so the row loads never wait for a dependent load.
+// Rows of tokens at or past the piece's end are written as zeros, never loaded: 0 x NaN is NaN, and the entries of block_ids
+// past a request's pages are never dereferenced.  Masking is by score.
+//
+// Split KV: piece p of request b covers tokens [p * len, min(L_b, (p + 1) * len)), len = ceil(L_b / splits) rounded up to 64,
+// computed on the DEVICE from num_seq_kvcache (nothing on the host depends on the lengths).  A piece that starts at or past L_b
+// writes nothing, and the merge kernel computes the same piece count and never reads it.  A piece stores its running maximum,
+// its sum and its UNNORMALISED fp32 output; the merge sums exp2(m_p - M) * O_p in piece order and divides once (no float
+// atomics, bit-identical from call to call; exact where the softmax is uniform and the length a power of two).
+#include "attention_decode_mla_route.h"
+#include "hpc_amd.h"
+#include "hpc_common.h"
+
+namespace hpc {
+namespace mla {
+
+constexpr int kThreads = 256;
+constexpr int kRowBytes = 1184;               // LDS pitch of a latent row (1,152 B of data)
+constexpr int kBufBytes = kMlaKvTile * kRowBytes;
+constexpr int kLds = 2 * kBufBytes;           // 151,552 B
+constexpr int kKSteps = kMlaDim / 32;         // 18 MFMA k-steps over the 576 columns
+constexpr int kColBlocks = kMlaDimV / 16;     // 32 output column blocks
+constexpr float kLn2 = 0.693147180559945309f;
+constexpr float kLog2e = 1.442695040888963407f;
+static_assert(4 * 16 * kMlaDimV * 4 + 4 * 16 * 2 * 4 <= kLds, "the narrow form's merge fits the tile images");
+
+struct Args {
+  const uint8_t* q;
+  const uint8_t* ckv;
+  const int* block_ids;
+  const int* num_seq;
+  uint16_t* out;
+  float* lse;     // may be null
+  float* ws_o;    // [splits, total_rows, 512]
+  float* ws_ml;   // [splits, total_rows, 2]
+  int64_t block_stride_bytes, token_stride_bytes, total_rows;
+  int num_head, num_seq_q, rows, row_tiles, splits, page_shift, max_blocks, new_kv_included;
+  float scale_log2;  // softmax_scale * log2(e)
+};
+
+// tokens of request b including the new ones, never beyond the page table's reach
+__device__ __forceinline__ int request_len(const Args& a, int b) {
+  const int64_t cap = static_cast<int64_t>(a.max_blocks) << a.page_shift;
+  int64_t len = static_cast<int64_t>(a.num_seq[b]) + (a.new_kv_included ? 0 : a.num_seq_q);
+  len = len < 0 ? 0 : (len > cap ? cap : len);
+  return static_cast<int>(len);
+}
+__device__ __forceinline__ int piece_len(int len, int splits) {
+  return ((len + splits - 1) / splits + kMlaKvTile - 1) & ~(kMlaKvTile - 1);
+}
+
+// one result quad: the final bf16 output (one piece) or the piece's unnormalised fp32 partial
+__device__ __forceinline__ void emit4(const Args& a, int piece, int64_t grow, int col, f32x4 v, float l) {
+  if (a.splits == 1) {
+    const float inv = 1.0f / l;
+    *reinterpret_cast<u32x2*>(a.out + grow * kMlaDimV + col) =
+        u32x2{pack_bf16x2(v[0] * inv, v[1] * inv), pack_bf16x2(v[2] * inv, v[3] * inv)};
+  } else {
+    *reinterpret_cast<f32x4*>(a.ws_o + (piece * a.total_rows + grow) * kMlaDimV + col) = v;
+  }
+}
+__device__ __forceinline__ void emit_ml(const Args& a, int piece, int64_t grow, float m, float l) {
+  if (a.splits == 1) {
+    if (a.lse) a.lse[grow] = (m + __builtin_log2f(l)) * kLn2;
+  } else {
+    *reinterpret_cast<f32x2*>(a.ws_ml + (piece * a.total_rows + grow) * 2) = f32x2{m, l};
+  }
+}
+
+template <bool kNarrow>
+__global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Args a) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_mem[kLds];
+  constexpr int kTB = kNarrow ? 1 : 4;  // 16-token blocks a wave takes of a tile
+  constexpr int kKS = kNarrow ? 1 : 2;  // 32-token k-steps of the second product
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int c16 = lane & 15, g = lane >> 4;
+  int id = blockIdx.x;
+  const int piece = id % a.splits;
+  id /= a.splits;
+  const int tile = id % a.row_tiles, b = id / a.row_tiles;
+
+  const int len = request_len(a, b);
+  const int plen = piece_len(len, a.splits);
+  const int p0 = piece * plen;
+  if (p0 >= len) return;  // an empty piece writes nothing; the merge does not read it
+  const int p1 = p0 + plen < len ? p0 + plen : len;
+  const int n_tiles = (p1 - p0 + kMlaKvTile - 1) / kMlaKvTile;
+
+  const int rb = kNarrow ? 0 : tile * kMlaRowTile + 16 * wv;  // first q row of this wave
+  const bool active = rb < a.rows;                           // rows is a multiple of 16: all 16 rows exist or none
+  const int64_t grow = static_cast<int64_t>(b) * a.rows + rb + c16;
+  // causal limit of this lane's q row, cut at the piece's end
+  int lim = len - a.num_seq_q + (rb + c16) / a.num_head + 1;
+  lim = lim < p1 ? lim : p1;
+
+  bf16x8 qf[kKSteps];
+  if (active) {
+    const uint8_t* qrow = a.q + grow * (kMlaDim * 2) + g * 16;
+#pragma unroll
+    for (int ks = 0; ks < kKSteps; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + ks * 64);
+  }
+
+  // ---- gather: thread (rr, sub) takes chunks sub + 8 i of rows rr and rr + 32 ----
+  const int rr = tid >> 3, sub = tid & 7;
+  const int* pages = a.block_ids + static_cast<int64_t>(b) * a.max_blocks;
+  u32x4 stg[2][9];
+  // the page ids of the rows this thread loads next, looked up one tile ahead: the row loads do not wait for the page table
+  int page[2];
+  auto lookup = [&](int t0) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int tok = t0 + rr + 32 * p;
+      page[p] = tok < p1 ? pages[tok >> a.page_shift] : 0;
+    }
+  };
+  auto gather_issue = [&](int t0) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int tok = t0 + rr + 32 * p;
+      if (tok < p1) {
+        const uint8_t* src = a.ckv + static_cast<int64_t>(page[p]) * a.block_stride_bytes +
+                             static_cast<int64_t>(tok & ((1 << a.page_shift) - 1)) * a.token_stride_bytes + sub * 16;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) stg[p][i] = ld16(src + i * 128);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) stg[p][i] = u32x4{0, 0, 0, 0};
+      }
+    }
+    lookup(t0 + kMlaKvTile);
+  };
+  auto gather_commit = [&](int buf) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      uint8_t* dst = s_mem + buf * kBufBytes + (rr + 32 * p) * kRowBytes + sub * 16;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) *reinterpret_cast<u32x4*>(dst + i * 128) = stg[p][i];
+    }
+  };
+
+  f32x4 acc[kColBlocks];
+#pragma unroll
+  for (int cb = 0; cb < kColBlocks; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;  // running maximum (log2 units) and this lane's share of the sum
+
+  // transposing-read address of this lane inside a 16-token block: row 4 g + (c16 >> 2), columns 4 (c16 & 3) ..
+  const int tr_off = (4 * g + (c16 >> 2)) * kRowBytes + (c16 & 3) * 8;
+  const int rd_off = c16 * kRowBytes + g * 16;
+
+  lookup(p0);
+  gather_issue(p0);
+  gather_commit(0);
+  __syncthreads();
+
+  for (int it = 0; it < n_tiles; ++it) {
+    const int t0 = p0 + it * kMlaKvTile;
+    const int cur = it & 1;
+    const bool more = it + 1 < n_tiles;
+    if (more) gather_issue(t0 + kMlaKvTile);
+    if (active) {
+      const uint8_t* img = s_mem + cur * kBufBytes;
+      // ---- S^T = C Q^T ----
+      f32x4 s[kTB];
+#pragma unroll
+      for (int t = 0; t < kTB; ++t) {
+        const int tb = kNarrow ? wv : t;
+        s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < kKSteps; ++ks) {
+          const bf16x8 c = *reinterpret_cast<const bf16x8*>(img + tb * 16 * kRowBytes + rd_off + ks * 64);
+          s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(c, qf[ks], s[t], 0, 0, 0);
+        }
+      }
+      // ---- online softmax, masked by score ----
+      float mx = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < kTB; ++t) {
+        const int tb = kNarrow ? wv : t;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int tok = t0 + 16 * tb + 4 * g + i;
+          s[t][i] = tok < lim ? s[t][i] * a.scale_log2 : -INFINITY;
+          mx = fmaxf(mx, s[t][i]);
+        }
+      }
+      mx = row4_max(mx);
+      const float m_new = fmaxf(m, mx);
+      const float m_use = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = __builtin_amdgcn_exp2f(m - m_use);
+      m = m_new;
+      float psum = 0.f;
+#pragma unroll
+      for (int t = 0; t < kTB; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          s[t][i] = __builtin_amdgcn_exp2f(s[t][i] - m_use);
+          psum += s[t][i];
+        }
+      l = l * alpha + psum;
+      if (__any(alpha != 1.0f)) {
+#pragma unroll
+        for (int cb = 0; cb < kColBlocks; ++cb) acc[cb] *= alpha;
+      }
+      // ---- O^T += C^T P^T ----
+#pragma unroll
+      for (int ks = 0; ks < kKS; ++ks) {
+        u32x4 pw;
+        pw[0] = pack_bf16x2(s[kNarrow ? 0 : 2 * ks][0], s[kNarrow ? 0 : 2 * ks][1]);
+        pw[1] = pack_bf16x2(s[kNarrow ? 0 : 2 * ks][2], s[kNarrow ? 0 : 2 * ks][3]);
+        pw[2] = kNarrow ? 0u : pack_bf16x2(s[kNarrow ? 0 : 2 * ks + 1][0], s[kNarrow ? 0 : 2 * ks + 1][1]);
+        pw[3] = kNarrow ? 0u : pack_bf16x2(s[kNarrow ? 0 : 2 * ks + 1][2], s[kNarrow ? 0 : 2 * ks + 1][3]);
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
+        const int tb0 = kNarrow ? wv : 2 * ks;
+#pragma unroll
+        for (int cb = 0; cb < kColBlocks; ++cb) {
+          u32x4 vw = u32x4{0, 0, 0, 0};
+          const uint8_t* p_lo = img + tb0 * 16 * kRowBytes + tr_off + cb * 32;
+          const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              reinterpret_cast<lds_v4i16*>(static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_u8*)p_lo))));
+          const u32x2 lo2 = __builtin_bit_cast(u32x2, lo);
+          vw[0] = lo2[0], vw[1] = lo2[1];
+          if constexpr (!kNarrow) {
+            const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_v4i16*>(
+                static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_u8*)(p_lo + 16 * kRowBytes)))));
+            const u32x2 hi2 = __builtin_bit_cast(u32x2, hi);
+            vw[2] = hi2[0], vw[3] = hi2[1];
+          }
+          acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vw), pf, acc[cb], 0, 0, 0);
+        }
+      }
+    }
+    if (more) gather_commit(cur ^ 1);
+    __syncthreads();
+  }
+
+  // ---- epilogue: lane (c16, g) holds columns 16 cb + 4 g + 0..3 of q row c16 ----
+  if constexpr (!kNarrow) {
+    if (!active) return;
+    l = row4_sum(l);
+#pragma unroll
+    for (int cb = 0; cb < kColBlocks; ++cb) emit4(a, piece, grow, 16 * cb + 4 * g, acc[cb], l);
+    if (g == 0) emit_ml(a, piece, grow, m, l);
+  } else {
+    // the four waves' states of the same 16 rows: scale to the common maximum, sum in wave order
+    float* s_f = reinterpret_cast<float*>(s_mem);      // [4][16][512]
+    float* s_ml = s_f + 4 * 16 * kMlaDimV;             // [4][16][2]
+    l = row4_sum(l);
+    if (g == 0) {
+      s_ml[(wv * 16 + c16) * 2] = m;
+      s_ml[(wv * 16 + c16) * 2 + 1] = l;
+    }
+    __syncthreads();
+    float mm = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, s_ml[(w * 16 + c16) * 2]);
+    const float f = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mm);
+#pragma unroll
+    for (int cb = 0; cb < kColBlocks; ++cb)
+      *reinterpret_cast<f32x4*>(s_f + (wv * 16 + c16) * kMlaDimV + 16 * cb + 4 * g) = acc[cb] * f;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int idx = tid + kThreads * e, row = idx >> 7, col = (idx & 127) * 4;
+      float mr = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) mr = fmaxf(mr, s_ml[(w * 16 + row) * 2]);
+      float lt = 0.f;
+      f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float mw = s_ml[(w * 16 + row) * 2], lw = s_ml[(w * 16 + row) * 2 + 1];
+        lt += (mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - mr)) * lw;
+        sum += *reinterpret_cast<const f32x4*>(s_f + (w * 16 + row) * kMlaDimV + col);
+      }
+      const int64_t gr = static_cast<int64_t>(b) * a.rows + row;
+      emit4(a, piece, gr, col, sum, lt);
+      if (col == 0) emit_ml(a, piece, gr, mr, lt);
+    }
+  }
+}
+
+// Sums the pieces of one output row in piece order.  Pieces at or past the request's end were never written and are not read;
+// a piece in which this row saw no token (its sum is 0) is skipped.
+__global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const Args a) {
+  const int64_t grow = blockIdx.x;
+  const int b = static_cast<int>(grow / a.rows);
+  const int len = request_len(a, b);
+  if (len == 0) return;
+  const int plen = piece_len(len, a.splits);
+  const int np = (len + plen - 1) / plen;  // <= splits
+  const int col = threadIdx.x * 4;
+  float mm = -INFINITY;
+  for (int p = 0; p < np; ++p) {
+    const f32x2 ml = *reinterpret_cast<const f32x2*>(a.ws_ml + (p * a.total_rows + grow) * 2);
+    if (ml[1] > 0.f) mm = fmaxf(mm, ml[0]);
+  }
+  float lt = 0.f;
+  f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int p = 0; p < np; ++p) {
+    const f32x2 ml = *reinterpret_cast<const f32x2*>(a.ws_ml + (p * a.total_rows + grow) * 2);
+    if (ml[1] > 0.f) {
+      const float f = __builtin_amdgcn_exp2f(ml[0] - mm);
+      lt += f * ml[1];
+      sum += *reinterpret_cast<const f32x4*>(a.ws_o + (p * a.total_rows + grow) * kMlaDimV + col) * f;
+    }
+  }
+  const float inv = 1.0f / lt;
+  *reinterpret_cast<u32x2*>(a.out + grow * kMlaDimV + col) =
+      u32x2{pack_bf16x2(sum[0] * inv, sum[1] * inv), pack_bf16x2(sum[2] * inv, sum[3] * inv)};
+  if (a.lse && threadIdx.x == 0) a.lse[grow] = (mm + __builtin_log2f(lt)) * kLn2;
+}
+
+}  // namespace mla
+}  // namespace hpc
+
+namespace {
+int mla_current_cu_count() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
+}
+}  // namespace
+
+// What a call of hpc_attention_decode_mla_bf16_async with this `splits_wanted` runs with and needs: mla_route()
+// (attention_decode_mla_route.h).  num_cu <= 0: the current device's (256 without a device).
+extern "C" int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int num_head, int splits_wanted, int num_cu,
+                                             int* splits, int* max_splits, int64_t* workspace_bytes) {
+  if (!splits || !max_splits || !workspace_bytes) return HPC_ERR_INVALID;
+  // refusals first, on the host alone; only a call that leaves both the split count and the CU count open asks the device
+  hpc::MlaRoute r = hpc::mla_route(num_batch, num_seq_q, num_head, splits_wanted, num_cu > 0 ? num_cu : 256);
+  if (r.code == HPC_OK && num_cu <= 0 && splits_wanted == 0 && num_batch > 0)
+    r = hpc::mla_route(num_batch, num_seq_q, num_head, 0, mla_current_cu_count());
+  *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes;
+  return r.code;
+}
+
+extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                   const int* block_ids_ptr, const int* num_seq_kvcache_ptr, int num_batch,
+                                                   int num_seq_q, int num_head, int block_size, int max_blocks,
+                                                   int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                                   int new_kv_included, int splits, void* workspace_ptr,
+                                                   int64_t workspace_bytes, hipStream_t stream) {
+  using namespace hpc::mla;
+  if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr) return HPC_ERR_INVALID;
+  if (splits < 0 || max_blocks < 0 || ckv_block_stride < 0) return HPC_ERR_INVALID;
+  // the split count is the caller's, or with 0 the route's for this device; shapes are refused before the device is asked
+  const hpc::MlaRoute shape = hpc::mla_route(num_batch, num_seq_q, num_head, splits > 0 ? splits : 1, 256);
+  if (shape.code != HPC_OK) return shape.code;
+  if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
+  if (ckv_token_stride < hpc::kMlaDim || (ckv_token_stride & 7) || (ckv_block_stride & 7)) return HPC_ERR_UNSUPPORTED;
+  if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(q_ptr) | reinterpret_cast<uintptr_t>(ckv_ptr)) & 15) return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3)) return HPC_ERR_UNSUPPORTED;
+  if (num_batch == 0) return HPC_OK;
+  if (max_blocks == 0) return HPC_ERR_INVALID;
+  const hpc::MlaRoute r = splits > 0 ? shape : hpc::mla_route(num_batch, num_seq_q, num_head, 0, mla_current_cu_count());
+  if (r.code != HPC_OK) return r.code;
+  if (r.splits > 1) {
+    if (!workspace_ptr || workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(workspace_ptr) & 15) return HPC_ERR_UNSUPPORTED;
+  }
+  Args a;
+  a.q = static_cast<const uint8_t*>(q_ptr);
+  a.ckv = static_cast<const uint8_t*>(ckv_ptr);
+  a.block_ids = block_ids_ptr;
+  a.num_seq = num_seq_kvcache_ptr;
+  a.out = static_cast<uint16_t*>(out_ptr);
+  a.lse = lse_ptr;
+  a.ws_o = static_cast<float*>(workspace_ptr);
+  a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
+  a.block_stride_bytes = ckv_block_stride * 2;
+  a.token_stride_bytes = ckv_token_stride * 2;
+  a.total_rows = static_cast<int64_t>(num_batch) * r.rows;
+  a.num_head = num_head;
+  a.num_seq_q = num_seq_q;
+  a.rows = r.rows;
+  a.row_tiles = r.row_tiles;
+  a.splits = r.splits;
+  a.page_shift = block_size == 16 ? 4 : (block_size == 32 ? 5 : (block_size == 64 ? 6 : 7));
+  a.max_blocks = max_blocks;
+  a.new_kv_included = new_kv_included ? 1 : 0;
+  a.scale_log2 = softmax_scale * kLog2e;
+  if (r.narrow)
+    attention_decode_mla_kernel<true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+  else
+    attention_decode_mla_kernel<false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+  HPC_CHECK_LAUNCH();
+  if (r.splits > 1) {
+    attention_decode_mla_merge_kernel<<<dim3(r.merge_grid), 128, 0, stream>>>(a);
+    HPC_CHECK_LAUNCH();
+  }
+  return HPC_OK;
+}

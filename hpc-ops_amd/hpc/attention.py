@@ -127,7 +127,8 @@ def task_workspace_bytes(num_cu, max_num_batch, max_seqlen, num_head_kv, min_pro
 
 def release_decode_workspaces():
     """Drop EVERY zero-once scratch buffer the host library caches per (purpose, device, stream, hipGraph capture) - the
-    decode workspaces and the router GEMM's split-K ticket buffers alike (csrc/torch_common.h::release_cached_scratch) -
+    decode workspaces, the router GEMM's split-K ticket buffers and the MLA decode's split-KV partials alike
+    (csrc/torch_common.h::release_cached_scratch) -
     e.g. after the streams / graphs that used them are gone.  Buffers of captures that have ended are dropped on the
     next call on their stream anyway."""
     torch.ops.hpc._release_decode_workspaces()
@@ -320,3 +321,70 @@ def _attention_with_kvcache_prefill_bf16_fake(q, kcache, vcache, cu_seqlens_q, b
                                               max_seqlens_q, output=None):
     return output if output is not None else torch.empty((q.shape[0], q.shape[1], vcache.shape[-1]), dtype=q.dtype,
                                                          device=q.device)
+
+
+def attention_decode_mla_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,
+                              softmax_scale: float, mtp: int = 0, new_kv_included: bool = False, *, output: Tensor = None,
+                              output_lse: Tensor = None, return_lse: bool = False, splits: int = 0):
+    """Multi-head latent attention (MLA) decode in its weight-absorbed form over the paged latent KV cache, bfloat16
+    (DeepSeek-V3 / R1, Kimi-K2 decode steps).  Returns out bf16 [B * Sq, H, 512], or (out, lse) with return_lse or
+    output_lse.
+
+    No reference counterpart; semantics = the PyTorch statement tests/mla_ref.py, in float64.  One latent row per token
+    is the key of every head (all 576 columns) and its value (the first 512).  With Sq = mtp + 1 and L_b the tokens of
+    request b including the Sq new ones, row (b, s, h) sees tokens j < L_b - Sq + s + 1 (causal among the new tokens):
+
+        z_j = softmax_scale * sum_{d < 576} q[b * Sq + s, h, d] * c_b[j, d]
+        out[b * Sq + s, h, :] = bf16( sum_j softmax(z)_j * c_b[j, :512] )
+        lse[b * Sq + s, h]    = log sum_j exp(z_j)                      (float32, natural log)
+
+    Layouts:
+      q                bfloat16 [B * Sq, H, 576], contiguous: columns 0..511 are q_nope already multiplied by W_UK
+                       (latent space), columns 512..575 the RoPE part;
+      ckv_cache        bfloat16, logical [num_blocks, P, 576]: one latent row per token, 512 compressed KV + 64 RoPE'd
+                       k_pe.  Any block stride that is a multiple of 8 elements, token stride >= 576 and a multiple of 8,
+                       last dim contiguous, base 16-byte aligned: padded rows and a view into a larger pool both work;
+      block_ids        int32 [B, max_blocks] page table; entries past a request's pages are never dereferenced;
+      num_seq_kvcache  int32 [B] on the device: the tokens before this step, or including the Sq new ones with
+                       new_kv_included (the convention of attention_decode_bf16; the new tokens' rows are in the cache).
+                       Nothing on the host depends on its values: a captured hipGraph replayed after the lengths
+                       changed gives the new lengths' result;
+      softmax_scale    explicit: 1 / sqrt(128 + 64) times the model's YaRN factor - it is not guessed from 576;
+      output           bfloat16 [B * Sq, H, 512] and output_lse float32 [B * Sq, H], contiguous.  When given they are
+                       written and returned (the same objects) and nothing is allocated per call beyond the cached
+                       scratch, so the call captures into a hipGraph.
+
+    Limits: H % 16 == 0, 16 <= H <= 128; mtp 0..3; P in {16, 32, 64, 128}.  B == 0 returns empty tensors without a
+    launch.  Every row must see at least one token.  NaN / Inf inputs: unspecified.  Finite values in page tails, in
+    pages no block table lists and in later new tokens of the same request do not influence the result.
+
+    splits: the number of pieces each request's token range is cut into, each piece a workgroup of its own per 64 q
+    rows (r = s * H + h).  0 = the library chooses (one piece when the batch fills the CUs, else about two workgroups
+    per CU); 1 .. max = the caller's count, max = 64; beyond it the call is refused.  The piece length of request b is
+    ceil(L_b / splits) rounded up to the kernel's KV tile of 64 tokens, computed on the device; a piece that starts at
+    or past L_b is empty, writes nothing and is never read.  With splits == 1 the kernel writes out directly; otherwise
+    the pieces go through a cached scratch buffer per (device, stream, hipGraph capture), which
+    hpc.release_decode_workspaces() drops, and a second launch merges them.
+
+    Determinism: for given shapes, splits and CU count the result is bit-identical from call to call - the merge sums
+    the pieces in piece order and no float atomics are used."""
+    out, lse = torch.ops.hpc_mla.attention_decode_mla_bf16(q, ckv_cache, block_ids, num_seq_kvcache, float(softmax_scale),
+                                                           int(mtp), bool(new_kv_included), output, output_lse,
+                                                           bool(return_lse), int(splits))
+    out = out if output is None else output
+    if not (return_lse or output_lse is not None):
+        return out
+    return out, (lse if output_lse is None else output_lse)
+
+
+@torch.library.register_fake("hpc_mla::attention_decode_mla_bf16")
+def _attention_decode_mla_bf16_fake(q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp, new_kv_included,
+                                    output=None, output_lse=None, return_lse=False, splits=0):
+    out = output if output is not None else torch.empty((q.shape[0], q.shape[1], 512), dtype=torch.bfloat16, device=q.device)
+    if output_lse is not None:
+        lse = output_lse
+    elif return_lse:
+        lse = torch.empty((q.shape[0], q.shape[1]), dtype=torch.float32, device=q.device)
+    else:
+        lse = torch.empty((0,), dtype=torch.float32, device=q.device)
+    return out, lse

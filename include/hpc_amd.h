@@ -455,6 +455,37 @@ int hpc_gemm_blockwise_fp8_async(void* y, const void* x, const float* x_scale, c
                                  int m, int n, int k, int64_t ws_row_stride, int splits, void* workspace,
                                  int64_t workspace_bytes, void* counters, hpc_stream_t stream);
 
+/* ---- MLA decode attention over the paged latent KV cache, bf16 (csrc/attention_decode_mla.hip) -------------------------------
+ * No reference kernel exists; the semantics are the PyTorch statement tests/mla_ref.py (weight-absorbed multi-head latent
+ * attention: DeepSeek-V3 / R1, Kimi-K2).  One latent row of 576 bf16 per token (512 compressed KV + 64 RoPE) is the key of every
+ * head, its first 512 columns the value.  With L_b = the tokens of request b including the num_seq_q new ones, row (b, s, h) sees
+ * tokens j < L_b - num_seq_q + s + 1:
+ *   z_j = softmax_scale * sum_{d < 576} q[b * num_seq_q + s, h, d] * c_b[j, d]
+ *   out[b * num_seq_q + s, h, :] = bf16( sum_j softmax(z)_j * c_b[j, :512] )     lse[b * num_seq_q + s, h] = log sum_j exp(z_j)
+ * q bf16 [num_batch * num_seq_q, num_head, 576] contiguous; ckv bf16, token (page, t) at ckv + page * ckv_block_stride +
+ * t * ckv_token_stride elements (token stride >= 576, both strides multiples of 8, base 16-byte aligned); block_ids int32
+ * [num_batch, max_blocks] (entries past a request's pages are never read); num_seq_kvcache int32 [num_batch] ON THE DEVICE:
+ * the tokens before this step, or including the new ones with new_kv_included - no host decision depends on its values.
+ * out bf16 [num_batch * num_seq_q, num_head, 512]; lse fp32 [num_batch * num_seq_q, num_head] or NULL.
+ * num_head % 16 == 0, 16 .. 128; num_seq_q 1 .. 4; block_size 16 / 32 / 64 / 128; max_blocks * block_size <= 2^30.
+ * splits: pieces every request's tokens are cut into (piece length ceil(L_b / splits) rounded up to 64 tokens, computed on the
+ * device): 0 = the library chooses for the current device, 1 .. max_splits = the caller's count.  One piece writes out
+ * directly; more go through `workspace` (16-byte aligned, never zeroed: pieces past a request's end are neither written nor
+ * read) and a merge launch that sums the pieces in piece order - no float atomics, bit-identical from call to call.
+ * hpc_attention_decode_mla_plan(num_batch, num_seq_q, num_head, splits_wanted, num_cu (<= 0: the current device's), ...) gives
+ * the split count such a call runs with, max_splits and the workspace bytes (0 with one piece) and returns what the call
+ * would: HPC_ERR_UNSUPPORTED for the head count and num_seq_q, HPC_ERR_INVALID for negative counts and splits beyond max_splits.
+ * hpc_attention_decode_mla_bf16_async adds HPC_ERR_INVALID for null pointers (lse may be NULL), negative max_blocks or block
+ * stride and a workspace that is missing or too small, HPC_ERR_UNSUPPORTED for block_size, the strides and alignment.  Every
+ * check is made on the host before any device call. */
+int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int num_head, int splits_wanted, int num_cu, int* splits,
+                                  int* max_splits, int64_t* workspace_bytes);
+int hpc_attention_decode_mla_bf16_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                        const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size,
+                                        int max_blocks, int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                        int new_kv_included, int splits, void* workspace, int64_t workspace_bytes,
+                                        hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

@@ -13,8 +13,12 @@
 // one kv head) and finishes alone - no split-KV, no merge; a workgroup = 4 waves = 128 consecutive rows
 // that walk the KV tiles together (causal: each wave masks what its rows cannot see) and share every
 // K/V tile through a double-buffered LDS stage filled one tile ahead.
+//
+// Host side: which form a call runs, its shifts, its grid and every refusal are attention_prefill_route.h::prefill_route(); the
+// entries at the end of this file check their operands, ask it and launch from it.
+#include "attention_prefill_route.h"
+#include "attention_prefill_tile.h"
 #include "hpc_common.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
@@ -42,13 +46,8 @@ struct Args {
   float scale_log2;
 };
 
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kNB = 2;                  // 16-row q blocks per wave
-constexpr int kRowsPerWave = 16 * kNB;  // 32
-constexpr float kNegInf = -__builtin_inff();
+using namespace prefill_tile;
 constexpr int kKRow = 128 + 16;  // padded LDS row of the K transpose tile
-constexpr int kMaskCols = 512;    // block-sparse: mask columns (128-token tiles) cached per head
 
 // ---- loads the compiler does not see (hand-counted vmcnt, as in attention_decode_v2.hip) ---------------------------
 __device__ __forceinline__ void ld_pair(u32x4& x0, u32x4& x1, int voff, i32x4 rs, int soff1) {
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
   // block-sparse: the mask rows of this workgroup's q tile, one per q head of the kv head (<= 64k tokens)
   // (round 3: ONE word per mask column, bit gq = q head gq of this kv head attends the column - a tile costs one
   // broadcast LDS read instead of G + 2 byte reads; 16 bits: the launcher accepts up to 16 q heads per kv head)
-  __shared__ uint16_t s_mask[kSparse ? kMaskCols : 16];
+  __shared__ uint16_t s_mask[kSparse ? kPrefillMaskCols : 16];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -103,7 +102,6 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
   // Row mapping of the workgroup's 128 (position, q head) rows.  G <= 8: every 16-row MFMA block is ONE
   // q head x 16 consecutive positions (block-sparse masks are per head: a whole block can then skip a
   // tile); G = 16: 8 positions x 16 heads, head fastest.
-  constexpr int kWgRows = kWaves * kRowsPerWave;
   // q tiles are handed out last-first: a late tile walks the most KV (causal), so the longest workgroups start first
   // and the grid's tail is made of the short ones
   const int wg_pos0 = ((gridDim.x - 1 - blockIdx.x) * kWgRows) >> a.g_shift;  // positions per workgroup = 128 / G
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
     const int gtok = blk << 4;
     const int pid = __builtin_amdgcn_readfirstlane(bid_row[gtok >> a.page_shift]);
     const int inpage = gtok & page_mask;
-    // unsigned 32 x 32 -> 64 products (the launcher refuses block strides of 4 GB and more): as signed 64-bit
+    // unsigned 32 x 32 -> 64 products (prefill_route() refuses block strides of 4 GB and more): as signed 64-bit
     // arithmetic the four descriptor bases of a stage cost ~90 scalar instructions
     const uint32_t pidu = static_cast<uint32_t>(pid), inp = static_cast<uint32_t>(inpage);
     const i32x4 rk = srd_of(kbase_h + static_cast<uint64_t>(pidu) * static_cast<uint32_t>(a.k_block_stride) +
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
   }
   if constexpr (kSparse) {
     const int mask_tm = min(wg_pos0 >> 7, a.mask_tiles_m - 1);
-    const int cols = min(a.mask_tiles_kv, kMaskCols);
+    const int cols = min(a.mask_tiles_kv, kPrefillMaskCols);
     for (int col = tid; col < cols; col += kThreads) {
       uint32_t bits = 0;
       for (int gq = 0; gq < G; ++gq)
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
       for (int nb = 0; nb < kNB; ++nb) bit[nb] = true;
       return true;
     } else {
-      const int col = min(t, min(a.mask_tiles_kv, kMaskCols) - 1);  // t: stage = mask column
+      const int col = min(t, min(a.mask_tiles_kv, kPrefillMaskCols) - 1);  // t: stage = mask column
       const uint32_t bits = s_mask[col];
 #pragma unroll
       for (int nb = 0; nb < kNB; ++nb) bit[nb] = ((bits >> row_hl[nb]) & 1u) != 0;
@@ -403,14 +401,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
         w = __builtin_amdgcn_cvt_pk_fp8_f32(p[2], p[3], w, true);
         pf[nb][tb] = w;
       }
-      // rescale only when some row's maximum moved (past the first stages of a long row it rarely does)
-      if (__builtin_amdgcn_ballot_w64(m_new != m_run[nb]) != 0) {
-        const float alpha = __builtin_amdgcn_exp2f(m_run[nb] - m_use);
-        l_run[nb] *= alpha;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) o[nb][jj] *= alpha;
-        m_run[nb] = m_new;
-      }
+      rescale_if_max_moved(m_new, m_use, m_run[nb], l_run[nb], o[nb]);
       l_run[nb] += psum;
 
       if constexpr (kSparse) pv_block(nb, pf[nb]);  // block-sparse: right here, and not at all for a block that is off
@@ -480,92 +471,74 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_fp8_kernel(const Args a) 
 }  // namespace prefill
 }  // namespace hpc
 
-// reference: attention_with_kvcache_prefill_{qpertoken_perhead_kvpertensor,qkpertoken_perhead_vperhead}_fp8_async
-// (src/attention/prefill/prefill.h; argument meaning kept; TMA scratch dropped).  quant_type 1 / 0 as in
-// hpc_attention_decode_fp8_async; kscale strides (bytes) only for quant_type 0.
-static int prefill_fp8_launch(const void* block_mask_ptr, int mask_tiles_m, int mask_tiles_kv,
-    void* y_ptr, const void* q_ptr, const void* kcache_ptr, const void* vcache_ptr, const void* qscale_ptr,
-    const void* kscale_ptr, const void* vscale_ptr, const void* cu_seqlens_q_ptr, const void* block_ids_ptr,
-    const void* seqlens_kvcache_ptr, int quant_type, int num_batch, int max_seqlens_q, int max_seqlens_q_pad,
-    int num_dim_qk, int num_dim_v, int num_head_q, int num_head_kv, int block_size, int num_seq_max_blocks,
-    int ldY, int ldQ, int64_t kcache_block_stride, int64_t kcache_token_stride, int64_t kcache_head_stride,
-    int64_t vcache_block_stride, int64_t vcache_token_stride, int64_t vcache_head_stride,
-    int64_t kscale_block_stride_bytes, int64_t kscale_row_stride_bytes, int64_t kscale_head_stride_bytes,
-    hipStream_t stream) {
+using namespace hpc;
+
+#ifdef HPC_DEV
+// development (tests/test_prefill_route.py): prefill_route() on flat arrays, the members of PrefillCall and PrefillRoute in their order
+extern "C" int hpc_dev_prefill_route(const int64_t* call, int n_in, int* route, int n_out) {
+  if (!call || !route || n_in != 20 || n_out != 12) return HPC_ERR_INVALID;
+  const auto i = [call](int k) { return static_cast<int>(call[k]); };
+  const PrefillCall c{i(0), i(1), call[2] != 0, i(3), i(4), i(5), i(6), i(7), i(8), i(9), i(10), i(11), i(12), i(13),
+                      call[14], call[15], call[16], call[17], call[18], call[19]};
+  const PrefillRoute r = prefill_route(c);
+  const int out[12] = {r.code, r.empty, r.g_shift, r.page_shift, r.quant, r.sparse, r.by_head, r.v_perm, r.grid_x, r.grid_y, r.grid_z, r.threads};
+  for (int k = 0; k < 12; ++k) route[k] = out[k];
+  return HPC_OK;
+}
+#endif
+
+namespace {
+// What a C entry was given (include/hpc_amd.h), in the order of the block-sparse entry's arguments; the dense entry has no mask.
+// K / V strides in elements (= bytes), K-scale strides in bytes (quant_type 0 only).
+struct Entry {
+  int which;  // kPrefillFp8 or kPrefillFp8Sparse
+  void* y;
+  const void *q, *kcache, *vcache, *qscale, *kscale, *vscale, *cu_seqlens_q, *block_ids, *seqlens_kv, *block_mask;
+  int mask_tiles_m, mask_tiles_kv, quant_type, num_batch, max_seqlens_q, qs_pad, num_dim_qk, num_dim_v, num_head_q, num_head_kv;
+  int block_size, max_blocks, ldY, ldQ;
+  int64_t k_block_stride, k_token_stride, k_head_stride, v_block_stride, v_token_stride, v_head_stride;
+  int64_t ks_block_stride, ks_row_stride, ks_head_stride;
+  hipStream_t stream;
+};
+
+// check the operands, ask the route, fill the kernel's argument block (in the order of its members) and launch
+int run(const Entry& e) {
   using namespace hpc::prefill;
-  if (!y_ptr || !q_ptr || !kcache_ptr || !vcache_ptr || !qscale_ptr || !kscale_ptr || !vscale_ptr ||
-      !cu_seqlens_q_ptr || !block_ids_ptr || !seqlens_kvcache_ptr)
+  if (e.which == kPrefillFp8Sparse && !prefill_mask_page_ok(e.block_size)) return HPC_ERR_UNSUPPORTED;  // the route's first refusal
+  if (!e.y || !e.q || !e.kcache || !e.vcache || !e.qscale || !e.kscale || !e.vscale || !e.cu_seqlens_q || !e.block_ids || !e.seqlens_kv)
     return HPC_ERR_INVALID;
-  if (quant_type != 0 && quant_type != 1) return HPC_ERR_INVALID;
-  if (num_batch <= 0 || max_seqlens_q <= 0) return num_batch < 0 || max_seqlens_q < 0 ? HPC_ERR_INVALID : HPC_OK;
-  if (num_dim_qk != 128 || num_dim_v != 128) return HPC_ERR_UNSUPPORTED;
-  if (block_size != 16 && block_size != 32 && block_size != 64) return HPC_ERR_UNSUPPORTED;
-  if (quant_type == 0 && block_size < 32) return HPC_ERR_UNSUPPORTED;
-  if (num_head_kv <= 0 || num_head_q % num_head_kv) return HPC_ERR_INVALID;
-  const int group = num_head_q / num_head_kv;
-  if (group != 1 && group != 2 && group != 4 && group != 8 && group != 16) return HPC_ERR_UNSUPPORTED;
-  if ((ldQ & 15) || (ldY & 7) || (kcache_token_stride & 15) || (vcache_token_stride & 7) ||
-      (kcache_head_stride & 15) || (vcache_head_stride & 7) || (kcache_block_stride & 15) ||
-      (vcache_block_stride & 7))
-    return HPC_ERR_UNSUPPORTED;
-  Args a{};
-  a.q = q_ptr;
-  a.kcache = kcache_ptr;
-  a.vcache = vcache_ptr;
-  a.block_ids = static_cast<const int*>(block_ids_ptr);
-  a.cu_seqlens_q = static_cast<const int*>(cu_seqlens_q_ptr);
-  a.seqlens_kv = static_cast<const int*>(seqlens_kvcache_ptr);
-  a.y = static_cast<uint16_t*>(y_ptr);
-  a.qscale = static_cast<const float*>(qscale_ptr);
-  a.kscale = static_cast<const float*>(kscale_ptr);
-  a.vscale = static_cast<const float*>(vscale_ptr);
-  a.block_mask = static_cast<const uint8_t*>(block_mask_ptr);
-  // head-major 16-row blocks let a block skip masked-out tiles (block-sparse); dense attention measured ~8 %
-  // faster with every wave holding all G heads of a few positions (key kDevPrefillRowMap overrides: 1 = by head, 2 = by position)
-  a.by_head = group <= 8 && (hpc_dev_tuning_get(kDevPrefillRowMap) ? hpc_dev_tuning_get(kDevPrefillRowMap) == 1 : block_mask_ptr != nullptr);
-  a.mask_tiles_m = mask_tiles_m;
-  a.mask_tiles_kv = mask_tiles_kv;
-  if (block_mask_ptr && (mask_tiles_m <= 0 || mask_tiles_kv <= 0)) return HPC_ERR_INVALID;
-  if (block_mask_ptr && mask_tiles_kv > kMaskCols) return HPC_ERR_UNSUPPORTED;  // > 64k tokens of mask columns
-  a.num_batch = num_batch;
-  a.num_head_q = num_head_q;
-  a.num_head_kv = num_head_kv;
-  a.g_shift = group == 1 ? 0 : (group == 2 ? 1 : (group == 4 ? 2 : (group == 8 ? 3 : 4)));
-  a.page_shift = block_size == 64 ? 6 : (block_size == 32 ? 5 : 4);
-  a.max_blocks = num_seq_max_blocks;
-  a.qs_pad = max_seqlens_q_pad;
-  a.ldq = ldQ;
-  a.ldy = ldY;
-  a.k_block_stride = kcache_block_stride;
-  a.k_token_stride = kcache_token_stride;
-  a.k_head_stride = kcache_head_stride;
-  a.v_block_stride = vcache_block_stride;
-  a.v_token_stride = vcache_token_stride;
-  a.v_head_stride = vcache_head_stride;
-  a.ks_block_stride = kscale_block_stride_bytes;
-  a.ks_row_stride = kscale_row_stride_bytes;
-  a.ks_head_stride = kscale_head_stride_bytes;
-  a.scale_log2 = 1.4426950408889634f / 11.313708498984761f;  // log2(e) / sqrt(128)
-  // the kernel forms page offsets as unsigned 32 x 32 -> 64 products
-  if (kcache_block_stride <= 0 || vcache_block_stride <= 0 || kcache_token_stride <= 0 || vcache_token_stride <= 0 ||
-      kcache_block_stride >= (1ll << 32) || vcache_block_stride >= (1ll << 32) ||
-      kcache_token_stride * block_size >= (1ll << 32) || vcache_token_stride * block_size >= (1ll << 32))
-    return HPC_ERR_UNSUPPORTED;
-  const long rows = static_cast<long>(max_seqlens_q) * group;
-  dim3 grid(static_cast<unsigned>((rows + kWaves * kRowsPerWave - 1) / (kWaves * kRowsPerWave)), num_head_kv, num_batch);
-  if (grid.z > 65535 || grid.y > 65535) return HPC_ERR_UNSUPPORTED;
+  const PrefillRoute r = prefill_route({e.which, e.quant_type, e.block_mask != nullptr, e.mask_tiles_m, e.mask_tiles_kv, e.num_batch,
+                                        e.max_seqlens_q, e.num_dim_qk, e.num_dim_v, e.num_head_q, e.num_head_kv, e.block_size, e.ldQ, e.ldY,
+                                        e.k_block_stride, e.k_token_stride, e.k_head_stride, e.v_block_stride, e.v_token_stride,
+                                        e.v_head_stride});
+  if (r.code != HPC_OK || r.empty) return r.code;
+  const Args a{e.q, e.kcache, e.vcache, static_cast<const int*>(e.block_ids), static_cast<const int*>(e.cu_seqlens_q),
+               static_cast<const int*>(e.seqlens_kv), static_cast<uint16_t*>(e.y),
+               static_cast<const float*>(e.qscale), static_cast<const float*>(e.kscale), static_cast<const float*>(e.vscale),
+               r.by_head, static_cast<const uint8_t*>(e.block_mask), e.mask_tiles_m, e.mask_tiles_kv,
+               e.num_batch, e.num_head_q, e.num_head_kv, r.g_shift, r.page_shift, e.max_blocks, e.qs_pad,
+               e.ldQ, e.ldY,
+               e.k_block_stride, e.k_token_stride, e.k_head_stride,
+               e.v_block_stride, e.v_token_stride, e.v_head_stride,
+               e.ks_block_stride, e.ks_row_stride, e.ks_head_stride,
+               kPrefillScaleLog2};
+  const dim3 grid(r.grid_x, r.grid_y, r.grid_z);
   // default (temporal) cache policy: K/V tiles are re-read by every q tile of the request from L2
-  if (block_mask_ptr) {
-    if (quant_type == 1) prefill_fp8_kernel<1, true><<<grid, kThreads, 0, stream>>>(a);
-    else prefill_fp8_kernel<0, true><<<grid, kThreads, 0, stream>>>(a);
+  if (r.sparse) {
+    if (r.quant == 1) prefill_fp8_kernel<1, true><<<grid, r.threads, 0, e.stream>>>(a);
+    else prefill_fp8_kernel<0, true><<<grid, r.threads, 0, e.stream>>>(a);
   } else {
-    if (quant_type == 1) prefill_fp8_kernel<1, false><<<grid, kThreads, 0, stream>>>(a);
-    else prefill_fp8_kernel<0, false><<<grid, kThreads, 0, stream>>>(a);
+    if (r.quant == 1) prefill_fp8_kernel<1, false><<<grid, r.threads, 0, e.stream>>>(a);
+    else prefill_fp8_kernel<0, false><<<grid, r.threads, 0, e.stream>>>(a);
   }
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
+}  // namespace
 
+// reference: attention_with_kvcache_prefill_{qpertoken_perhead_kvpertensor,qkpertoken_perhead_vperhead}_fp8_async
+// (src/attention/prefill/prefill.h; argument meaning kept; TMA scratch dropped).  quant_type 1 / 0 as in
+// hpc_attention_decode_fp8_async; kscale strides (bytes) only for quant_type 0.
 extern "C" int hpc_attention_with_kvcache_prefill_fp8_async(
     void* y_ptr, const void* q_ptr, const void* kcache_ptr, const void* vcache_ptr, const void* qscale_ptr,
     const void* kscale_ptr, const void* vscale_ptr, const void* cu_seqlens_q_ptr, const void* block_ids_ptr,
@@ -575,12 +548,11 @@ extern "C" int hpc_attention_with_kvcache_prefill_fp8_async(
     int64_t vcache_block_stride, int64_t vcache_token_stride, int64_t vcache_head_stride,
     int64_t kscale_block_stride_bytes, int64_t kscale_row_stride_bytes, int64_t kscale_head_stride_bytes,
     hipStream_t stream) {
-  return prefill_fp8_launch(nullptr, 0, 0, y_ptr, q_ptr, kcache_ptr, vcache_ptr, qscale_ptr, kscale_ptr, vscale_ptr,
-                            cu_seqlens_q_ptr, block_ids_ptr, seqlens_kvcache_ptr, quant_type, num_batch,
-                            max_seqlens_q, max_seqlens_q_pad, num_dim_qk, num_dim_v, num_head_q, num_head_kv,
-                            block_size, num_seq_max_blocks, ldY, ldQ, kcache_block_stride, kcache_token_stride,
-                            kcache_head_stride, vcache_block_stride, vcache_token_stride, vcache_head_stride,
-                            kscale_block_stride_bytes, kscale_row_stride_bytes, kscale_head_stride_bytes, stream);
+  return run({kPrefillFp8, y_ptr, q_ptr, kcache_ptr, vcache_ptr, qscale_ptr, kscale_ptr, vscale_ptr, cu_seqlens_q_ptr, block_ids_ptr,
+              seqlens_kvcache_ptr, nullptr, 0, 0, quant_type, num_batch, max_seqlens_q, max_seqlens_q_pad, num_dim_qk, num_dim_v,
+              num_head_q, num_head_kv, block_size, num_seq_max_blocks, ldY, ldQ, kcache_block_stride, kcache_token_stride,
+              kcache_head_stride, vcache_block_stride, vcache_token_stride, vcache_head_stride, kscale_block_stride_bytes,
+              kscale_row_stride_bytes, kscale_head_stride_bytes, stream});
 }
 
 // reference: attention_with_kvcache_blocksparse_prefill_fp8 (src/attention/entry.cc:264-409): the same
@@ -596,12 +568,9 @@ extern "C" int hpc_attention_with_kvcache_blocksparse_prefill_fp8_async(
     int64_t vcache_block_stride, int64_t vcache_token_stride, int64_t vcache_head_stride,
     int64_t kscale_block_stride_bytes, int64_t kscale_row_stride_bytes, int64_t kscale_head_stride_bytes,
     hipStream_t stream) {
-  if (128 % block_size) return HPC_ERR_UNSUPPORTED;
-  return prefill_fp8_launch(block_mask_ptr, mask_tiles_m, mask_tiles_kv, y_ptr, q_ptr, kcache_ptr, vcache_ptr,
-                            qscale_ptr, kscale_ptr, vscale_ptr, cu_seqlens_q_ptr, block_ids_ptr, seqlens_kvcache_ptr,
-                            quant_type, num_batch, max_seqlens_q, max_seqlens_q_pad, num_dim_qk, num_dim_v,
-                            num_head_q, num_head_kv, block_size, num_seq_max_blocks, ldY, ldQ, kcache_block_stride,
-                            kcache_token_stride, kcache_head_stride, vcache_block_stride, vcache_token_stride,
-                            vcache_head_stride, kscale_block_stride_bytes, kscale_row_stride_bytes,
-                            kscale_head_stride_bytes, stream);
+  return run({kPrefillFp8Sparse, y_ptr, q_ptr, kcache_ptr, vcache_ptr, qscale_ptr, kscale_ptr, vscale_ptr, cu_seqlens_q_ptr, block_ids_ptr,
+              seqlens_kvcache_ptr, block_mask_ptr, mask_tiles_m, mask_tiles_kv, quant_type, num_batch, max_seqlens_q, max_seqlens_q_pad,
+              num_dim_qk, num_dim_v, num_head_q, num_head_kv, block_size, num_seq_max_blocks, ldY, ldQ, kcache_block_stride,
+              kcache_token_stride, kcache_head_stride, vcache_block_stride, vcache_token_stride, vcache_head_stride,
+              kscale_block_stride_bytes, kscale_row_stride_bytes, kscale_head_stride_bytes, stream});
 }

@@ -14,8 +14,11 @@
 // epilogue reuses the staging LDS (aliased), so two workgroups fit a CU.
 // Contiguous form: K/V rows of request b are rows cu_seqlens_q[b] .. of [total_seq, Hkv, 128] tensors
 // (block_ids == null), every q token attends the keys up to itself.
+//
+// Host side: the form, the shifts, the grid and every refusal of both entries are attention_prefill_route.h::prefill_route().
+#include "attention_prefill_route.h"
+#include "attention_prefill_tile.h"
 #include "hpc_common.h"
-#include "hpc_dev.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
@@ -36,11 +39,7 @@ struct Args {
   float scale_log2;
 };
 
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
-constexpr int kNB = 2;
-constexpr int kRowsPerWave = 16 * kNB;
-constexpr float kNegInf = -__builtin_inff();
+using namespace prefill_tile;
 constexpr int kKRow = 256 + 16;             // padded LDS row (bytes)
 constexpr int kTileBytes = 64 * kKRow;      // one K or V tile
 constexpr int kVTileBytes = 64 * 256;       // one V tile: unpadded 256-byte rows, 16-byte chunks XOR-swizzled (transposing reads)
@@ -68,7 +67,6 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_bf16_kernel(const Args a)
   const int q0 = as_const(a.cu_seqlens_q)[b];
   const int Sq = as_const(a.cu_seqlens_q)[b + 1] - q0;
   const int L = a.seqlens_kv ? as_const(a.seqlens_kv)[b] : Sq;
-  constexpr int kWgRows = kWaves * kRowsPerWave;
   // q tiles are handed out last-first: a late tile walks the most KV (causal), so the longest workgroups start first
   // and the grid's tail is made of the short ones
   const int wg_pos0 = ((gridDim.x - 1 - blockIdx.x) * kWgRows) >> a.g_shift;
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_bf16_kernel(const Args a)
       const int pid = __builtin_amdgcn_readfirstlane(
           as_const(a.block_ids)[static_cast<long>(b) * a.max_blocks + (gtok >> a.page_shift)]);
       const int inpage = gtok & page_mask;
-      // unsigned 32 x 32 -> 64 products (the launcher refuses larger strides): a quarter of the scalar instructions
+      // unsigned 32 x 32 -> 64 products (prefill_route() refuses larger strides): a quarter of the scalar instructions
       // of the signed 64-bit form
       const uint32_t pidu = static_cast<uint32_t>(pid), inp = static_cast<uint32_t>(inpage);
       kb = static_cast<long>(static_cast<uint64_t>(pidu) * static_cast<uint32_t>(a.k_block_stride) +
@@ -255,14 +253,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_bf16_kernel(const Args a)
         pf[nb][tb >> 1][(tb & 1) * 2] = pack_bf16x2(p[0], p[1]);
         pf[nb][tb >> 1][(tb & 1) * 2 + 1] = pack_bf16x2(p[2], p[3]);
       }
-      // rescale only when some row's maximum moved (past the first tiles of a long row it rarely does)
-      if (__builtin_amdgcn_ballot_w64(m_new != m_run[nb]) != 0) {
-        const float alpha = __builtin_amdgcn_exp2f(m_run[nb] - m_use);
-        l_run[nb] *= alpha;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) o[nb][jj] *= alpha;
-        m_run[nb] = m_new;
-      }
+      rescale_if_max_moved(m_new, m_use, m_run[nb], l_run[nb], o[nb]);
       l_run[nb] += psum;
     }
 
@@ -363,28 +354,41 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_bf16_kernel(const Args a)
 }  // namespace prefill16
 }  // namespace hpc
 
+using namespace hpc;
+
 namespace {
-int launch_prefill_bf16(hpc::prefill16::Args& a, int max_seqlens_q, int num_head_q, int num_head_kv, int num_batch,
-                        hipStream_t stream) {
+// What a C entry was given (include/hpc_amd.h); K / V strides in elements.  Contiguous K / V (kPrefillBf16): no pages - block_ids and
+// seqlens_kv null, block_size, max_blocks and the block strides 0 -, rows ldK / ldV apart, heads 128 apart.
+struct Entry {
+  int which;  // kPrefillBf16Paged or kPrefillBf16
+  void* y;
+  const void *q, *k, *v, *cu_seqlens_q, *block_ids, *seqlens_kv;
+  int num_batch, max_seqlens_q, num_dim_qk, num_dim_v, num_head_q, num_head_kv, block_size, max_blocks, ldY, ldQ;
+  int64_t k_block_stride, k_token_stride, k_head_stride, v_block_stride, v_token_stride, v_head_stride;
+  hipStream_t stream;
+};
+
+// check the operands, ask the route, fill the kernel's argument block (in the order of its members) and launch
+int run(const Entry& e) {
   using namespace hpc::prefill16;
-  if (num_head_kv <= 0 || num_head_q % num_head_kv) return HPC_ERR_INVALID;
-  const int group = num_head_q / num_head_kv;
-  if (group != 1 && group != 2 && group != 4 && group != 8 && group != 16) return HPC_ERR_UNSUPPORTED;
-  if ((a.ldq & 7) || (a.ldy & 7) || (a.k_token_stride & 7) || (a.v_token_stride & 7) || (a.k_head_stride & 7) ||
-      (a.v_head_stride & 7) || (a.k_block_stride & 7) || (a.v_block_stride & 7))
-    return HPC_ERR_UNSUPPORTED;  // 16-byte vector accesses
-  a.num_batch = num_batch;
-  a.num_head_q = num_head_q;
-  a.num_head_kv = num_head_kv;
-  a.g_shift = group == 1 ? 0 : (group == 2 ? 1 : (group == 4 ? 2 : (group == 8 ? 3 : 4)));
-  a.scale_log2 = 1.4426950408889634f / 11.313708498984761f;  // log2(e) / sqrt(128)
-  const long rows = static_cast<long>(max_seqlens_q) * group;
-  dim3 grid(static_cast<unsigned>((rows + kWaves * kRowsPerWave - 1) / (kWaves * kRowsPerWave)), num_head_kv, num_batch);
-  if (grid.z > 65535 || grid.y > 65535) return HPC_ERR_UNSUPPORTED;
-  if (kHpcDevBuild && hpc_dev_tuning_get(kDevPrefillBf16Perm) == 1)  // development key kDevPrefillBf16Perm = 1: V^T operands built with v_perm_b32 (rounds 3-4)
-    prefill_bf16_kernel<false><<<grid, kThreads, 0, stream>>>(a);
+  if (!e.y || !e.q || !e.k || !e.v || !e.cu_seqlens_q || (e.which == kPrefillBf16Paged && (!e.block_ids || !e.seqlens_kv)))
+    return HPC_ERR_INVALID;
+  const PrefillRoute r = prefill_route({e.which, 0, false, 0, 0, e.num_batch, e.max_seqlens_q, e.num_dim_qk, e.num_dim_v, e.num_head_q,
+                                        e.num_head_kv, e.block_size, e.ldQ, e.ldY, e.k_block_stride, e.k_token_stride, e.k_head_stride,
+                                        e.v_block_stride, e.v_token_stride, e.v_head_stride});
+  if (r.code != HPC_OK || r.empty) return r.code;
+  const Args a{e.q, e.k, e.v, static_cast<const int*>(e.block_ids), static_cast<const int*>(e.cu_seqlens_q),
+               static_cast<const int*>(e.seqlens_kv), static_cast<uint16_t*>(e.y),
+               e.num_batch, e.num_head_q, e.num_head_kv, r.g_shift, r.page_shift, e.max_blocks,
+               e.ldQ, e.ldY,
+               e.k_block_stride, e.k_token_stride, e.k_head_stride,
+               e.v_block_stride, e.v_token_stride, e.v_head_stride,
+               kPrefillScaleLog2};
+  const dim3 grid(r.grid_x, r.grid_y, r.grid_z);
+  if (kHpcDevBuild && r.v_perm)  // the product does not hold that instantiation
+    prefill_bf16_kernel<false><<<grid, r.threads, 0, e.stream>>>(a);
   else
-    prefill_bf16_kernel<true><<<grid, kThreads, 0, stream>>>(a);
+    prefill_bf16_kernel<true><<<grid, r.threads, 0, e.stream>>>(a);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
@@ -399,35 +403,9 @@ extern "C" int hpc_attention_with_kvcache_prefill_bf16_async(
     int num_dim_v, int num_head_q, int num_head_kv, int block_size, int num_seq_max_blocks, int ldY, int ldQ,
     int64_t kcache_block_stride, int64_t kcache_token_stride, int64_t kcache_head_stride,
     int64_t vcache_block_stride, int64_t vcache_token_stride, int64_t vcache_head_stride, hipStream_t stream) {
-  if (!y_ptr || !q_ptr || !kcache_ptr || !vcache_ptr || !cu_seqlens_q_ptr || !block_ids_ptr || !seqlens_kvcache_ptr)
-    return HPC_ERR_INVALID;
-  if (num_batch <= 0 || max_seqlens_q <= 0) return num_batch < 0 || max_seqlens_q < 0 ? HPC_ERR_INVALID : HPC_OK;
-  if (num_dim_qk != 128 || num_dim_v != 128) return HPC_ERR_UNSUPPORTED;
-  if (block_size != 16 && block_size != 32 && block_size != 64) return HPC_ERR_UNSUPPORTED;
-  hpc::prefill16::Args a{};
-  a.q = q_ptr;
-  a.k = kcache_ptr;
-  a.v = vcache_ptr;
-  a.block_ids = static_cast<const int*>(block_ids_ptr);
-  a.cu_seqlens_q = static_cast<const int*>(cu_seqlens_q_ptr);
-  a.seqlens_kv = static_cast<const int*>(seqlens_kvcache_ptr);
-  a.y = static_cast<uint16_t*>(y_ptr);
-  a.page_shift = block_size == 64 ? 6 : (block_size == 32 ? 5 : 4);
-  a.max_blocks = num_seq_max_blocks;
-  a.ldq = ldQ;
-  a.ldy = ldY;
-  a.k_block_stride = kcache_block_stride;
-  a.k_token_stride = kcache_token_stride;
-  a.k_head_stride = kcache_head_stride;
-  a.v_block_stride = vcache_block_stride;
-  a.v_token_stride = vcache_token_stride;
-  a.v_head_stride = vcache_head_stride;
-  // the kernel forms page offsets (in elements) as unsigned 32 x 32 -> 64 products
-  if (kcache_block_stride <= 0 || vcache_block_stride <= 0 || kcache_token_stride <= 0 || vcache_token_stride <= 0 ||
-      kcache_block_stride >= (1ll << 31) || vcache_block_stride >= (1ll << 31) ||
-      kcache_token_stride * block_size >= (1ll << 31) || vcache_token_stride * block_size >= (1ll << 31))
-    return HPC_ERR_UNSUPPORTED;
-  return launch_prefill_bf16(a, max_seqlens_q, num_head_q, num_head_kv, num_batch, stream);
+  return run({kPrefillBf16Paged, y_ptr, q_ptr, kcache_ptr, vcache_ptr, cu_seqlens_q_ptr, block_ids_ptr, seqlens_kvcache_ptr, num_batch,
+              max_seqlens_q, num_dim_qk, num_dim_v, num_head_q, num_head_kv, block_size, num_seq_max_blocks, ldY, ldQ, kcache_block_stride,
+              kcache_token_stride, kcache_head_stride, vcache_block_stride, vcache_token_stride, vcache_head_stride, stream});
 }
 
 // reference: attention_prefill_bf16_async (src/attention/prefill/prefill.h; entry src/attention/entry.cc:15-81):
@@ -436,26 +414,6 @@ extern "C" int hpc_attention_prefill_bf16_async(void* y_ptr, const void* q_ptr, 
                                                 const void* cu_seqlens_q_ptr, int num_batch, int max_seqlens_q,
                                                 int num_dim_qk, int num_dim_v, int num_head_q, int num_head_kv,
                                                 int ldY, int ldQ, int ldK, int ldV, hipStream_t stream) {
-  if (!y_ptr || !q_ptr || !k_ptr || !v_ptr || !cu_seqlens_q_ptr) return HPC_ERR_INVALID;
-  if (num_batch <= 0 || max_seqlens_q <= 0) return num_batch < 0 || max_seqlens_q < 0 ? HPC_ERR_INVALID : HPC_OK;
-  if (num_dim_qk != 128 || num_dim_v != 128) return HPC_ERR_UNSUPPORTED;
-  hpc::prefill16::Args a{};
-  a.q = q_ptr;
-  a.k = k_ptr;
-  a.v = v_ptr;
-  a.block_ids = nullptr;
-  a.cu_seqlens_q = static_cast<const int*>(cu_seqlens_q_ptr);
-  a.seqlens_kv = nullptr;
-  a.y = static_cast<uint16_t*>(y_ptr);
-  a.page_shift = 6;
-  a.max_blocks = 0;
-  a.ldq = ldQ;
-  a.ldy = ldY;
-  a.k_block_stride = 0;
-  a.k_token_stride = ldK;
-  a.k_head_stride = 128;
-  a.v_block_stride = 0;
-  a.v_token_stride = ldV;
-  a.v_head_stride = 128;
-  return launch_prefill_bf16(a, max_seqlens_q, num_head_q, num_head_kv, num_batch, stream);
+  return run({kPrefillBf16, y_ptr, q_ptr, k_ptr, v_ptr, cu_seqlens_q_ptr, nullptr, nullptr, num_batch, max_seqlens_q, num_dim_qk,
+              num_dim_v, num_head_q, num_head_kv, 0, 0, ldY, ldQ, 0, ldK, 128, 0, ldV, 128, stream});
 }

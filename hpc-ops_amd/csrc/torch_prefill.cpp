@@ -66,7 +66,7 @@ at::Tensor prefill_fp8(const at::Tensor& q, const at::Tensor& kcache, const at::
   at::Tensor y = prefill_output(q, output, dim_v);
   if (total_q == 0) return y;
   if (blocksparse) {
-    TORCH_CHECK(128 % block_size == 0, "unsupported block_size for FP8 blocksparse prefill");
+    TORCH_CHECK(block_size > 0 && 128 % block_size == 0, "unsupported block_size for FP8 blocksparse prefill");
     const int64_t tiles_m = (max_seqlens_q + 127) / 128;
     int64_t tiles_kv = 0;
     if (block_mask.has_value()) {

@@ -28,7 +28,7 @@ def test_product_library_has_no_development_registers():
     assert not leaked, f"development symbols exported by the product library: {leaked}"
     dev = _exported_symbols(ROOT / "hpc-ops_amd" / "hpc" / "libhpc_amd_dev.so")
     for sym in ("hpc_dev_tuning_set", "hpc_dev_tuning_get", "hpc_dev_decode_prof_buffer", "hpc_dev_allreduce_loopback_ht",
-                "hpc_dev_allreduce_loopback_ll", "hpc_dev_ggemm_route", "hpc_dev_p8_prof_buffer"):
+                "hpc_dev_allreduce_loopback_ll", "hpc_dev_ggemm_route", "hpc_dev_p8_prof_buffer", "hpc_dev_prefill_route"):
         assert sym in dev, sym + " missing from the development build"
         assert sym not in prod
     assert any(s.startswith("hpc_") for s in prod)  # the scan sees the C-ABI at all

@@ -2,7 +2,8 @@
 // attention_decode_mla_bf16.  Ours only (no reference op; pinned to the PyTorch statement tests/mla_ref.py), so under its own
 // namespace: torch.ops.hpc_mla.* (hpc:: holds the reference's surface).  With `output` (and `output_lse` where an lse is wanted)
 // given nothing is allocated per call beyond the cached scratch and the call captures into a hipGraph.  Nothing here reads the
-// values of num_seq_kvcache.  No kernels here.
+// values of num_seq_kvcache.  Below it rope_norm_store_kv, the op that writes that cache and the RoPE columns of q
+// (csrc/mla_store.hip).  No kernels here.
 #include "torch_common.h"
 
 using namespace hpc_torch;
@@ -68,9 +69,113 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q
   return {out, lse};
 }
 
+// ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------
+// A bf16 tensor whose last dim (of `width`) is contiguous, every other stride a multiple of 8 elements and wide enough that
+// rows (and heads) do not overlap, base 16-byte aligned: kv_a, out_ckv [rows, 576]; q_pe, out_q_pe [rows, H, 64].
+void check_rows_bf16(const at::Tensor& t, const char* name, const at::Tensor& like, at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on kv_a's device");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
+  TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
+  const int64_t width = shape.back();
+  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
+  for (int64_t d = 0; d + 1 < t.dim(); ++d)
+    TORCH_CHECK(t.stride(d) % 8 == 0 && (t.stride(d) >= width || t.size(d) <= 1), name, " stride ", d,
+                " must be a multiple of 8 elements and at least ", width, ", got ", t.stride(d));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, at::ScalarType dtype, int64_t dim) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on kv_a's device");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype == at::kInt ? "int32" : "float32");
+  TORCH_CHECK(t.dim() == dim && t.is_contiguous(), name, " must be a contiguous ", dim, "-d tensor");
+}
+
+// Returns out_q_pe (the caller's, or a fresh contiguous one); an empty tensor when q_pe is not given.  With out_q_pe (or no
+// q_pe) nothing is allocated and the call captures into a hipGraph.  Nothing here reads the values of num_seqlen_per_req,
+// q_index or block_ids.
+at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
+                              const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index,
+                              const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
+                              const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
+                              bool interleaved) {
+  TORCH_CHECK(kv_a.is_cuda(), "kv_a tensor must be cuda");
+  TORCH_CHECK(kv_a.dim() == 2 && kv_a.size(1) == 576, "kv_a must be [rows, 576]");
+  const int64_t rows = kv_a.size(0);
+  check_rows_bf16(kv_a, "kv_a", kv_a, {rows, 576});
+  check_table(cos_sin, "cos_sin", kv_a, at::kFloat, 2);
+  TORCH_CHECK(cos_sin.size(1) == 64 && cos_sin.size(0) > 0, "cos_sin must be [max_pos, 64] with max_pos > 0");
+  check_table(kv_norm_weight, "kv_norm_weight", kv_a, at::kFloat, 1);
+  TORCH_CHECK(kv_norm_weight.size(0) == 512, "kv_norm_weight must be [512]");
+  check_table(num_seqlen_per_req, "num_seqlen_per_req", kv_a, at::kInt, 1);
+  check_table(q_index, "q_index", kv_a, at::kInt, 1);
+  check_table(block_ids, "block_ids", kv_a, at::kInt, 2);
+  const int64_t num_req = num_seqlen_per_req.size(0);
+  TORCH_CHECK(q_index.size(0) == num_req + 1, "q_index must be [num_req + 1] = [", num_req + 1, "]");
+  TORCH_CHECK(block_ids.size(0) == num_req, "block_ids must have num_req = ", num_req, " rows");
+  TORCH_CHECK(ckv_cache.has_value() || out_ckv.has_value(), "one of ckv_cache and out_ckv must be given");
+  TORCH_CHECK(q_pe.has_value() || !out_q_pe.has_value(), "out_q_pe needs q_pe");
+  TORCH_CHECK(cos_sin.size(0) <= INT32_MAX && rows <= INT32_MAX && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX,
+              "sizes beyond int32");
+
+  int64_t page = 16, block_stride = 0, token_stride = 576, num_blocks = 0;
+  if (ckv_cache.has_value()) {
+    const at::Tensor& c = *ckv_cache;
+    TORCH_CHECK(c.is_cuda() && c.device() == kv_a.device(), "ckv_cache must be on kv_a's device");
+    TORCH_CHECK(c.scalar_type() == at::kBFloat16, "ckv_cache dtype must be bfloat16");
+    TORCH_CHECK(c.dim() == 3 && c.size(2) == 576, "ckv_cache must be [num_blocks, block_size, 576]");
+    page = c.size(1), block_stride = c.stride(0), token_stride = c.stride(1), num_blocks = c.size(0);
+    TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, "block_size must be 16, 32, 64 or 128, got ", page);
+    TORCH_CHECK(c.stride(2) == 1, "ckv_cache must have a contiguous last dim");
+    TORCH_CHECK(token_stride >= 576 && token_stride % 8 == 0 && block_stride % 8 == 0 && block_stride >= 0,
+                "ckv_cache token stride must be >= 576 and, like the block stride, a multiple of 8 elements; got ", token_stride,
+                " and ", block_stride);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, "ckv_cache must be 16-byte aligned");
+    TORCH_CHECK(num_blocks <= INT32_MAX, "sizes beyond int32");
+  }
+  if (out_ckv.has_value()) check_rows_bf16(*out_ckv, "out_ckv", kv_a, {rows, 576});
+  int64_t h = 0;
+  at::Tensor oq = at::empty({0}, kv_a.options());
+  if (q_pe.has_value()) {
+    TORCH_CHECK(q_pe->dim() == 3 && q_pe->size(0) == rows && q_pe->size(2) == 64, "q_pe must be [rows, num_head, 64]");
+    h = q_pe->size(1);
+    TORCH_CHECK(h >= 1 && h <= 128, "num_head must be 1 .. 128, got ", h);
+    check_rows_bf16(*q_pe, "q_pe", kv_a, {rows, h, 64});
+    if (out_q_pe.has_value()) {
+      check_rows_bf16(*out_q_pe, "out_q_pe", kv_a, {rows, h, 64});
+      oq = *out_q_pe;
+      TORCH_CHECK(rows <= 1 || oq.stride(0) >= (h - 1) * oq.stride(1) + 64, "out_q_pe stride 0 = ", oq.stride(0),
+                  " lets its rows overlap: num_head heads of stride ", oq.stride(1), " need ", (h - 1) * oq.stride(1) + 64);
+      if (rows > 0) {  // q_pe and out_q_pe may share memory only as the same tensor (in place)
+        const bool in_place = oq.data_ptr() == q_pe->data_ptr() && oq.strides() == q_pe->strides();
+        const auto lo = [](const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()); };
+        const auto hi = [&](const at::Tensor& t) { return lo(t) + 2 * ((rows - 1) * t.stride(0) + (h - 1) * t.stride(1) + 64); };
+        TORCH_CHECK(in_place || lo(oq) >= hi(*q_pe) || lo(*q_pe) >= hi(oq),
+                    "out_q_pe overlaps q_pe without being the same tensor: only the exact in-place form is supported");
+      }
+    } else {
+      oq = at::empty({rows, h, 64}, kv_a.options());
+    }
+  }
+  if (rows == 0 || num_req == 0) return oq;  // nothing to launch
+  const bool with_q = q_pe.has_value();
+  const int rc = hpc_mla_rope_norm_store_kv_async(
+      ptr(ckv_cache), ptr(out_ckv), with_q ? oq.data_ptr() : nullptr, ptr(kv_a), ptr(q_pe),
+      static_cast<const float*>(cos_sin.data_ptr()), static_cast<const float*>(kv_norm_weight.data_ptr()),
+      static_cast<const int*>(num_seqlen_per_req.data_ptr()), static_cast<const int*>(q_index.data_ptr()),
+      static_cast<const int*>(block_ids.data_ptr()), i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)),
+      i32(num_blocks), i32(cos_sin.size(0)), block_stride, token_stride, kv_a.stride(0),
+      out_ckv.has_value() ? out_ckv->stride(0) : 576, with_q ? q_pe->stride(0) : 0, with_q ? q_pe->stride(1) : 0,
+      with_q ? oq.stride(0) : 0, with_q ? oq.stride(1) : 0, static_cast<float>(eps), interleaved ? 1 : 0, stream_of(kv_a));
+  HPC_LAUNCH_CHECK(rc, "mla_rope_norm_store_kv");
+  return oq;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hpc_mla, m) {
+  m.def(
+      "rope_norm_store_kv(Tensor? ckv_cache, Tensor kv_a, Tensor cos_sin, Tensor kv_norm_weight, Tensor num_seqlen_per_req, "
+      "Tensor q_index, Tensor block_ids, Tensor? q_pe, Tensor? out_q_pe, Tensor? out_ckv, float eps, bool interleaved) -> Tensor");
   m.def(
       "attention_decode_mla_bf16(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seq_kvcache, float softmax_scale, "
       "int mtp, bool new_kv_included, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
@@ -78,4 +183,7 @@ TORCH_LIBRARY(hpc_mla, m) {
   m.def("_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMla); });
 }
 
-TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) { m.impl("attention_decode_mla_bf16", &attention_decode_mla_bf16); }
+TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
+  m.impl("attention_decode_mla_bf16", &attention_decode_mla_bf16);
+  m.impl("rope_norm_store_kv", &rope_norm_store_kv);
+}

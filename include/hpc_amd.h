@@ -486,6 +486,40 @@ int hpc_attention_decode_mla_bf16_async(void* out, float* lse, const void* q, co
                                         int new_kv_included, int splits, void* workspace, int64_t workspace_bytes,
                                         hpc_stream_t stream);
 
+/* ---- MLA latent-cache write: kv_a RMSNorm + RoPE + paged store, bf16 (csrc/mla_store.hip) ------------------------------------
+ * No reference kernel exists; the semantics are the PyTorch statement tests/mla_store_ref.py.  The producer of the cache and of
+ * the RoPE columns of q that hpc_attention_decode_mla_bf16_async reads.  Row r of kv_a is one new token; its request b is the
+ * last one with q_index[b] <= r and its position pos = num_seqlen_per_req[b] - (q_index[b + 1] - r), as in
+ * hpc_rope_norm_store_kv_async; rows at or past q_index[num_req] and rows with pos < 0 belong to no request.  In fp32 with one
+ * rounding to bf16:
+ *   lat[:512] = kv_a[r, :512] / sqrt(mean(kv_a[r, :512]^2) + eps) * kv_norm_weight
+ *   lat[512:] = rot(kv_a[r, 512:576], cos_sin[pos])            out_q_pe[r, h, :] = rot(q_pe[r, h, :], cos_sin[pos])
+ *   ckv_cache[block_ids[b, pos / block_size], pos % block_size, :576] = lat    and / or    out_ckv[r, :] = lat
+ * rot turns the pair (a, b) into (a cos_i - b sin_i, b cos_i + a sin_i), cos_i = cos_sin[pos, i], sin_i = cos_sin[pos, 32 + i],
+ * i < 32; the pair is elements (2i, 2i + 1) with interleaved != 0 (GPT-J style) and (i, i + 32) with 0 (neox).
+ * kv_a bf16 [num_rows, 576] and out_ckv bf16 [num_rows, 576] with row strides; q_pe / out_q_pe bf16 [num_rows, num_head, 64]
+ * with row and head strides (out_q_pe may be q_pe: in place), both NULL to process the latent rows only; ckv_cache as in
+ * hpc_attention_decode_mla_bf16_async (token (page, t) at ckv_cache + page * ckv_block_stride + t * ckv_token_stride); one of
+ * ckv_cache and out_ckv may be NULL.  All strides in elements and multiples of 8, the token stride and (with more than
+ * one row) the row strides of kv_a and out_ckv >= 576, the head and row strides of q_pe and out_q_pe >= 64 (with more than one
+ * head / row), the row stride of out_q_pe >= (num_head - 1) * its head stride + 64, out_q_pe either q_pe itself with q_pe's strides
+ * or disjoint from it, every base 16-byte aligned.  cos_sin f32 [max_pos, 64], kv_norm_weight f32 [512], num_seqlen_per_req int32 [num_req], q_index int32
+ * [num_req + 1], block_ids int32 [num_req, max_blocks], all ON THE DEVICE and never read by the host.  Only the 576 columns
+ * of the new tokens' cells are written in the cache (no tail is cleared); rows of no request store nothing there and are
+ * written as zeros in out_ckv and out_q_pe.  The kernel trusts no device value with an address: the table index is clamped to
+ * max_pos - 1 (the result of such a row is unspecified), a token is not stored when pos / block_size >= max_blocks or when its
+ * page id is outside [0, num_blocks).
+ * HPC_ERR_INVALID: null pointers, neither destination, one of q_pe / out_q_pe without the other, negative counts, max_pos 0;
+ * HPC_ERR_UNSUPPORTED: num_head outside 1 .. 128, block_size outside 16 / 32 / 64 / 128, the strides, alignment.  num_rows == 0
+ * or num_req == 0 launches nothing.  Every check is made on the host before any device call. */
+int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe,
+                                     const float* cos_sin, const float* kv_norm_weight, const int* num_seqlen_per_req,
+                                     const int* q_index, const int* block_ids, int num_rows, int num_req, int num_head,
+                                     int block_size, int max_blocks, int num_blocks, int max_pos, int64_t ckv_block_stride,
+                                     int64_t ckv_token_stride, int64_t kv_a_row_stride, int64_t out_ckv_row_stride,
+                                     int64_t q_pe_row_stride, int64_t q_pe_head_stride, int64_t out_q_pe_row_stride,
+                                     int64_t out_q_pe_head_stride, float eps, int interleaved, hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

@@ -26,7 +26,15 @@
 // writes nothing, and the merge kernel computes the same piece count and never reads it.  A piece stores its running maximum,
 // its sum and its UNNORMALISED fp32 output; the merge sums exp2(m_p - M) * O_p in piece order and divides once (no float
 // atomics, bit-identical from call to call; exact where the softmax is uniform and the length a power of two).
+//
+// FP8 latent cache (kFp8, hpc_attention_decode_mla_fp8_async): the row of mla_fp8_format.h - 512 e4m3 codes, four fp32 scales,
+// the 64 RoPE columns in bf16, 656 B.  Only the gather differs: thread (rr, sub) stages per row the four 16-byte code chunks
+// sub + 8 i (chunk sub + 8 i lies in scale group i), the scale quad and RoPE chunk sub - 12 quads where the bf16 form stages
+// 18 - and the commit turns each code chunk into 16 bf16 (cvt to fp32, ONE fp32 multiply by the group's scale, RNE pack) stored
+// as two 16-byte quads at element column 16 (sub + 8 i).  The LDS image is byte for byte what the bf16 form builds from the
+// dequantised cache, and everything behind it is the same code: the two ops agree bit for bit on such a pair of caches.
 #include "attention_decode_mla_route.h"
+#include "mla_fp8_format.h"
 #include "hpc_amd.h"
 #include "hpc_common.h"
 
@@ -86,7 +94,21 @@ __device__ __forceinline__ void emit_ml(const Args& a, int piece, int64_t grow, 
   }
 }
 
-template <bool kNarrow>
+// 16 e4m3 codes -> 16 bf16 = bf16_rne(fp32(code) * scale): the dequantisation of mla_fp8_format.h
+__device__ __forceinline__ void dequant16(const u32x4 codes, const float scale, u32x4& lo, u32x4& hi) {
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), false);
+    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), true);
+    w[2 * j] = pack_bf16x2(a[0] * scale, a[1] * scale);
+    w[2 * j + 1] = pack_bf16x2(b[0] * scale, b[1] * scale);
+  }
+  lo = u32x4{w[0], w[1], w[2], w[3]};
+  hi = u32x4{w[4], w[5], w[6], w[7]};
+}
+
+template <bool kNarrow, bool kFp8>
 __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Args a) {
   __shared__ __attribute__((aligned(16))) uint8_t s_mem[kLds];
   constexpr int kTB = kNarrow ? 1 : 4;  // 16-token blocks a wave takes of a tile
@@ -123,7 +145,8 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   // ---- gather: thread (rr, sub) takes chunks sub + 8 i of rows rr and rr + 32 ----
   const int rr = tid >> 3, sub = tid & 7;
   const int* pages = a.block_ids + static_cast<int64_t>(b) * a.max_blocks;
-  u32x4 stg[2][9];
+  constexpr int kStage = kFp8 ? 6 : 9;  // 16-byte quads staged per row: 4 code chunks + the scales + 1 RoPE chunk, or 9 bf16 chunks
+  u32x4 stg[2][kStage];
   // the page ids of the rows this thread loads next, looked up one tile ahead: the row loads do not wait for the page table
   int page[2];
   auto lookup = [&](int t0) {
@@ -140,11 +163,18 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
       if (tok < p1) {
         const uint8_t* src = a.ckv + static_cast<int64_t>(page[p]) * a.block_stride_bytes +
                              static_cast<int64_t>(tok & ((1 << a.page_shift) - 1)) * a.token_stride_bytes + sub * 16;
+        if constexpr (kFp8) {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) stg[p][i] = ld16(src + i * 128);
-      } else {
+          for (int i = 0; i < 4; ++i) stg[p][i] = ld16(src + kMlaFp8CodesAt + i * 128);
+          stg[p][4] = ld16(src - sub * 16 + kMlaFp8ScalesAt);  // the same quad for the eight threads of a row
+          stg[p][5] = ld16(src + kMlaFp8RopeAt);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) stg[p][i] = u32x4{0, 0, 0, 0};
+          for (int i = 0; i < 9; ++i) stg[p][i] = ld16(src + i * 128);
+        }
+      } else {  // codes 0 x scale 0: zeros in the image, like the bf16 form's
+#pragma unroll
+        for (int i = 0; i < kStage; ++i) stg[p][i] = u32x4{0, 0, 0, 0};
       }
     }
     lookup(t0 + kMlaKvTile);
@@ -153,8 +183,19 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       uint8_t* dst = s_mem + buf * kBufBytes + (rr + 32 * p) * kRowBytes + sub * 16;
+      if constexpr (kFp8) {
 #pragma unroll
-      for (int i = 0; i < 9; ++i) *reinterpret_cast<u32x4*>(dst + i * 128) = stg[p][i];
+        for (int i = 0; i < 4; ++i) {  // chunk sub + 8 i: columns 16 (sub + 8 i) .. + 15, all in scale group i
+          u32x4 lo, hi;
+          dequant16(stg[p][i], __uint_as_float(stg[p][4][i]), lo, hi);
+          *reinterpret_cast<u32x4*>(dst + sub * 16 + i * 256) = lo;
+          *reinterpret_cast<u32x4*>(dst + sub * 16 + i * 256 + 16) = hi;
+        }
+        *reinterpret_cast<u32x4*>(dst + kMlaDimV * 2) = stg[p][5];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) *reinterpret_cast<u32x4*>(dst + i * 128) = stg[p][i];
+      }
     }
   };
 
@@ -353,20 +394,24 @@ extern "C" int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int n
   return r.code;
 }
 
-extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
-                                                   const int* block_ids_ptr, const int* num_seq_kvcache_ptr, int num_batch,
-                                                   int num_seq_q, int num_head, int block_size, int max_blocks,
-                                                   int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
-                                                   int new_kv_included, int splits, void* workspace_ptr,
-                                                   int64_t workspace_bytes, hipStream_t stream) {
+namespace {
+// Both launchers: the checks, the route and the launches.  The cache's strides come in units of `unit` bytes (2: the bf16
+// cache's elements, 1: the FP8 cache's bytes); a token's row is `row_units` of them and both strides are multiples of
+// `align_units` (16 bytes either way).
+template <bool kFp8>
+int mla_decode_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr, const int* block_ids_ptr,
+                      const int* num_seq_kvcache_ptr, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
+                      int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale, int new_kv_included, int splits,
+                      void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
   using namespace hpc::mla;
+  constexpr int unit = kFp8 ? 1 : 2, row_units = kFp8 ? hpc::kMlaFp8RowBytes : hpc::kMlaDim, align_units = 16 / unit;
   if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr) return HPC_ERR_INVALID;
   if (splits < 0 || max_blocks < 0 || ckv_block_stride < 0) return HPC_ERR_INVALID;
   // the split count is the caller's, or with 0 the route's for this device; shapes are refused before the device is asked
   const hpc::MlaRoute shape = hpc::mla_route(num_batch, num_seq_q, num_head, splits > 0 ? splits : 1, 256);
   if (shape.code != HPC_OK) return shape.code;
   if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
-  if (ckv_token_stride < hpc::kMlaDim || (ckv_token_stride & 7) || (ckv_block_stride & 7)) return HPC_ERR_UNSUPPORTED;
+  if (ckv_token_stride < row_units || ckv_token_stride % align_units || ckv_block_stride % align_units) return HPC_ERR_UNSUPPORTED;
   if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(q_ptr) | reinterpret_cast<uintptr_t>(ckv_ptr)) & 15) return HPC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3)) return HPC_ERR_UNSUPPORTED;
@@ -387,8 +432,8 @@ extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr
   a.lse = lse_ptr;
   a.ws_o = static_cast<float*>(workspace_ptr);
   a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
-  a.block_stride_bytes = ckv_block_stride * 2;
-  a.token_stride_bytes = ckv_token_stride * 2;
+  a.block_stride_bytes = ckv_block_stride * unit;
+  a.token_stride_bytes = ckv_token_stride * unit;
   a.total_rows = static_cast<int64_t>(num_batch) * r.rows;
   a.num_head = num_head;
   a.num_seq_q = num_seq_q;
@@ -400,13 +445,37 @@ extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr
   a.new_kv_included = new_kv_included ? 1 : 0;
   a.scale_log2 = softmax_scale * kLog2e;
   if (r.narrow)
-    attention_decode_mla_kernel<true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<true, kFp8><<<dim3(r.grid), kThreads, 0, stream>>>(a);
   else
-    attention_decode_mla_kernel<false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<false, kFp8><<<dim3(r.grid), kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   if (r.splits > 1) {
     attention_decode_mla_merge_kernel<<<dim3(r.merge_grid), 128, 0, stream>>>(a);
     HPC_CHECK_LAUNCH();
   }
   return HPC_OK;
+}
+}  // namespace
+
+extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                   const int* block_ids_ptr, const int* num_seq_kvcache_ptr, int num_batch,
+                                                   int num_seq_q, int num_head, int block_size, int max_blocks,
+                                                   int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                                   int new_kv_included, int splits, void* workspace_ptr,
+                                                   int64_t workspace_bytes, hipStream_t stream) {
+  return mla_decode_launch<false>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, num_batch, num_seq_q,
+                                  num_head, block_size, max_blocks, ckv_block_stride, ckv_token_stride, softmax_scale,
+                                  new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+}
+
+// the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
+extern "C" int hpc_attention_decode_mla_fp8_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                  const int* block_ids_ptr, const int* num_seq_kvcache_ptr, int num_batch,
+                                                  int num_seq_q, int num_head, int block_size, int max_blocks,
+                                                  int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
+                                                  float softmax_scale, int new_kv_included, int splits, void* workspace_ptr,
+                                                  int64_t workspace_bytes, hipStream_t stream) {
+  return mla_decode_launch<true>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, num_batch, num_seq_q,
+                                 num_head, block_size, max_blocks, ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale,
+                                 new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
 }

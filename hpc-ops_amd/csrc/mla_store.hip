@@ -14,7 +14,15 @@
 //                                  with cos[4j..4j+3] / sin[32+4j..32+4j+3] and no value crosses lanes.
 // The data loads are issued before the dependent chain q_index search -> seqlen -> page-table entry (the last in the latent
 // unit only), which bounds a decode-sized launch.  Device values are never trusted with an address: see the guards at `live` and `store`.
+//
+// FP8 latent cache (kFp8, hpc_mla_rope_norm_store_kv_fp8_async): the cache cell is the 656-byte row of mla_fp8_format.h.  Only
+// the latent unit's cache store differs.  Lane l owns columns 8 l .. 8 l + 7, so scale group g is lanes 16 g .. 16 g + 15: the
+// group amax of the lane's eight bf16-ROUNDED values (what the bf16 writer stores - the FP8 cache is an exact function of it) is
+// a four-step xor-shuffle, the codes are the project's 128-column quantiser (act_quant.h) and leave as one 8-byte store per
+// lane, the scale as one 4-byte store per group, k_pe unquantised from lanes 0..7.  out_ckv and out_q_pe are the bf16 form's.
+#include "act_quant.h"
 #include "hpc_common.h"
+#include "mla_fp8_format.h"
 #include "../../include/hpc_amd.h"
 
 namespace hpc {
@@ -28,7 +36,7 @@ struct Args {
   const int* seqlen;         // [num_req] total length incl. the new tokens
   const int* q_index;        // [num_req + 1]
   const int* block_ids;      // [num_req, max_blocks]
-  uint16_t* cache;           // token (page, t) at cache + page * cache_bs + t * cache_ts, or null
+  uint16_t* cache;           // token (page, t) at cache + page * cache_bs + t * cache_ts, or null (kFp8: uint8_t, strides in bytes)
   uint16_t* out_ckv;         // [rows, 576], row stride out_ckv_rs, or null
   uint16_t* out_q_pe;        // [rows, H, 64] or null
   long kv_a_rs, q_rs, q_hs, oq_rs, oq_hs, out_ckv_rs, cache_bs, cache_ts;  // elements
@@ -100,7 +108,8 @@ struct Piece {
   }
 };
 
-template <bool kInterleaved, int kU>  // kU groups of 8 heads per q-unit wave (same row): one position lookup for all of them
+// kU groups of 8 heads per q-unit wave (same row): one position lookup for all of them; kFp8: the FP8 cache row
+template <bool kInterleaved, int kU, bool kFp8>
 __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int hsub = lane >> 3, j = lane & 7;
@@ -185,7 +194,28 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
     const float wa = i < 2 ? w0[2 * i] : w1[2 * i - 4], wb = i < 2 ? w0[2 * i + 1] : w1[2 * i - 3];
     o[i] = pack_bf16x2(x[2 * i] * r * wa, x[2 * i + 1] * r * wb);
   }
-  if (store) {
+  if constexpr (kFp8) {
+    // the bf16-rounded values, quantised per 128 columns = 16 lanes (the shuffles run on every lane: `store` is per wave anyway)
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[2 * i] = bf16lo_to_f32(o[i]);
+      v[2 * i + 1] = bf16hi_to_f32(o[i]);
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
+    const float scale = e4m3_block_scale(amax), inv = e4m3_block_inv(scale);
+    if (store) {
+      uint8_t* row = reinterpret_cast<uint8_t*>(a.cache) + cell;
+      *reinterpret_cast<u32x2*>(row + kMlaFp8CodesAt + 8 * lane) =
+          u32x2{quant_4xe4m3(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv), quant_4xe4m3(v[4] * inv, v[5] * inv, v[6] * inv, v[7] * inv)};
+      if ((lane & 15) == 0) *reinterpret_cast<float*>(row + kMlaFp8ScalesAt + 4 * (lane >> 4)) = scale;
+      if (lane < 8) pe[0].store(reinterpret_cast<uint16_t*>(row + kMlaFp8RopeAt), j);
+    }
+  } else if (store) {
     st16(a.cache + cell + 8 * lane, o);
     if (lane < 8) pe[0].store(a.cache + cell + kLatent, j);
   }
@@ -203,15 +233,18 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
 }  // namespace mla_store
 }  // namespace hpc
 
-extern "C" int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe,
-                                                const float* cos_sin, const float* kv_norm_weight, const int* num_seqlen_per_req,
-                                                const int* q_index, const int* block_ids, int num_rows, int num_req, int num_head,
-                                                int block_size, int max_blocks, int num_blocks, int max_pos,
-                                                int64_t ckv_block_stride, int64_t ckv_token_stride, int64_t kv_a_row_stride,
-                                                int64_t out_ckv_row_stride, int64_t q_pe_row_stride, int64_t q_pe_head_stride,
-                                                int64_t out_q_pe_row_stride, int64_t out_q_pe_head_stride, float eps,
-                                                int interleaved, hipStream_t stream) {
+namespace {
+// Both launchers: the checks and the launch.  kFp8: the cache is the FP8 row and its two strides are in bytes (multiples of 16,
+// a token >= 656); otherwise they are in bf16 elements (multiples of 8, a token >= 576) - 16 bytes either way.
+template <bool kFp8>
+int mla_store_launch(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe, const float* cos_sin,
+                     const float* kv_norm_weight, const int* num_seqlen_per_req, const int* q_index, const int* block_ids,
+                     int num_rows, int num_req, int num_head, int block_size, int max_blocks, int num_blocks, int max_pos,
+                     int64_t ckv_block_stride, int64_t ckv_token_stride, int64_t kv_a_row_stride, int64_t out_ckv_row_stride,
+                     int64_t q_pe_row_stride, int64_t q_pe_head_stride, int64_t out_q_pe_row_stride,
+                     int64_t out_q_pe_head_stride, float eps, int interleaved, hipStream_t stream) {
   using namespace hpc::mla_store;
+  constexpr int64_t cache_row = kFp8 ? hpc::kMlaFp8RowBytes : kLatent + kRope, cache_align = kFp8 ? hpc::kMlaFp8Align : 8;
   // every check on the host, before any device call
   if (num_rows < 0 || num_req < 0 || num_head < 0 || max_blocks < 0 || num_blocks < 0 || max_pos < 0) return HPC_ERR_INVALID;
   if (!kv_a || !cos_sin || !kv_norm_weight || !num_seqlen_per_req || !q_index) return HPC_ERR_INVALID;
@@ -228,8 +261,9 @@ extern "C" int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, 
   if (ckv_cache) {
     if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
     while ((1 << page_shift) < block_size) ++page_shift;
-    if (misaligned(ckv_cache) || bad_stride(ckv_block_stride) || bad_stride(ckv_token_stride) ||
-        ckv_token_stride < kLatent + kRope)
+    const auto bad_cache_stride = [](int64_t s) { return s < 0 || s % cache_align != 0; };
+    if (misaligned(ckv_cache) || bad_cache_stride(ckv_block_stride) || bad_cache_stride(ckv_token_stride) ||
+        ckv_token_stride < cache_row)
       return HPC_ERR_UNSUPPORTED;
   }
   if (out_ckv && (misaligned(out_ckv) || bad_stride(out_ckv_row_stride))) return HPC_ERR_UNSUPPORTED;
@@ -284,8 +318,40 @@ extern "C" int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, 
   a.max_pos = max_pos;
   a.eps = eps;
   const int grid = static_cast<int>((units + 3) / 4);
-  if (interleaved) mla_store_kernel<true, kGroupsPerWave><<<grid, kThreads, 0, stream>>>(a);
-  else mla_store_kernel<false, kGroupsPerWave><<<grid, kThreads, 0, stream>>>(a);
+  if (interleaved) mla_store_kernel<true, kGroupsPerWave, kFp8><<<grid, kThreads, 0, stream>>>(a);
+  else mla_store_kernel<false, kGroupsPerWave, kFp8><<<grid, kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
+}
+}  // namespace
+
+extern "C" int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe,
+                                                const float* cos_sin, const float* kv_norm_weight, const int* num_seqlen_per_req,
+                                                const int* q_index, const int* block_ids, int num_rows, int num_req, int num_head,
+                                                int block_size, int max_blocks, int num_blocks, int max_pos,
+                                                int64_t ckv_block_stride, int64_t ckv_token_stride, int64_t kv_a_row_stride,
+                                                int64_t out_ckv_row_stride, int64_t q_pe_row_stride, int64_t q_pe_head_stride,
+                                                int64_t out_q_pe_row_stride, int64_t out_q_pe_head_stride, float eps,
+                                                int interleaved, hipStream_t stream) {
+  return mla_store_launch<false>(ckv_cache, out_ckv, out_q_pe, kv_a, q_pe, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
+                                 block_ids, num_rows, num_req, num_head, block_size, max_blocks, num_blocks, max_pos,
+                                 ckv_block_stride, ckv_token_stride, kv_a_row_stride, out_ckv_row_stride, q_pe_row_stride,
+                                 q_pe_head_stride, out_q_pe_row_stride, out_q_pe_head_stride, eps, interleaved, stream);
+}
+
+// the same into the FP8 latent cache (mla_fp8_format.h); the cache's two strides in bytes, every other stride in bf16 elements
+extern "C" int hpc_mla_rope_norm_store_kv_fp8_async(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a,
+                                                    const void* q_pe, const float* cos_sin, const float* kv_norm_weight,
+                                                    const int* num_seqlen_per_req, const int* q_index, const int* block_ids,
+                                                    int num_rows, int num_req, int num_head, int block_size, int max_blocks,
+                                                    int num_blocks, int max_pos, int64_t ckv_block_stride_bytes,
+                                                    int64_t ckv_token_stride_bytes, int64_t kv_a_row_stride,
+                                                    int64_t out_ckv_row_stride, int64_t q_pe_row_stride, int64_t q_pe_head_stride,
+                                                    int64_t out_q_pe_row_stride, int64_t out_q_pe_head_stride, float eps,
+                                                    int interleaved, hipStream_t stream) {
+  return mla_store_launch<true>(ckv_cache, out_ckv, out_q_pe, kv_a, q_pe, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
+                                block_ids, num_rows, num_req, num_head, block_size, max_blocks, num_blocks, max_pos,
+                                ckv_block_stride_bytes, ckv_token_stride_bytes, kv_a_row_stride, out_ckv_row_stride,
+                                q_pe_row_stride, q_pe_head_stride, out_q_pe_row_stride, out_q_pe_head_stride, eps, interleaved,
+                                stream);
 }

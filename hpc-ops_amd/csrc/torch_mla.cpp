@@ -3,19 +3,44 @@
 // namespace: torch.ops.hpc_mla.* (hpc:: holds the reference's surface).  With `output` (and `output_lse` where an lse is wanted)
 // given nothing is allocated per call beyond the cached scratch and the call captures into a hipGraph.  Nothing here reads the
 // values of num_seq_kvcache.  Below it rope_norm_store_kv, the op that writes that cache and the RoPE columns of q
-// (csrc/mla_store.hip).  No kernels here.
+// (csrc/mla_store.hip).  Each has its twin over the FP8 latent cache (csrc/mla_fp8_format.h: a uint8 tensor of 656-byte rows,
+// strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's dtype, row width and
+// stride rule being the only difference.  No kernels here.
+#include "mla_fp8_format.h"
 #include "torch_common.h"
 
 using namespace hpc_torch;
 
 namespace {
 
-std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q, const at::Tensor& ckv_cache,
-                                                             const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
-                                                             double softmax_scale, int64_t mtp, bool new_kv_included,
-                                                             const c10::optional<at::Tensor>& output,
-                                                             const c10::optional<at::Tensor>& output_lse, bool return_lse,
-                                                             int64_t splits) {
+// what distinguishes the two caches: dtype, row width and the 16-byte stride rule in the dtype's elements
+struct CacheKind {
+  bool fp8;
+  at::ScalarType dtype;
+  const char* dtype_name;
+  int64_t row, align;
+};
+constexpr CacheKind kCacheBf16{false, at::kBFloat16, "bfloat16", 576, 8};
+constexpr CacheKind kCacheFp8{true, at::kByte, "uint8", hpc::kMlaFp8RowBytes, hpc::kMlaFp8Align};
+
+// [num_blocks, block_size, row] of the kind's dtype, last dim contiguous, both strides multiples of `align`, 16-byte aligned
+void check_cache(const at::Tensor& c, const CacheKind& kind) {
+  TORCH_CHECK(c.scalar_type() == kind.dtype, "ckv_cache dtype must be ", kind.dtype_name);
+  TORCH_CHECK(c.dim() == 3 && c.size(2) == kind.row, "ckv_cache must be [num_blocks, block_size, ", kind.row, "]");
+  const int64_t page = c.size(1);
+  TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, "block_size must be 16, 32, 64 or 128, got ", page);
+  TORCH_CHECK(c.stride(2) == 1, "ckv_cache must have a contiguous last dim");
+  TORCH_CHECK(c.stride(1) >= kind.row && c.stride(1) % kind.align == 0 && c.stride(0) % kind.align == 0 && c.stride(0) >= 0,
+              "ckv_cache token stride must be >= ", kind.row, " and, like the block stride, a multiple of ", kind.align,
+              kind.fp8 ? " bytes" : " elements", "; got ", c.stride(1), " and ", c.stride(0));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, "ckv_cache must be 16-byte aligned");
+}
+
+std::tuple<at::Tensor, at::Tensor> decode_mla(const CacheKind& kind, const char* op, const at::Tensor& q,
+                                              const at::Tensor& ckv_cache, const at::Tensor& block_ids,
+                                              const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
+                                              bool new_kv_included, const c10::optional<at::Tensor>& output,
+                                              const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
   cuda_contig(q, "q");
   cuda_contig(block_ids, "block_ids");
   cuda_contig(num_seq_kvcache, "num_seq_kvcache");
@@ -23,26 +48,20 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q
   TORCH_CHECK(ckv_cache.device() == q.device() && block_ids.device() == q.device() && num_seq_kvcache.device() == q.device(),
               "ckv_cache, block_ids and num_seq_kvcache must be on q's device");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
-  TORCH_CHECK(ckv_cache.scalar_type() == at::kBFloat16, "ckv_cache dtype must be bfloat16");
+  TORCH_CHECK(ckv_cache.scalar_type() == kind.dtype, "ckv_cache dtype must be ", kind.dtype_name);
   TORCH_CHECK(block_ids.scalar_type() == at::kInt, "block_ids dtype must be int32");
   TORCH_CHECK(num_seq_kvcache.scalar_type() == at::kInt, "num_seq_kvcache dtype must be int32");
   TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
   const int64_t sq = mtp + 1;
   TORCH_CHECK(q.dim() == 3 && q.size(2) == 576, "q must be [num_batch * num_seq_q, num_head, 576]");
-  TORCH_CHECK(ckv_cache.dim() == 3 && ckv_cache.size(2) == 576, "ckv_cache must be [num_blocks, block_size, 576]");
+  TORCH_CHECK(ckv_cache.dim() == 3 && ckv_cache.size(2) == kind.row, "ckv_cache must be [num_blocks, block_size, ", kind.row, "]");
   TORCH_CHECK(block_ids.dim() == 2, "block_ids must be [num_batch, max_blocks]");
   TORCH_CHECK(num_seq_kvcache.dim() == 1, "num_seq_kvcache must be [num_batch]");
   const int64_t b = num_seq_kvcache.size(0), h = q.size(1), page = ckv_cache.size(1);
   TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
   TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
   TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
-  TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, "block_size must be 16, 32, 64 or 128, got ", page);
-  TORCH_CHECK(ckv_cache.stride(2) == 1, "ckv_cache must have a contiguous last dim");
-  TORCH_CHECK(ckv_cache.stride(1) >= 576 && ckv_cache.stride(1) % 8 == 0 && ckv_cache.stride(0) % 8 == 0 &&
-                  ckv_cache.stride(0) >= 0,
-              "ckv_cache token stride must be >= 576 and, like the block stride, a multiple of 8 elements; got ",
-              ckv_cache.stride(1), " and ", ckv_cache.stride(0));
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(ckv_cache.data_ptr()) % 16 == 0, "ckv_cache must be 16-byte aligned");
+  check_cache(ckv_cache, kind);
   TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
   TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
   at::Tensor out = out_or_new(output, q, {b * sq, h, 512}, at::kBFloat16, "output", kOnInputDevice);
@@ -55,18 +74,38 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q
   const int rc_plan = hpc_attention_decode_mla_plan(i32(b), i32(sq), i32(h), i32(std::min<int64_t>(splits, INT32_MAX)),
                                                     b > 0 ? hpc_get_cu_count(q.device().index()) : 256, &s, &max_splits, &ws_bytes);
   TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a request may be cut into");
-  HPC_LAUNCH_CHECK(rc_plan, "attention_decode_mla_bf16");
+  HPC_LAUNCH_CHECK(rc_plan, op);
   if (b == 0) return {out, lse};
   TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
   at::Tensor ws;
   if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: an unwritten piece is never read
-  const int rc = hpc_attention_decode_mla_bf16_async(
+  const int rc = (kind.fp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
       ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache),
       static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(num_seq_kvcache.data_ptr()), i32(b), i32(sq), i32(h),
       i32(page), i32(block_ids.size(1)), ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale),
       new_kv_included ? 1 : 0, s, s > 1 ? ws.data_ptr() : nullptr, ws_bytes, stream_of(q));
-  HPC_LAUNCH_CHECK(rc, "attention_decode_mla_bf16");
+  HPC_LAUNCH_CHECK(rc, op);
   return {out, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q, const at::Tensor& ckv_cache,
+                                                             const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
+                                                             double softmax_scale, int64_t mtp, bool new_kv_included,
+                                                             const c10::optional<at::Tensor>& output,
+                                                             const c10::optional<at::Tensor>& output_lse, bool return_lse,
+                                                             int64_t splits) {
+  return decode_mla(kCacheBf16, "attention_decode_mla_bf16", q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp,
+                    new_kv_included, output, output_lse, return_lse, splits);
+}
+
+std::tuple<at::Tensor, at::Tensor> attention_decode_mla_fp8(const at::Tensor& q, const at::Tensor& ckv_cache,
+                                                            const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
+                                                            double softmax_scale, int64_t mtp, bool new_kv_included,
+                                                            const c10::optional<at::Tensor>& output,
+                                                            const c10::optional<at::Tensor>& output_lse, bool return_lse,
+                                                            int64_t splits) {
+  return decode_mla(kCacheFp8, "attention_decode_mla_fp8", q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp,
+                    new_kv_included, output, output_lse, return_lse, splits);
 }
 
 // ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------
@@ -93,11 +132,11 @@ void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, 
 // Returns out_q_pe (the caller's, or a fresh contiguous one); an empty tensor when q_pe is not given.  With out_q_pe (or no
 // q_pe) nothing is allocated and the call captures into a hipGraph.  Nothing here reads the values of num_seqlen_per_req,
 // q_index or block_ids.
-at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
-                              const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index,
-                              const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
-                              const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
-                              bool interleaved) {
+at::Tensor store_kv(const CacheKind& kind, const char* op, const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a,
+                    const at::Tensor& cos_sin, const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req,
+                    const at::Tensor& q_index, const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
+                    const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
+                    bool interleaved) {
   TORCH_CHECK(kv_a.is_cuda(), "kv_a tensor must be cuda");
   TORCH_CHECK(kv_a.dim() == 2 && kv_a.size(1) == 576, "kv_a must be [rows, 576]");
   const int64_t rows = kv_a.size(0);
@@ -117,19 +156,12 @@ at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const 
   TORCH_CHECK(cos_sin.size(0) <= INT32_MAX && rows <= INT32_MAX && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX,
               "sizes beyond int32");
 
-  int64_t page = 16, block_stride = 0, token_stride = 576, num_blocks = 0;
+  int64_t page = 16, block_stride = 0, token_stride = kind.row, num_blocks = 0;
   if (ckv_cache.has_value()) {
     const at::Tensor& c = *ckv_cache;
     TORCH_CHECK(c.is_cuda() && c.device() == kv_a.device(), "ckv_cache must be on kv_a's device");
-    TORCH_CHECK(c.scalar_type() == at::kBFloat16, "ckv_cache dtype must be bfloat16");
-    TORCH_CHECK(c.dim() == 3 && c.size(2) == 576, "ckv_cache must be [num_blocks, block_size, 576]");
+    check_cache(c, kind);
     page = c.size(1), block_stride = c.stride(0), token_stride = c.stride(1), num_blocks = c.size(0);
-    TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, "block_size must be 16, 32, 64 or 128, got ", page);
-    TORCH_CHECK(c.stride(2) == 1, "ckv_cache must have a contiguous last dim");
-    TORCH_CHECK(token_stride >= 576 && token_stride % 8 == 0 && block_stride % 8 == 0 && block_stride >= 0,
-                "ckv_cache token stride must be >= 576 and, like the block stride, a multiple of 8 elements; got ", token_stride,
-                " and ", block_stride);
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, "ckv_cache must be 16-byte aligned");
     TORCH_CHECK(num_blocks <= INT32_MAX, "sizes beyond int32");
   }
   if (out_ckv.has_value()) check_rows_bf16(*out_ckv, "out_ckv", kv_a, {rows, 576});
@@ -158,7 +190,7 @@ at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const 
   }
   if (rows == 0 || num_req == 0) return oq;  // nothing to launch
   const bool with_q = q_pe.has_value();
-  const int rc = hpc_mla_rope_norm_store_kv_async(
+  const int rc = (kind.fp8 ? hpc_mla_rope_norm_store_kv_fp8_async : hpc_mla_rope_norm_store_kv_async)(
       ptr(ckv_cache), ptr(out_ckv), with_q ? oq.data_ptr() : nullptr, ptr(kv_a), ptr(q_pe),
       static_cast<const float*>(cos_sin.data_ptr()), static_cast<const float*>(kv_norm_weight.data_ptr()),
       static_cast<const int*>(num_seqlen_per_req.data_ptr()), static_cast<const int*>(q_index.data_ptr()),
@@ -166,8 +198,26 @@ at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const 
       i32(num_blocks), i32(cos_sin.size(0)), block_stride, token_stride, kv_a.stride(0),
       out_ckv.has_value() ? out_ckv->stride(0) : 576, with_q ? q_pe->stride(0) : 0, with_q ? q_pe->stride(1) : 0,
       with_q ? oq.stride(0) : 0, with_q ? oq.stride(1) : 0, static_cast<float>(eps), interleaved ? 1 : 0, stream_of(kv_a));
-  HPC_LAUNCH_CHECK(rc, "mla_rope_norm_store_kv");
+  HPC_LAUNCH_CHECK(rc, op);
   return oq;
+}
+
+at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
+                              const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index,
+                              const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
+                              const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
+                              bool interleaved) {
+  return store_kv(kCacheBf16, "mla_rope_norm_store_kv", ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
+                  block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
+}
+
+at::Tensor rope_norm_store_kv_fp8(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
+                                  const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req,
+                                  const at::Tensor& q_index, const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
+                                  const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv,
+                                  double eps, bool interleaved) {
+  return store_kv(kCacheFp8, "mla_rope_norm_store_kv_fp8", ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
+                  block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
 }
 
 }  // namespace
@@ -179,6 +229,12 @@ TORCH_LIBRARY(hpc_mla, m) {
   m.def(
       "attention_decode_mla_bf16(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seq_kvcache, float softmax_scale, "
       "int mtp, bool new_kv_included, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
+  m.def(
+      "rope_norm_store_kv_fp8(Tensor? ckv_cache, Tensor kv_a, Tensor cos_sin, Tensor kv_norm_weight, Tensor num_seqlen_per_req, "
+      "Tensor q_index, Tensor block_ids, Tensor? q_pe, Tensor? out_q_pe, Tensor? out_ckv, float eps, bool interleaved) -> Tensor");
+  m.def(
+      "attention_decode_mla_fp8(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seq_kvcache, float softmax_scale, "
+      "int mtp, bool new_kv_included, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
   // the cached split-KV scratch buffers (tests fill them with NaN bytes: no piece that was not written may be read)
   m.def("_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMla); });
 }
@@ -186,4 +242,6 @@ TORCH_LIBRARY(hpc_mla, m) {
 TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("attention_decode_mla_bf16", &attention_decode_mla_bf16);
   m.impl("rope_norm_store_kv", &rope_norm_store_kv);
+  m.impl("attention_decode_mla_fp8", &attention_decode_mla_fp8);
+  m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv_fp8);
 }

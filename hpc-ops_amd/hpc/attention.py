@@ -388,3 +388,46 @@ def _attention_decode_mla_bf16_fake(q, ckv_cache, block_ids, num_seq_kvcache, so
     else:
         lse = torch.empty((0,), dtype=torch.float32, device=q.device)
     return out, lse
+
+
+def attention_decode_mla_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,
+                             softmax_scale: float, mtp: int = 0, new_kv_included: bool = False, *, output: Tensor = None,
+                             output_lse: Tensor = None, return_lse: bool = False, splits: int = 0):
+    """attention_decode_mla_bf16 over an FP8 latent KV cache: 656 bytes per token where the bf16 cache has 1,152, so the
+    same memory holds 1.76 x the tokens.  Returns out bf16 [B * Sq, H, 512], or (out, lse) with return_lse or output_lse.
+    Only the cache is FP8: q, out and lse are those of attention_decode_mla_bf16, and so is every other argument, limit
+    (H % 16 == 0, 16 <= H <= 128; mtp 0..3; P in {16, 32, 64, 128}), the splits rule (0 .. 64), the cached scratch that
+    hpc.release_decode_workspaces() drops (shared with the bf16 op), hipGraph capture with caller-provided outputs and
+    the determinism statement; num_seq_kvcache is never read on the host.
+
+    ckv_cache is a torch.uint8 tensor, logical [num_blocks, P, 656].  The row of one token:
+
+        bytes   0 .. 511   512 float8_e4m3fn codes: the normalised compressed KV, column d at byte d (offset 0)
+        bytes 512 .. 527   four little-endian float32 scales (offset 512); scale g belongs to columns 128 g .. 128 g + 127
+        bytes 528 .. 655   64 bfloat16 (offset 528): the RoPE'd k_pe, unquantised
+
+    Last dim contiguous, token stride >= 656 bytes and a multiple of 16, block stride a multiple of 16, base 16-byte
+    aligned: padded rows and views into a larger pool work.  Allocate it as torch.empty(num_blocks, P, 656,
+    dtype=torch.uint8) and fill it with hpc.mla_rope_norm_store_kv_fp8.
+
+    Semantics = attention_decode_mla_bf16 (tests/mla_ref.py::mla_statement in float64) applied to the dequantised cache,
+    whose latent column d < 512 of a token is
+
+        c[d] = bf16_rne( fp32(code[d]) * scale[d // 128] )
+
+    with one float32 multiply and one round-to-nearest-even to bfloat16; columns 512..575 are the bf16 k_pe.  The scales
+    may be any finite non-negative float32 (hpc.mla_rope_norm_store_kv_fp8 writes amax / 448 per group and codes
+    e4m3fn(lat * (1 / (scale + 1e-8)))); a scale of 0 makes its group zeros.  NaN codes (0x7f / 0xff) and non-finite
+    scales in tokens a row can see: unspecified.  The kernel is attention_decode_mla_bf16's behind the gather, which
+    dequantises into the same on-chip image: for given shapes, splits and CU count the result is bit-identical to
+    attention_decode_mla_bf16 on the dequantised cache, and bit-identical from call to call."""
+    out, lse = torch.ops.hpc_mla.attention_decode_mla_fp8(q, ckv_cache, block_ids, num_seq_kvcache, float(softmax_scale),
+                                                          int(mtp), bool(new_kv_included), output, output_lse,
+                                                          bool(return_lse), int(splits))
+    out = out if output is None else output
+    if not (return_lse or output_lse is not None):
+        return out
+    return out, (lse if output_lse is None else output_lse)
+
+
+torch.library.register_fake("hpc_mla::attention_decode_mla_fp8")(_attention_decode_mla_bf16_fake)

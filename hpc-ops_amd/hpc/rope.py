@@ -168,3 +168,35 @@ def _mla_rope_norm_store_kv_fake(ckv_cache, kv_a, cos_sin, kv_norm_weight, num_s
     if out_q_pe is not None:
         return out_q_pe
     return torch.empty(q_pe.shape, dtype=kv_a.dtype, device=kv_a.device)
+
+
+def mla_rope_norm_store_kv_fp8(ckv_cache: Optional[Tensor], kv_a: Tensor, cos_sin: Tensor, kv_norm_weight: Tensor,
+                               num_seqlen_per_req: Tensor, q_index: Tensor, block_ids: Tensor, *,
+                               q_pe: Optional[Tensor] = None, out_q_pe: Optional[Tensor] = None,
+                               out_ckv: Optional[Tensor] = None, eps: float = 1e-6,
+                               interleaved: bool = True) -> Optional[Tensor]:
+    """mla_rope_norm_store_kv into the FP8 latent KV cache that attention_decode_mla_fp8 reads.  Arguments, the
+    row-to-position rule, the guards (a page id outside [0, num_blocks) is not stored, neither is a token with
+    pos // P >= max_blocks, the table index is clamped) and the return value are those of mla_rope_norm_store_kv; out_ckv
+    and out_q_pe stay bfloat16 and are bit-identical to what mla_rope_norm_store_kv writes.
+
+    ckv_cache is a torch.uint8 tensor, logical [num_blocks, P, 656], P in {16, 32, 64, 128}, or None when out_ckv is
+    given: last dim contiguous, token stride >= 656 bytes and a multiple of 16, block stride a multiple of 16, base
+    16-byte aligned.  With lat the bfloat16-ROUNDED row mla_rope_norm_store_kv stores, the written row is
+
+        bytes   0 .. 511 (offset 0)    code[d] = e4m3fn_sat( lat[d] * (1 / (scale[d // 128] + 1e-8)) ),  d < 512
+        bytes 512 .. 527 (offset 512)  scale[g] = amax / 448 of lat[128 g .. 128 g + 127], float32, g < 4
+        bytes 528 .. 655 (offset 528)  lat[512:], the RoPE'd k_pe in bfloat16
+
+    every step in float32 - tests/blockwise_quant_ref.py::quant on the 512 columns, the quantiser of
+    fused_rmsnorm_blockwise_quant.  Quantising the rounded row makes the FP8 cache an exact function of the bf16 cache.
+    A reader recovers c[d] = bf16_rne( fp32(code[d]) * scale[d // 128] ).  Only those 656 bytes of a new token's cell are
+    written: token-stride padding, page tails and unlisted pages stay byte-identical."""
+    out = torch.ops.hpc_mla.rope_norm_store_kv_fp8(ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
+                                                   block_ids, q_pe, out_q_pe, out_ckv, float(eps), bool(interleaved))
+    if q_pe is None:
+        return None
+    return out if out_q_pe is None else out_q_pe
+
+
+torch.library.register_fake("hpc_mla::rope_norm_store_kv_fp8")(_mla_rope_norm_store_kv_fake)

@@ -486,6 +486,26 @@ int hpc_attention_decode_mla_bf16_async(void* out, float* lse, const void* q, co
                                         int new_kv_included, int splits, void* workspace, int64_t workspace_bytes,
                                         hpc_stream_t stream);
 
+/* ---- The FP8 latent KV cache of the MLA ops (the constants: csrc/mla_fp8_format.h) -----------------------------------------
+ * One token is a row of 656 bytes: bytes 0 .. 511 hold 512 float8_e4m3fn codes (the normalised compressed KV, column d at byte
+ * d), bytes 512 .. 527 four little-endian fp32 scales (scale g belongs to columns 128 g .. 128 g + 127), bytes 528 .. 655 the
+ * 64 RoPE'd k_pe columns in bf16, unquantised.  Latent column d < 512 of a token is
+ *   c[d] = bf16_rne( fp32(code[d]) * scale[d / 128] )          (one fp32 multiply, one round-to-nearest-even to bf16)
+ * for ANY finite non-negative scales; a scale of 0 makes its group zeros; NaN codes and non-finite scales in tokens a row can
+ * see are unspecified.  Token (page, t) lies at ckv + page * ckv_block_stride_bytes + t * ckv_token_stride_bytes: token stride
+ * >= 656, both strides multiples of 16 bytes, base 16-byte aligned.
+ *
+ * hpc_attention_decode_mla_fp8_async is hpc_attention_decode_mla_bf16_async on the dequantised cache - every other argument,
+ * limit, refusal, the split rule, hpc_attention_decode_mla_plan and the workspace are the bf16 call's; q, out and lse keep
+ * their types.  Built from the same kernel source behind the gather, it agrees with the bf16 call on the dequantised cache bit
+ * for bit.  HPC_ERR_UNSUPPORTED for a token stride < 656 or not a multiple of 16, a block stride not a multiple of 16, a
+ * misaligned base. */
+int hpc_attention_decode_mla_fp8_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                       const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size,
+                                       int max_blocks, int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
+                                       float softmax_scale, int new_kv_included, int splits, void* workspace,
+                                       int64_t workspace_bytes, hpc_stream_t stream);
+
 /* ---- MLA latent-cache write: kv_a RMSNorm + RoPE + paged store, bf16 (csrc/mla_store.hip) ------------------------------------
  * No reference kernel exists; the semantics are the PyTorch statement tests/mla_store_ref.py.  The producer of the cache and of
  * the RoPE columns of q that hpc_attention_decode_mla_bf16_async reads.  Row r of kv_a is one new token; its request b is the
@@ -519,6 +539,20 @@ int hpc_mla_rope_norm_store_kv_async(void* ckv_cache, void* out_ckv, void* out_q
                                      int64_t ckv_token_stride, int64_t kv_a_row_stride, int64_t out_ckv_row_stride,
                                      int64_t q_pe_row_stride, int64_t q_pe_head_stride, int64_t out_q_pe_row_stride,
                                      int64_t out_q_pe_head_stride, float eps, int interleaved, hpc_stream_t stream);
+/* The same into the FP8 latent cache described above: arguments, the row-to-position rule, the guards and the refusals are those
+ * of hpc_mla_rope_norm_store_kv_async, except that ckv_cache holds 656-byte rows and its two strides are in BYTES (multiples of
+ * 16, token stride >= 656).  With lat the bf16-rounded row the bf16 call stores, per group g of 128 columns and in fp32:
+ *   scale[g] = max |lat[128 g .. 128 g + 127]| / 448        code[d] = e4m3fn_sat( lat[d] * (1 / (scale[d / 128] + 1e-8)) )
+ * and bytes 528 .. 655 = lat[512:] in bf16.  Only those 656 bytes of a new token's cell are written.  out_ckv and out_q_pe stay
+ * bf16 and are bit-identical to the bf16 call's. */
+int hpc_mla_rope_norm_store_kv_fp8_async(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe,
+                                         const float* cos_sin, const float* kv_norm_weight, const int* num_seqlen_per_req,
+                                         const int* q_index, const int* block_ids, int num_rows, int num_req, int num_head,
+                                         int block_size, int max_blocks, int num_blocks, int max_pos,
+                                         int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes, int64_t kv_a_row_stride,
+                                         int64_t out_ckv_row_stride, int64_t q_pe_row_stride, int64_t q_pe_head_stride,
+                                         int64_t out_q_pe_row_stride, int64_t out_q_pe_head_stride, float eps, int interleaved,
+                                         hpc_stream_t stream);
 
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).

@@ -6,7 +6,12 @@
           rows x 80 x 256 x 2 there.
 Times are device-event times of a replayed hipGraph holding one call, median of 20 replays after warm-up (bench.timed).  The op
 and the eager statement must agree before their times are taken.
-usage: python tools/tune_mla_store.py [--out FILE] [--no-eager]"""
+
+--cache fp8: hpc.mla_rope_norm_store_kv_fp8 (656-byte rows, csrc/mla_fp8_format.h) beside hpc.mla_rope_norm_store_kv in the same
+run on the same shapes and inputs.  Before the times are taken the FP8 cells must be the project's 128-column quantisation
+(hpc.blockwise_fp8_quant) of the bf16 cells, bit for bit, and out_q_pe equal.  Algorithmic bytes: the bf16 op's with the cache
+write of 1,152 B per row replaced by 656 B.  The two ops are timed alternately, twice, and the lower median of each is kept.
+usage: python tools/tune_mla_store.py [--cache bf16|fp8] [--out FILE] [--no-eager]"""
 import argparse
 import sys
 from pathlib import Path
@@ -29,14 +34,73 @@ def rot(t, cos, sin):  # interleaved pairing, fp32
     return torch.stack([a * cos - b * sin, b * cos + a * sin], -1).flatten(-2)
 
 
+def main_fp8(dev, cs):
+    lines = ["# mla_rope_norm_store_kv_fp8 beside mla_rope_norm_store_kv on %d CUs, pages of %d, interleaved pairing, kv_a = "
+             "y[:, 1536:2112], q_pe = q[..., 128:], out_q_pe = q_abs[..., 512:]; us per call: one call in a replayed hipGraph, "
+             "median of 20" % (_C.cu_count(dev), P),
+             "# shape req new ctx H rows | bf16 us  fp8 us  fp8/bf16 | fp8: MB  frac of 8 TB/s"]
+    for name, B, new, ctx in SHAPES:
+        rows, total = B * new, ctx + new
+        nb = (total + P - 1) // P
+        bid = torch.randperm(B * nb + 8)[: B * nb].to(torch.int32).reshape(B, nb).to(dev)
+        ns = torch.full((B,), total, dtype=torch.int32, device=dev)
+        qi = torch.arange(0, rows + 1, new, dtype=torch.int32, device=dev)
+        y = torch.randn(rows, 2112, device=dev).to(BF16)
+        w = torch.randn(512, device=dev)
+        kv_a = y[:, 1536:]
+        r = torch.arange(rows, device=dev)
+        req = r // new
+        pos = ns[req].long() - (qi[req + 1].long() - r)
+        page, slot = bid[req, pos // P].long(), pos % P
+        for H in HEADS:
+            q = (torch.randn(rows, H, 192, device=dev) / 24).to(BF16)
+            q_pe = q[..., 128:]
+            q_abs, q_abs8 = (torch.zeros(rows, H, 576, dtype=BF16, device=dev) for _ in range(2))
+            ckv = torch.zeros(B * nb + 8, P, 576, dtype=BF16, device=dev)
+            ckv8 = torch.zeros(B * nb + 8, P, 656, dtype=torch.uint8, device=dev)
+
+            def op16():
+                return hpc.mla_rope_norm_store_kv(ckv, kv_a, cs, w, ns, qi, bid, q_pe=q_pe, out_q_pe=q_abs[..., 512:])
+
+            def op8():
+                return hpc.mla_rope_norm_store_kv_fp8(ckv8, kv_a, cs, w, ns, qi, bid, q_pe=q_pe, out_q_pe=q_abs8[..., 512:])
+
+            op16(), op8()
+            torch.cuda.synchronize()
+            cells16, cells8 = ckv[page, slot], ckv8[page, slot]
+            codes, scales = hpc.blockwise_fp8_quant(cells16[:, :512].contiguous())
+            assert torch.equal(cells8[:, :512], codes.view(torch.uint8)), (name, B, H, "codes")
+            assert torch.equal(cells8[:, 512:528], scales.view(torch.uint8)), (name, B, H, "scales")
+            assert torch.equal(cells8[:, 528:], cells16[:, 512:].contiguous().view(torch.uint8)), (name, B, H, "k_pe")
+            assert torch.equal(q_abs8, q_abs) and bool(q_abs.float().abs().max() > 0), (name, B, H, "q_pe")
+            # alternating, the lower of two medians each: at decode sizes both sit on the ~15 us floor of a one-call replay
+            # and whichever is timed first in a process state takes outliers of several us
+            t = [bench.timed(op, iters=20, graph=True) for op in (op16, op8, op16, op8)]
+            us16, us8 = min(t[0], t[2]), min(t[1], t[3])
+            mb = (rows * (1152 + 656 + 2 * H * 128) + rows * 256 + (2 * B + 1 + rows) * 4) / 1e6
+            lines.append(f"{name:7s} {B:3d} {new:4d} {ctx:4d} {H:3d} {rows:5d} | {us16:7.1f} {us8:7.1f} {us8 / us16:5.2f} | "
+                         f"{mb:7.2f} {mb / us8 / 8:5.3f}")
+            print(lines[-1], flush=True)
+            del q, q_abs, q_abs8, ckv, ckv8
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cache", default="bf16", choices=("bf16", "fp8"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-eager", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     cs = orc.generate_cos_sin_cache(MAX_POS, 64).to(dev)
+    if a.cache == "fp8":
+        lines = main_fp8(dev, cs)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(a.out).write_text("\n".join(lines) + "\n")
+        return
     cs128 = orc.generate_cos_sin_cache(MAX_POS, 128).to(dev)
     lines = ["# mla_rope_norm_store_kv on %d CUs, pages of %d, interleaved pairing, kv_a = y[:, 1536:2112], q_pe = q[..., 128:], "
              "out_q_pe = q_abs[..., 512:]; us per call: one call in a replayed hipGraph, median of 20" % (_C.cu_count(dev), P),

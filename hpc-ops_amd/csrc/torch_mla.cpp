@@ -5,7 +5,8 @@
 // values of num_seq_kvcache.  Below it rope_norm_store_kv, the op that writes that cache and the RoPE columns of q
 // (csrc/mla_store.hip).  Each has its twin over the FP8 latent cache (csrc/mla_fp8_format.h: a uint8 tensor of 656-byte rows,
 // strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's dtype, row width and
-// stride rule being the only difference.  No kernels here.
+// stride rule being the only difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
+// the non-absorbed 192 / 128 form with an lse output) and merge_attn_states (csrc/merge_attn_states.hip).  No kernels here.
 #include "mla_fp8_format.h"
 #include "torch_common.h"
 
@@ -220,6 +221,104 @@ at::Tensor rope_norm_store_kv_fp8(const c10::optional<at::Tensor>& ckv_cache, co
                   block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
 }
 
+// ---- attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip), pinned to tests/mla_prefill_ref.py -------------------------
+// bf16 on `like`'s device, last dim `width` and contiguous; the stride rules (multiples of 8, wide enough, 16-byte base) are the
+// route's (csrc/attention_prefill_mla_route.h) and come back as its refusal
+void check_prefill_operand(const at::Tensor& t, const char* name, const at::Tensor& like, int64_t dim, int64_t width) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on q's device");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
+  TORCH_CHECK(t.dim() == dim && t.size(-1) == width, name, " must be ", dim, "-d with a last dim of ", width);
+  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
+}
+
+void check_cu_seqlens(const at::Tensor& t, const char* name, const at::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on q's device");
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " dtype must be int32");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) >= 1 && t.is_contiguous(), name, " must be a contiguous [num_batch + 1] tensor");
+}
+
+// Nothing here reads the values of cu_seqlens_q / cu_seqlens_k; with output (and output_lse where an lse is wanted) given nothing
+// is allocated and the call captures into a hipGraph.
+std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_bf16(const at::Tensor& q, const at::Tensor& k_nope, const at::Tensor& k_pe,
+                                                              const at::Tensor& v, const at::Tensor& cu_seqlens_q,
+                                                              int64_t max_seqlens_q, double softmax_scale,
+                                                              const c10::optional<at::Tensor>& cu_seqlens_k,
+                                                              c10::optional<int64_t> max_seqlens_k, bool causal,
+                                                              const c10::optional<at::Tensor>& output,
+                                                              const c10::optional<at::Tensor>& output_lse, bool return_lse) {
+  TORCH_CHECK(q.is_cuda(), "q tensor must be cuda");
+  check_prefill_operand(q, "q", q, 3, 192);
+  const int64_t tq = q.size(0), h = q.size(1), tk = k_nope.dim() > 0 ? k_nope.size(0) : 0;
+  check_prefill_operand(k_nope, "k_nope", q, 3, 128);
+  check_prefill_operand(v, "v", q, 3, 128);
+  check_prefill_operand(k_pe, "k_pe", q, 2, 64);
+  TORCH_CHECK(k_nope.size(1) == h && v.size(1) == h, "k_nope and v must have q's ", h, " heads");
+  TORCH_CHECK(v.size(0) == tk && k_pe.size(0) == tk, "k_nope, k_pe and v must have the same number of rows");
+  check_cu_seqlens(cu_seqlens_q, "cu_seqlens_q", q);
+  if (cu_seqlens_k.has_value()) {
+    check_cu_seqlens(*cu_seqlens_k, "cu_seqlens_k", q);
+    TORCH_CHECK(cu_seqlens_k->size(0) == cu_seqlens_q.size(0), "cu_seqlens_k must have cu_seqlens_q's length");
+    TORCH_CHECK(max_seqlens_k.has_value(), "cu_seqlens_k needs max_seqlens_k");
+  }
+  TORCH_CHECK(max_seqlens_q >= 0 && max_seqlens_q <= INT32_MAX && tq <= INT32_MAX && tk <= INT32_MAX &&
+                  (!max_seqlens_k.has_value() || (*max_seqlens_k >= 0 && *max_seqlens_k <= INT32_MAX)),
+              "max_seqlens_q / max_seqlens_k must be non-negative int32 counts");
+  const int64_t b = cu_seqlens_q.size(0) - 1;
+  at::Tensor out = out_or_new(output, q, {tq, h, 128}, at::kBFloat16, "output", kOnInputDevice);
+  const bool want_lse = return_lse || output_lse.has_value();
+  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {tq, h}, at::kFloat, "output_lse", kOnInputDevice)
+                            : at::empty({0}, q.options().dtype(at::kFloat));
+  if (b == 0 || tq == 0) return {out, lse};  // nothing to launch
+  // an empty k side (every request without context) has no storage to point at: the kernel reads no row of it, q stands in
+  const bool no_keys = tk == 0;
+  const int rc = hpc_attention_prefill_mla_bf16_async(
+      ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), no_keys ? ptr(q) : ptr(k_nope),
+      no_keys ? ptr(q) : ptr(k_pe), no_keys ? ptr(q) : ptr(v), static_cast<const int*>(cu_seqlens_q.data_ptr()),
+      cu_seqlens_k.has_value() ? static_cast<const int*>(cu_seqlens_k->data_ptr()) : nullptr, i32(b), i32(h), i32(max_seqlens_q),
+      max_seqlens_k.has_value() ? i32(*max_seqlens_k) : -1, q.stride(0), q.stride(1), no_keys ? 128 * h : k_nope.stride(0),
+      no_keys ? 128 : k_nope.stride(1), no_keys ? 64 : k_pe.stride(0), no_keys ? 128 * h : v.stride(0), no_keys ? 128 : v.stride(1),
+      static_cast<float>(softmax_scale), causal ? 1 : 0, stream_of(q));
+  HPC_LAUNCH_CHECK(rc, "attention_prefill_mla_bf16");
+  return {out, lse};
+}
+
+// ---- merge_attn_states (csrc/merge_attn_states.hip) ----------------------------------------------------------------------------
+std::tuple<at::Tensor, at::Tensor> merge_attn_states(const at::Tensor& out_a, const at::Tensor& lse_a, const at::Tensor& out_b,
+                                                     const at::Tensor& lse_b, const c10::optional<at::Tensor>& output,
+                                                     const c10::optional<at::Tensor>& output_lse) {
+  TORCH_CHECK(out_a.is_cuda(), "out_a tensor must be cuda");
+  TORCH_CHECK(out_a.dim() == 3, "out_a must be [T, H, D]");
+  const int64_t t = out_a.size(0), h = out_a.size(1), d = out_a.size(2);
+  const auto check_state = [&](const at::Tensor& x, const char* name) {
+    TORCH_CHECK(x.is_cuda() && x.device() == out_a.device(), name, " must be on out_a's device");
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
+    TORCH_CHECK(x.sizes() == out_a.sizes(), name, " must have out_a's shape ", out_a.sizes());
+    TORCH_CHECK(x.stride(2) == 1, name, " must have a contiguous last dim");
+  };
+  const auto check_lse = [&](const at::Tensor& x, const char* name) {
+    TORCH_CHECK(x.is_cuda() && x.device() == out_a.device(), name, " must be on out_a's device");
+    TORCH_CHECK(x.scalar_type() == at::kFloat, name, " dtype must be float32");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) == t && x.size(1) == h && x.is_contiguous(), name, " must be a contiguous [T, H] tensor");
+  };
+  check_state(out_a, "out_a");
+  check_state(out_b, "out_b");
+  check_lse(lse_a, "lse_a");
+  check_lse(lse_b, "lse_b");
+  TORCH_CHECK(d > 0 && d % 8 == 0 && d <= 512, "D must be a multiple of 8, 8 .. 512, got ", d);
+  TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
+  at::Tensor out = output.has_value() ? *output : at::empty({t, h, d}, out_a.options());
+  at::Tensor lse = output_lse.has_value() ? *output_lse : at::empty({t, h}, lse_a.options());
+  if (output.has_value()) check_state(out, "output");
+  if (output_lse.has_value()) check_lse(lse, "output_lse");
+  if (t == 0 || h == 0) return {out, lse};
+  const int rc = hpc_merge_attn_states_async(ptr(out), static_cast<float*>(lse.data_ptr()), ptr(out_a),
+                                             static_cast<const float*>(lse_a.data_ptr()), ptr(out_b),
+                                             static_cast<const float*>(lse_b.data_ptr()), t, i32(h), i32(d), out.stride(0), out.stride(1),
+                                             out_a.stride(0), out_a.stride(1), out_b.stride(0), out_b.stride(1), stream_of(out_a));
+  HPC_LAUNCH_CHECK(rc, "merge_attn_states");
+  return {out, lse};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hpc_mla, m) {
@@ -235,6 +334,13 @@ TORCH_LIBRARY(hpc_mla, m) {
   m.def(
       "attention_decode_mla_fp8(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seq_kvcache, float softmax_scale, "
       "int mtp, bool new_kv_included, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
+  m.def(
+      "attention_prefill_mla_bf16(Tensor q, Tensor k_nope, Tensor k_pe, Tensor v, Tensor cu_seqlens_q, int max_seqlens_q, "
+      "float softmax_scale, Tensor? cu_seqlens_k, int? max_seqlens_k, bool causal, Tensor? output, Tensor? output_lse, "
+      "bool return_lse) -> (Tensor, Tensor)");
+  m.def(
+      "merge_attn_states(Tensor out_a, Tensor lse_a, Tensor out_b, Tensor lse_b, Tensor? output, Tensor? output_lse) -> "
+      "(Tensor, Tensor)");
   // the cached split-KV scratch buffers (tests fill them with NaN bytes: no piece that was not written may be read)
   m.def("_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMla); });
 }
@@ -244,4 +350,6 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("rope_norm_store_kv", &rope_norm_store_kv);
   m.impl("attention_decode_mla_fp8", &attention_decode_mla_fp8);
   m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv_fp8);
+  m.impl("attention_prefill_mla_bf16", &attention_prefill_mla_bf16);
+  m.impl("merge_attn_states", &merge_attn_states);
 }

@@ -431,3 +431,99 @@ def attention_decode_mla_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, nu
 
 
 torch.library.register_fake("hpc_mla::attention_decode_mla_fp8")(_attention_decode_mla_bf16_fake)
+
+
+def attention_prefill_mla_bf16(q: Tensor, k_nope: Tensor, k_pe: Tensor, v: Tensor, cu_seqlens_q: Tensor, max_seqlens_q: int,
+                               softmax_scale: float, *, cu_seqlens_k: Tensor = None, max_seqlens_k: int = None,
+                               causal: bool = True, output: Tensor = None, output_lse: Tensor = None,
+                               return_lse: bool = False):
+    """Multi-head latent attention (MLA) prefill in its non-absorbed form, bfloat16: q / k heads of 192 columns (128 "nope" +
+    64 RoPE), v heads of 128 (DeepSeek-V3 / R1, Kimi-K2 prompts and prompt chunks).  Returns out bf16 [Tq, H, 128], or
+    (out, lse) with return_lse or output_lse.
+
+    No reference counterpart; semantics = the PyTorch statement tests/mla_prefill_ref.py, in float64.  Request b has
+    Sq = cu_seqlens_q[b + 1] - cu_seqlens_q[b] q rows and Lk = cu_seqlens_k[b + 1] - cu_seqlens_k[b] keys.  With causal, row s
+    sees keys j <= Lk - Sq + s (bottom-right aligned, the convention of attention_with_kvcache_prefill_bf16); without it
+    every j < Lk:
+
+        z_j = softmax_scale * (q[s, h, :128] . k_nope[j, h] + q[s, h, 128:] . k_pe[j])
+        out[s, h, :] = bf16( sum_j softmax(z)_j * v[j, h, :] )
+        lse[s, h]    = log sum_j exp(z_j)                                (float32, natural log)
+
+    A row that sees no key - Lk == 0 (a request without a prefix in the context pass), or Lk - Sq + s < 0 - writes out = 0
+    and lse = -inf.  Such a row is legal: merge_attn_states passes the other side through for it.
+
+    Layouts (no concat or copy between the producers and this call):
+      q              bfloat16 [Tq, H, 192]: columns 0..127 nope, 128..191 with RoPE already applied -
+                     hpc.mla_rope_norm_store_kv(..., q_pe=q[..., 128:], out_q_pe=q[..., 128:]) does that in place.  Last dim
+                     contiguous, row and head strides multiples of 8 elements and >= 192, base 16-byte aligned;
+      k_nope, v      bfloat16 [Tk, H, 128], any row / head strides that are multiples of 8 and >= 128: the two halves
+                     kv[..., :128] and kv[..., 128:] of the kv_b projection's [Tk, H, 256] output, passed as views;
+      k_pe           bfloat16 [Tk, 64], ONE RoPE'd head shared by all H heads, row stride a multiple of 8 and >= 64:
+                     out_ckv[:, 512:] of hpc.mla_rope_norm_store_kv (row stride 576).  The kernel reads it once per KV tile of a
+                     workgroup; no [Tk, H, 192] tensor is ever materialised;
+      cu_seqlens_q   int32 [B + 1] on the device; cu_seqlens_k int32 [B + 1], or None meaning the same tensor as cu_seqlens_q
+                     (self-attention of the chunk); given, it needs max_seqlens_k.  Only the two max_* ints are read on the
+                     host: a captured hipGraph replayed after the device lengths changed (same maxima) follows the new lengths;
+      softmax_scale  explicit: 1 / sqrt(192) times the model's YaRN factor; positive and finite;
+      output         bfloat16 [Tq, H, 128] and output_lse float32 [Tq, H], contiguous.  When given they are written and
+                     returned (the same objects) and nothing is allocated per call, so the call captures into a hipGraph.
+
+    Limits: 1 <= H <= 65535, any value (group 1: nothing needs a power of two); B <= 65535; row strides <= 2^25 elements.
+    B == 0 or Tq == 0 returns without a launch.  Refused: misaligned bases or strides, strides under 192 / 128 / 64,
+    cu_seqlens_k without max_seqlens_k, negative counts.  NaN / Inf inputs: unspecified.  Reads are bounded by the rows of the
+    request that exist: finite values in rows of other requests, in rows past cu_seqlens[-1] and in the columns around the
+    views do not influence the result.  No float atomics: bit-identical from call to call."""
+    out, lse = torch.ops.hpc_mla.attention_prefill_mla_bf16(
+        q, k_nope, k_pe, v, cu_seqlens_q, int(max_seqlens_q), float(softmax_scale), cu_seqlens_k,
+        None if max_seqlens_k is None else int(max_seqlens_k), bool(causal), output, output_lse, bool(return_lse))
+    out = out if output is None else output
+    if not (return_lse or output_lse is not None):
+        return out
+    return out, (lse if output_lse is None else output_lse)
+
+
+@torch.library.register_fake("hpc_mla::attention_prefill_mla_bf16")
+def _attention_prefill_mla_bf16_fake(q, k_nope, k_pe, v, cu_seqlens_q, max_seqlens_q, softmax_scale, cu_seqlens_k=None,
+                                     max_seqlens_k=None, causal=True, output=None, output_lse=None, return_lse=False):
+    out = output if output is not None else torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.bfloat16, device=q.device)
+    if output_lse is not None:
+        lse = output_lse
+    elif return_lse:
+        lse = torch.empty((q.shape[0], q.shape[1]), dtype=torch.float32, device=q.device)
+    else:
+        lse = torch.empty((0,), dtype=torch.float32, device=q.device)
+    return out, lse
+
+
+def merge_attn_states(out_a: Tensor, lse_a: Tensor, out_b: Tensor, lse_b: Tensor, *, output: Tensor = None,
+                      output_lse: Tensor = None):
+    """Merge two attention results over disjoint key sets by their log-sum-exps into the result over the union: the step
+    that comes with chunked prefill and prefix caching (a chunk's causal self pass and its non-causal pass over the cached
+    context, both from attention_prefill_mla_bf16 with return_lse).  Returns (out, lse).
+
+    No reference counterpart; semantics = tests/mla_prefill_ref.py::merge_statement.  In float32 with one rounding to bf16, per
+    (row, head):
+
+        m = max(la, lb)    wa = exp(la - m)    wb = exp(lb - m)
+        out = (wa a + wb b) / (wa + wb)        lse = m + log(wa + wb)
+
+    A side whose lse is -inf (it saw no key) passes the other side through bit for bit; both -inf give zeros and -inf.
+
+    out_a, out_b   bfloat16 [T, H, D], D % 8 == 0, D <= 512, last dim contiguous, row / head strides multiples of 8 and >= D,
+                   base 16-byte aligned;
+    lse_a, lse_b   float32 [T, H], contiguous, natural log;
+    output         bfloat16 [T, H, D] under the rules of out_a, output_lse float32 [T, H]: written and returned (the same
+                   objects), nothing allocated.  output may be out_a itself and output_lse may be lse_a (merge in place); any
+                   other overlap of an output with an input is refused.
+    T == 0 or H == 0 returns without a launch.  NaN / +Inf lse: unspecified.  A small streaming kernel (16-byte loads and
+    stores, one lane group per row of one head); bit-identical from call to call."""
+    out, lse = torch.ops.hpc_mla.merge_attn_states(out_a, lse_a, out_b, lse_b, output, output_lse)
+    return (out if output is None else output), (lse if output_lse is None else output_lse)
+
+
+@torch.library.register_fake("hpc_mla::merge_attn_states")
+def _merge_attn_states_fake(out_a, lse_a, out_b, lse_b, output=None, output_lse=None):
+    out = output if output is not None else torch.empty(out_a.shape, dtype=torch.bfloat16, device=out_a.device)
+    lse = output_lse if output_lse is not None else torch.empty(lse_a.shape, dtype=torch.float32, device=lse_a.device)
+    return out, lse

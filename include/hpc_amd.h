@@ -554,6 +554,42 @@ int hpc_mla_rope_norm_store_kv_fp8_async(void* ckv_cache, void* out_ckv, void* o
                                          int64_t out_q_pe_row_stride, int64_t out_q_pe_head_stride, float eps, int interleaved,
                                          hpc_stream_t stream);
 
+/* ---- MLA prefill attention, non-absorbed form, bf16, with an lse output (csrc/attention_prefill_mla.hip) ----------------------
+ * No reference kernel; the statement is tests/mla_prefill_ref.py.  Request b has Sq = cu_seqlens_q[b + 1] - cu_seqlens_q[b] q rows
+ * and Lk = cu_seqlens_k[b + 1] - cu_seqlens_k[b] keys (cu_seqlens_k NULL: the cu_seqlens_q array).  Row s sees keys
+ * j <= Lk - Sq + s with causal != 0 (bottom-right aligned) and every j < Lk with causal == 0:
+ *   z_j = softmax_scale * (q[s, h, :128] . k_nope[j, h] + q[s, h, 128:] . k_pe[j])
+ *   out[s, h, :] = bf16( softmax(z) @ v[:, h] )          lse[s, h] = log sum_j exp(z_j)         (fp32, natural log)
+ * A row that sees no key (Lk == 0, or Lk - Sq + s < 0) writes zeros and -inf.  q bf16 [Tq, num_head, 192] (columns 128..191 with
+ * RoPE applied), k_nope / v bf16 [Tk, num_head, 128], k_pe bf16 [Tk, 64] (one head shared by all), each with row (and head)
+ * strides in elements; out bf16 [Tq, num_head, 128] and lse fp32 [Tq, num_head] contiguous, lse may be NULL.  cu_seqlens_* int32
+ * [num_batch + 1] ON THE DEVICE: only max_seqlens_q (the grid) is read on the host, max_seqlens_k (-1: not given) is checked for
+ * being there.  Reads are bounded by the rows of the request that exist; no float atomics, bit-identical from call to call.
+ * Refusals, in this order: HPC_ERR_INVALID for a null out, q, k_nope, k_pe, v or cu_seqlens_q; HPC_ERR_UNSUPPORTED for a base that
+ * is not 16-byte aligned or a stride that is no multiple of 8; HPC_ERR_UNSUPPORTED for a q stride under 192, a k_nope / v stride
+ * under 128, a k_pe row stride under 64; HPC_ERR_INVALID for cu_seqlens_k with max_seqlens_k < 0; HPC_ERR_INVALID for a negative
+ * num_batch or max_seqlens_q, num_head <= 0 or a softmax_scale that is not positive and finite; HPC_ERR_UNSUPPORTED for num_head
+ * or num_batch beyond 65535 or a row stride beyond 2^25.  num_batch == 0 or max_seqlens_q == 0 launches nothing.  Every check is
+ * made on the host before any device call (csrc/attention_prefill_mla_route.h). */
+int hpc_attention_prefill_mla_bf16_async(void* out, float* lse, const void* q, const void* k_nope, const void* k_pe, const void* v,
+                                         const int* cu_seqlens_q, const int* cu_seqlens_k, int num_batch, int num_head,
+                                         int max_seqlens_q, int max_seqlens_k, int64_t q_row_stride, int64_t q_head_stride,
+                                         int64_t k_row_stride, int64_t k_head_stride, int64_t k_pe_row_stride, int64_t v_row_stride,
+                                         int64_t v_head_stride, float softmax_scale, int causal, hpc_stream_t stream);
+
+/* ---- merge of two attention states by their log-sum-exps (csrc/merge_attn_states.hip) ------------------------------------------
+ * No reference kernel; the statement is tests/mla_prefill_ref.py.  In fp32 with one rounding to bf16, per (row, head):
+ *   m = max(la, lb)   wa = exp(la - m)   wb = exp(lb - m)   out = (wa a + wb b) / (wa + wb)   lse = m + log(wa + wb)
+ * a side whose lse is -inf passes the other through bit for bit; both -inf: zeros and -inf.  out / out_a / out_b bf16
+ * [num_rows, num_head, dim] with row and head strides in elements (multiples of 8, >= dim), dim % 8 == 0, dim <= 512; the lse
+ * arrays fp32 [num_rows, num_head] contiguous.  out may be out_a (same base and strides) and lse may be lse_a: in place; any
+ * other overlap of an output with an input is HPC_ERR_UNSUPPORTED, like dim, alignment and the strides; null pointers and
+ * negative counts are HPC_ERR_INVALID.  num_rows == 0 or num_head == 0 launches nothing. */
+int hpc_merge_attn_states_async(void* out, float* lse, const void* out_a, const float* lse_a, const void* out_b, const float* lse_b,
+                                int64_t num_rows, int num_head, int dim, int64_t out_row_stride, int64_t out_head_stride,
+                                int64_t a_row_stride, int64_t a_head_stride, int64_t b_row_stride, int64_t b_head_stride,
+                                hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

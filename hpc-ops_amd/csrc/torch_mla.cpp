@@ -6,7 +6,8 @@
 // (csrc/mla_store.hip).  Each has its twin over the FP8 latent cache (csrc/mla_fp8_format.h: a uint8 tensor of 656-byte rows,
 // strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's dtype, row width and
 // stride rule being the only difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
-// the non-absorbed 192 / 128 form with an lse output) and merge_attn_states (csrc/merge_attn_states.hip).  No kernels here.
+// the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
+// kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  No kernels here.
 #include "mla_fp8_format.h"
 #include "torch_common.h"
 
@@ -113,7 +114,7 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_fp8(const at::Tensor& q,
 // A bf16 tensor whose last dim (of `width`) is contiguous, every other stride a multiple of 8 elements and wide enough that
 // rows (and heads) do not overlap, base 16-byte aligned: kv_a, out_ckv [rows, 576]; q_pe, out_q_pe [rows, H, 64].
 void check_rows_bf16(const at::Tensor& t, const char* name, const at::Tensor& like, at::IntArrayRef shape) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on kv_a's device");
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on the device of the op's first tensor");
   TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
   TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
   const int64_t width = shape.back();
@@ -125,7 +126,7 @@ void check_rows_bf16(const at::Tensor& t, const char* name, const at::Tensor& li
 }
 
 void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, at::ScalarType dtype, int64_t dim) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on kv_a's device");
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on the device of the op's first tensor");
   TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype == at::kInt ? "int32" : "float32");
   TORCH_CHECK(t.dim() == dim && t.is_contiguous(), name, " must be a contiguous ", dim, "-d tensor");
 }
@@ -219,6 +220,60 @@ at::Tensor rope_norm_store_kv_fp8(const c10::optional<at::Tensor>& ckv_cache, co
                                   double eps, bool interleaved) {
   return store_kv(kCacheFp8, "mla_rope_norm_store_kv_fp8", ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
                   block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
+}
+
+// ---- gather_ckv: the reader of that cache for the prompt side (csrc/mla_gather.hip), pinned to tests/mla_gather_ref.py ------------
+// Returns `output` (the caller's) or a fresh contiguous [num_rows, 576]; with `output` nothing is allocated and the call captures
+// into a hipGraph.  Nothing here reads the values of block_ids, cu_seqlens or seq_starts: the row count is the host's.
+at::Tensor gather(const CacheKind& kind, const char* op, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
+                  const at::Tensor& cu_seqlens, const c10::optional<at::Tensor>& seq_starts,
+                  const c10::optional<at::Tensor>& output, c10::optional<int64_t> num_rows) {
+  TORCH_CHECK(ckv_cache.is_cuda(), "ckv_cache tensor must be cuda");
+  check_cache(ckv_cache, kind);
+  check_table(block_ids, "block_ids", ckv_cache, at::kInt, 2);
+  check_table(cu_seqlens, "cu_seqlens", ckv_cache, at::kInt, 1);
+  TORCH_CHECK(cu_seqlens.size(0) >= 1, "cu_seqlens must be [num_req + 1]");
+  const int64_t num_req = cu_seqlens.size(0) - 1;
+  TORCH_CHECK(block_ids.size(0) == num_req, "block_ids must have num_req = ", num_req, " rows");
+  if (seq_starts.has_value()) {
+    check_table(*seq_starts, "seq_starts", ckv_cache, at::kInt, 1);
+    TORCH_CHECK(seq_starts->size(0) == num_req, "seq_starts must be [num_req] = [", num_req, "]");
+  }
+  TORCH_CHECK(output.has_value() || num_rows.has_value(), "one of output and num_rows must be given: the row count is a host value");
+  at::Tensor out;
+  if (output.has_value()) {
+    TORCH_CHECK(output->dim() == 2 && output->size(1) == 576, "output must be [num_rows, 576]");
+    TORCH_CHECK(!num_rows.has_value() || *num_rows == output->size(0), "num_rows = ", num_rows.value_or(0), " but output has ",
+                output->size(0), " rows");
+    check_rows_bf16(*output, "output", ckv_cache, {output->size(0), 576});
+    out = *output;
+  } else {
+    TORCH_CHECK(*num_rows >= 0, "num_rows must not be negative, got ", *num_rows);
+    out = at::empty({*num_rows, 576}, ckv_cache.options().dtype(at::kBFloat16));
+  }
+  const int64_t rows = out.size(0);
+  TORCH_CHECK(rows <= INT32_MAX - 32 && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX && ckv_cache.size(0) <= INT32_MAX,
+              "sizes beyond int32");
+  if (rows == 0 || num_req == 0) return out;  // nothing to launch
+  const int rc = (kind.fp8 ? hpc_mla_gather_ckv_fp8_async : hpc_mla_gather_ckv_async)(
+      ptr(out), ptr(ckv_cache), static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(cu_seqlens.data_ptr()),
+      seq_starts.has_value() ? static_cast<const int*>(seq_starts->data_ptr()) : nullptr, i32(rows), i32(num_req),
+      i32(ckv_cache.size(1)), i32(block_ids.size(1)), i32(ckv_cache.size(0)), ckv_cache.stride(0), ckv_cache.stride(1),
+      out.stride(0), stream_of(ckv_cache));
+  HPC_LAUNCH_CHECK(rc, op);
+  return out;
+}
+
+at::Tensor gather_ckv(const at::Tensor& ckv_cache, const at::Tensor& block_ids, const at::Tensor& cu_seqlens,
+                      const c10::optional<at::Tensor>& seq_starts, const c10::optional<at::Tensor>& output,
+                      c10::optional<int64_t> num_rows) {
+  return gather(kCacheBf16, "mla_gather_ckv", ckv_cache, block_ids, cu_seqlens, seq_starts, output, num_rows);
+}
+
+at::Tensor gather_ckv_fp8(const at::Tensor& ckv_cache, const at::Tensor& block_ids, const at::Tensor& cu_seqlens,
+                          const c10::optional<at::Tensor>& seq_starts, const c10::optional<at::Tensor>& output,
+                          c10::optional<int64_t> num_rows) {
+  return gather(kCacheFp8, "mla_gather_ckv_fp8", ckv_cache, block_ids, cu_seqlens, seq_starts, output, num_rows);
 }
 
 // ---- attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip), pinned to tests/mla_prefill_ref.py -------------------------
@@ -341,6 +396,10 @@ TORCH_LIBRARY(hpc_mla, m) {
   m.def(
       "merge_attn_states(Tensor out_a, Tensor lse_a, Tensor out_b, Tensor lse_b, Tensor? output, Tensor? output_lse) -> "
       "(Tensor, Tensor)");
+  m.def("gather_ckv(Tensor ckv_cache, Tensor block_ids, Tensor cu_seqlens, Tensor? seq_starts, Tensor? output, int? num_rows) -> Tensor");
+  m.def(
+      "gather_ckv_fp8(Tensor ckv_cache, Tensor block_ids, Tensor cu_seqlens, Tensor? seq_starts, Tensor? output, int? num_rows) -> "
+      "Tensor");
   // the cached split-KV scratch buffers (tests fill them with NaN bytes: no piece that was not written may be read)
   m.def("_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMla); });
 }
@@ -352,4 +411,6 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv_fp8);
   m.impl("attention_prefill_mla_bf16", &attention_prefill_mla_bf16);
   m.impl("merge_attn_states", &merge_attn_states);
+  m.impl("gather_ckv", &gather_ckv);
+  m.impl("gather_ckv_fp8", &gather_ckv_fp8);
 }

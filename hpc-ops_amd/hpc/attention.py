@@ -527,3 +527,110 @@ def _merge_attn_states_fake(out_a, lse_a, out_b, lse_b, output=None, output_lse=
     out = output if output is not None else torch.empty(out_a.shape, dtype=torch.bfloat16, device=out_a.device)
     lse = output_lse if output_lse is not None else torch.empty(lse_a.shape, dtype=torch.float32, device=lse_a.device)
     return out, lse
+
+
+def mla_gather_ckv(ckv_cache: Tensor, block_ids: Tensor, cu_seqlens: Tensor, *, seq_starts: Tensor = None,
+                   output: Tensor = None, num_rows: int = None) -> Tensor:
+    """Gather rows of the paged MLA latent cache (bfloat16) into one contiguous tensor: the step between the cache and the
+    kv_b projection in the context pass of chunked prefill and prefix caching.  Returns bfloat16 [T, 576] with the shape
+    and meaning of mla_rope_norm_store_kv's out_ckv: out[:, :512] feeds kv_b, out[:, 512:] is the k_pe operand of
+    attention_prefill_mla_bf16 (row stride 576).
+
+    No reference counterpart; semantics = the PyTorch statement tests/mla_gather_ref.py, which holds no float.  Request b
+    owns the output rows cu_seqlens[b] <= r < cu_seqlens[b + 1]; row r is the token at position
+    pos = seq_starts[b] + (r - cu_seqlens[b]), seq_starts = 0 when it is not given:
+
+        out[r, :] = ckv_cache[block_ids[b, pos // P], pos % P, :576]          (the bits, untouched: no arithmetic)
+
+    Layouts (all on one device):
+      ckv_cache   bfloat16, logical [num_blocks, P, 576], P in {16, 32, 64, 128}; the stride rules of
+                  attention_decode_mla_bf16: block and token strides multiples of 8 elements, token stride >= 576, last dim
+                  contiguous, base 16-byte aligned (padded rows, views into a larger pool).  Cache offsets are 64-bit;
+      block_ids   int32 [B, max_blocks] page table; cu_seqlens int32 [B + 1]; seq_starts int32 [B], the first context
+                  position of each request in this pass (hpc.mla_context_chunks plans the passes);
+      output      bfloat16 [T, 576], last dim contiguous, row stride a multiple of 8 and >= 576, base 16-byte aligned.
+                  Given, it is written and returned (the same object), nothing is allocated and the call captures into a
+                  hipGraph; otherwise num_rows (a host int) sizes a fresh contiguous tensor.  The call is refused when
+                  both are absent, or when they disagree.
+    Nothing on the host reads cu_seqlens, seq_starts or block_ids: T is output.shape[0] or num_rows, and a captured
+    hipGraph replayed after the device lengths changed follows the new lengths.  T == 0 or B == 0 returns without a launch.
+
+    Guards: rows that belong to no request (r < cu_seqlens[0], r >= cu_seqlens[B]) are not written and stay byte-identical,
+    and so do the bytes between the 576 columns and a wider row stride.  A row of a request whose token cannot be fetched
+    is written as 576 zeros: pos < 0, pos // P >= max_blocks, or a page id outside [0, num_blocks) - frameworks pad tables
+    with -1.  Memory safety does not depend on any device value: every index is checked against a host value, and with a
+    cu_seqlens that does not ascend a negative count is an empty request."""
+    out = torch.ops.hpc_mla.gather_ckv(ckv_cache, block_ids, cu_seqlens, seq_starts, output,
+                                       None if num_rows is None else int(num_rows))
+    return out if output is None else output
+
+
+@torch.library.register_fake("hpc_mla::gather_ckv")
+def _mla_gather_ckv_fake(ckv_cache, block_ids, cu_seqlens, seq_starts=None, output=None, num_rows=None):
+    if output is not None:
+        return output
+    if num_rows is None:
+        raise RuntimeError("one of output and num_rows must be given: the row count is a host value")
+    return torch.empty((num_rows, 576), dtype=torch.bfloat16, device=ckv_cache.device)
+
+
+def mla_gather_ckv_fp8(ckv_cache: Tensor, block_ids: Tensor, cu_seqlens: Tensor, *, seq_starts: Tensor = None,
+                       output: Tensor = None, num_rows: int = None) -> Tensor:
+    """mla_gather_ckv over the FP8 latent KV cache that hpc.mla_rope_norm_store_kv_fp8 writes and attention_decode_mla_fp8
+    reads: the gather and the dequantisation in one pass.  Returns bfloat16 [T, 576].  Arguments, the row-to-position rule
+    (request b owns rows cu_seqlens[b] <= r < cu_seqlens[b + 1], pos = seq_starts[b] + (r - cu_seqlens[b])), output /
+    num_rows, the guards (rows of no request are not written; pos < 0, pos // P >= max_blocks or a page id outside
+    [0, num_blocks) give 576 zeros; no device value is trusted with an address) and the hipGraph statement are those of
+    mla_gather_ckv; nothing on the host reads cu_seqlens, seq_starts or block_ids.
+
+    ckv_cache is a torch.uint8 tensor, logical [num_blocks, P, 656], P in {16, 32, 64, 128}: last dim contiguous, token
+    stride >= 656 bytes and a multiple of 16, block stride a multiple of 16, base 16-byte aligned.  With code, scale and the
+    RoPE part read from the 656-byte row of the token (bytes 0 .. 511, 512 .. 527, 528 .. 655):
+
+        out[r, d]    = bf16_rne( fp32(code[d]) * scale[d // 128] ),  d < 512     one float32 multiply, one rounding
+        out[r, 512:] = the 64 bfloat16 at byte offset 528                        (the bits, untouched)
+
+    That is tests/mla_fp8_ref.py::dequantise of the row, the dequantisation attention_decode_mla_fp8 applies
+    (csrc/mla_fp8_format.h): a prompt chunk and a decode step read the same keys from the same cache, bit for bit.  A scale
+    of 0 makes its group zeros.  NaN codes (0x7f / 0xff) and non-finite scales: unspecified."""
+    out = torch.ops.hpc_mla.gather_ckv_fp8(ckv_cache, block_ids, cu_seqlens, seq_starts, output,
+                                           None if num_rows is None else int(num_rows))
+    return out if output is None else output
+
+
+torch.library.register_fake("hpc_mla::gather_ckv_fp8")(_mla_gather_ckv_fake)
+
+
+def mla_context_chunks(context_lens, workspace_rows: int):
+    """Plan the context passes of chunked prefill on the host: cut every request's cached context [0, L_b) into passes so
+    that one pass gathers at most workspace_rows rows in all (the bound of the mla_gather_ckv output and of the kv_b
+    projection behind it).  context_lens is a sequence of B host ints - schedulers hold them on the host - and no device
+    memory is read.
+
+    Every pass gives each request the same share = workspace_rows // B rounded down to a multiple of 128 rows; a
+    workspace_rows below 128 * B is refused.  Pass p covers positions [p * share, min((p + 1) * share, L_b)) of request b;
+    a request whose context is exhausted contributes 0 rows.  There are ceil(max_b L_b / share) passes, none with all
+    lengths 0.
+
+    Returns a list with one tuple per pass:
+      seq_starts  CPU int32 tensor [B], for mla_gather_ckv(seq_starts=...);
+      cu_seqlens  CPU int32 tensor [B + 1], for mla_gather_ckv and attention_prefill_mla_bf16(cu_seqlens_k=...);
+      max_len     int, the longest piece of the pass, for max_seqlens_k."""
+    lens = [int(n) for n in context_lens]
+    workspace_rows = int(workspace_rows)
+    if any(n < 0 for n in lens):
+        raise ValueError("context_lens must not be negative")
+    if not lens or max(lens) == 0:
+        return []
+    share = workspace_rows // len(lens) // 128 * 128
+    if share < 128:
+        raise ValueError(f"workspace_rows = {workspace_rows} is below 128 rows for each of the {len(lens)} requests")
+    passes = []
+    for first in range(0, max(lens), share):
+        counts = [min(share, max(n - first, 0)) for n in lens]
+        cu = [0]
+        for c in counts:
+            cu.append(cu[-1] + c)
+        passes.append((torch.tensor([min(first, n) for n in lens], dtype=torch.int32), torch.tensor(cu, dtype=torch.int32),
+                       max(counts)))
+    return passes

@@ -590,6 +590,35 @@ int hpc_merge_attn_states_async(void* out, float* lse, const void* out_a, const 
                                 int64_t a_row_stride, int64_t a_head_stride, int64_t b_row_stride, int64_t b_head_stride,
                                 hpc_stream_t stream);
 
+/* ---- MLA latent-cache gather: paged latent cache -> contiguous bf16 rows (csrc/mla_gather.hip) -----------------------------------
+ * No reference kernel; the statement is tests/mla_gather_ref.py, without a float in it.  The step between the cache and the kv_b
+ * projection of a chunked-prefill context pass.  Request b owns output rows cu_seqlens[b] <= r < cu_seqlens[b + 1]; row r is the
+ * token at pos = seq_starts[b] + (r - cu_seqlens[b]) (seq_starts NULL: zeros):
+ *   out[r, :576] = ckv_cache[block_ids[b, pos / block_size], pos % block_size, :576]                       the bits, untouched
+ * out bf16 [num_rows, 576] with a row stride in elements (a multiple of 8, >= 576 with more than one row), ckv_cache as in
+ * hpc_attention_decode_mla_bf16_async (token (page, t) at ckv_cache + page * ckv_block_stride + t * ckv_token_stride, strides in
+ * elements and multiples of 8, token stride >= 576), every base 16-byte aligned.  block_ids int32 [num_req, max_blocks],
+ * cu_seqlens int32 [num_req + 1], seq_starts int32 [num_req], all ON THE DEVICE and never read by the host: num_rows is the
+ * host's bound on r.  Rows of no request (r < cu_seqlens[0], r >= cu_seqlens[num_req], or outside the range of the request a
+ * cu_seqlens that does not ascend leads to) are not written, nor are the bytes between 576 columns and the row stride.  A row
+ * of a request whose token cannot be fetched - pos < 0, pos / block_size >= max_blocks, a page id outside [0, num_blocks) - is
+ * written as 576 zeros.  The kernel trusts no device value with an address; cache offsets are 64-bit.
+ * HPC_ERR_INVALID: negative counts, and with num_rows > 0 and num_req > 0 a null out, ckv_cache, block_ids or cu_seqlens;
+ * HPC_ERR_UNSUPPORTED: block_size outside 16 / 32 / 64 / 128, the strides, alignment, num_rows beyond INT32_MAX - 32, strides
+ * whose offsets would leave 2^60 bytes.  num_rows == 0 or num_req == 0 launches nothing.  Every check is made on the host
+ * before any device call. */
+int hpc_mla_gather_ckv_async(void* out, const void* ckv_cache, const int* block_ids, const int* cu_seqlens, const int* seq_starts,
+                             int num_rows, int num_req, int block_size, int max_blocks, int num_blocks, int64_t ckv_block_stride,
+                             int64_t ckv_token_stride, int64_t out_row_stride, hpc_stream_t stream);
+/* The same from the FP8 latent cache described above: ckv_cache holds 656-byte rows and its two strides are in BYTES (multiples
+ * of 16, token stride >= 656); everything else, the guards and the refusals are those of hpc_mla_gather_ckv_async.  A fetched
+ * row is dequantised as hpc_attention_decode_mla_fp8_async does it, one fp32 multiply and one rounding:
+ *   out[r, d] = bf16_rne( fp32(code[d]) * scale[d / 128] ), d < 512        out[r, 512:] = bytes 528 .. 655, untouched */
+int hpc_mla_gather_ckv_fp8_async(void* out, const void* ckv_cache, const int* block_ids, const int* cu_seqlens,
+                                 const int* seq_starts, int num_rows, int num_req, int block_size, int max_blocks, int num_blocks,
+                                 int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes, int64_t out_row_stride,
+                                 hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

@@ -7,7 +7,8 @@
 // strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's dtype, row width and
 // stride rule being the only difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
 // the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
-// kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  No kernels here.
+// kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  Either side of the decode attention the
+// two absorb matmuls, absorb_q and unabsorb_o (csrc/mla_absorb.hip).  No kernels here.
 #include "mla_fp8_format.h"
 #include "torch_common.h"
 
@@ -374,9 +375,86 @@ std::tuple<at::Tensor, at::Tensor> merge_attn_states(const at::Tensor& out_a, co
   return {out, lse};
 }
 
+// ---- absorb_q / unabsorb_o (csrc/mla_absorb.hip), pinned to tests/mla_absorb_ref.py --------------------------------------------
+// dtype, device, shape and the contiguous last dim here; strides, alignment, H and overlap are the route's
+// (csrc/mla_absorb_route.h) and come back in its words.  With the outputs given nothing is allocated and nothing is read on the host.
+void check_absorb_operand(const at::Tensor& t, const char* name, const at::Tensor& like, at::IntArrayRef shape,
+                          at::ScalarType dtype = at::kBFloat16) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on the first tensor's device");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype);
+  TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
+  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
+}
+
+at::Tensor absorb_q(const at::Tensor& q_nope, const at::Tensor& w_uk, const c10::optional<at::Tensor>& output) {
+  TORCH_CHECK(q_nope.is_cuda(), "q_nope tensor must be cuda");
+  TORCH_CHECK(q_nope.dim() == 3 && q_nope.size(2) == 128, "q_nope must be [T, num_head, 128]");
+  const int64_t t = q_nope.size(0), h = q_nope.size(1);
+  TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
+  check_absorb_operand(q_nope, "q_nope", q_nope, {t, h, 128});
+  check_absorb_operand(w_uk, "w_uk", q_nope, {h, 128, 512});
+  at::Tensor out;
+  if (output.has_value()) {
+    check_absorb_operand(*output, "output", q_nope, {t, h, 512});
+    out = *output;
+  } else {
+    out = at::empty({t, h, 512}, q_nope.options());
+  }
+  const char* why = hpc_mla_absorb_q_refusal(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1),
+                                             w_uk.stride(0), w_uk.stride(1), out.stride(0), out.stride(1));
+  TORCH_CHECK(why == nullptr, "mla_absorb_q: ", why);
+  if (t == 0) return out;  // nothing to launch
+  const int rc = hpc_mla_absorb_q_async(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1),
+                                        w_uk.stride(0), w_uk.stride(1), out.stride(0), out.stride(1), stream_of(q_nope));
+  HPC_LAUNCH_CHECK(rc, "mla_absorb_q");
+  return out;
+}
+
+// (o, scale): quant false: o bf16 [T, H * 128] and an empty scale; quant true: the (x, x_scale) pair of gemm_blockwise_fp8
+std::tuple<at::Tensor, at::Tensor> unabsorb_o(const at::Tensor& o_lat, const at::Tensor& w_uv, const c10::optional<at::Tensor>& output,
+                                              bool quant, const c10::optional<at::Tensor>& output_scale) {
+  TORCH_CHECK(o_lat.is_cuda(), "o_lat tensor must be cuda");
+  TORCH_CHECK(o_lat.dim() == 3 && o_lat.size(2) == 512, "o_lat must be [T, num_head, 512]");
+  const int64_t t = o_lat.size(0), h = o_lat.size(1);
+  TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
+  check_absorb_operand(o_lat, "o_lat", o_lat, {t, h, 512});
+  check_absorb_operand(w_uv, "w_uv", o_lat, {h, 128, 512});
+  TORCH_CHECK(quant || !output_scale.has_value(), "output_scale needs quant=True");
+  const at::ScalarType odt = quant ? kF8 : at::kBFloat16;
+  at::Tensor out, scale = at::empty({0}, o_lat.options().dtype(at::kFloat));
+  if (output.has_value()) {
+    check_absorb_operand(*output, "output", o_lat, {t, h * 128}, odt);
+    out = *output;
+  } else {
+    out = at::empty({t, h * 128}, o_lat.options().dtype(odt));
+  }
+  if (quant) {
+    if (output_scale.has_value()) {
+      check_absorb_operand(*output_scale, "output_scale", o_lat, {t, h}, at::kFloat);
+      TORCH_CHECK(output_scale->is_contiguous(), "output_scale must be contiguous");
+      scale = *output_scale;
+    } else {
+      scale = at::empty({t, h}, o_lat.options().dtype(at::kFloat));
+    }
+  }
+  // a [1, N] or [0, N] tensor carries any row stride: the route is told the contiguous one
+  const int64_t out_rs = t > 1 ? out.stride(0) : h * 128;
+  float* sp = quant ? static_cast<float*>(scale.data_ptr()) : nullptr;
+  const char* why = hpc_mla_unabsorb_o_refusal(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1),
+                                               w_uv.stride(0), w_uv.stride(1), out_rs, quant ? 1 : 0);
+  TORCH_CHECK(why == nullptr, "mla_unabsorb_o: ", why);
+  if (t == 0) return {out, scale};  // nothing to launch
+  const int rc = hpc_mla_unabsorb_o_async(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1),
+                                          w_uv.stride(0), w_uv.stride(1), out_rs, quant ? 1 : 0, stream_of(o_lat));
+  HPC_LAUNCH_CHECK(rc, "mla_unabsorb_o");
+  return {out, scale};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hpc_mla, m) {
+  m.def("absorb_q(Tensor q_nope, Tensor w_uk, Tensor? output) -> Tensor");
+  m.def("unabsorb_o(Tensor o_lat, Tensor w_uv, Tensor? output, bool quant, Tensor? output_scale) -> (Tensor, Tensor)");
   m.def(
       "rope_norm_store_kv(Tensor? ckv_cache, Tensor kv_a, Tensor cos_sin, Tensor kv_norm_weight, Tensor num_seqlen_per_req, "
       "Tensor q_index, Tensor block_ids, Tensor? q_pe, Tensor? out_q_pe, Tensor? out_ckv, float eps, bool interleaved) -> Tensor");
@@ -413,4 +491,6 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("merge_attn_states", &merge_attn_states);
   m.impl("gather_ckv", &gather_ckv);
   m.impl("gather_ckv_fp8", &gather_ckv_fp8);
+  m.impl("absorb_q", &absorb_q);
+  m.impl("unabsorb_o", &unabsorb_o);
 }

@@ -109,6 +109,10 @@ _sig("hpc_attention_prefill_mla_bf16_async", I, P, P, P, P, P, P, IP, IP, I, I, 
 _sig("hpc_merge_attn_states_async", I, P, P, P, P, P, P, L, I, I, L, L, L, L, L, L, P)
 _sig("hpc_mla_gather_ckv_async", I, P, P, IP, IP, IP, I, I, I, I, I, L, L, L, P)
 _sig("hpc_mla_gather_ckv_fp8_async", I, P, P, IP, IP, IP, I, I, I, I, I, L, L, L, P)
+_sig("hpc_mla_absorb_q_refusal", c_char_p, P, P, P, L, I, L, L, L, L, L, L)
+_sig("hpc_mla_absorb_q_async", I, P, P, P, L, I, L, L, L, L, L, L, P)
+_sig("hpc_mla_unabsorb_o_refusal", c_char_p, P, P, P, P, L, I, L, L, L, L, L, I)
+_sig("hpc_mla_unabsorb_o_async", I, P, P, P, P, L, I, L, L, L, L, L, I, P)
 _sig("hpc_reformat_x_scale_async", I, P, P, P, P, I, I, I, I, P)
 _sig("hpc_stem_oam_prep_paged_kv_async", I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, L, L, L, L, L, L,
      L, L, L, P)

@@ -601,6 +601,79 @@ def mla_gather_ckv_fp8(ckv_cache: Tensor, block_ids: Tensor, cu_seqlens: Tensor,
 torch.library.register_fake("hpc_mla::gather_ckv_fp8")(_mla_gather_ckv_fake)
 
 
+def mla_absorb_q(q_nope: Tensor, w_uk: Tensor, *, output: Tensor = None) -> Tensor:
+    """The first absorb matmul of an MLA decode step: W_UK folded into the query, per head.  Returns bfloat16 [T, H, 512],
+    the first 512 columns of the q that attention_decode_mla_bf16 / _fp8 take.
+
+    No reference counterpart; semantics = tests/mla_absorb_ref.py::absorb_q_statement.  With fp32 accumulation and one rounding:
+
+        out[t, h, c] = bf16( sum_{d < 128} float(q_nope[t, h, d]) * float(w_uk[h, d, c]) ),   c < 512
+
+    q_nope   bfloat16 [T, H, 128], last dim contiguous, row and head strides multiples of 8 elements, base 16-byte aligned:
+             q[..., :128] of the q_b output [T, H, 192] is taken as it stands, columns 128 .. 191 are never read;
+    w_uk     bfloat16 [H, 128, 512], last dim contiguous, head and d strides multiples of 8 elements: the view
+             w_kv_b.view(H, 256, 512)[:, :128] of the dequantised kv_b_proj weight [H * 256, 512], without a copy (the
+             kernel transposes on chip);
+    output   bfloat16 [T, H, 512] under q_nope's stride rules, heads and rows not overlapping: q_abs[..., :512] of the
+             [T, H, 576] buffer is written in place and its columns 512 .. 575 - where mla_rope_norm_store_kv(out_q_pe=)
+             puts q_pe - are never touched, in either call order.  Given, it is written and returned (the same object),
+             nothing is allocated, nothing is read on the host and the call captures into a hipGraph; otherwise a contiguous
+             tensor is returned.  An output that shares bytes with an input is refused.
+    1 <= H <= 128 (no multiple-of-16 rule); T == 0 returns without a launch; offsets are 64-bit.  No split-K, no atomics, no
+    workspace: bit-identical from call to call."""
+    out = torch.ops.hpc_mla.absorb_q(q_nope, w_uk, output)
+    return out if output is None else output
+
+
+@torch.library.register_fake("hpc_mla::absorb_q")
+def _mla_absorb_q_fake(q_nope, w_uk, output=None):
+    if output is not None:
+        return output
+    return torch.empty((q_nope.shape[0], q_nope.shape[1], 512), dtype=torch.bfloat16, device=q_nope.device)
+
+
+def mla_unabsorb_o(o_lat: Tensor, w_uv: Tensor, *, output: Tensor = None, quant: bool = False, output_scale: Tensor = None):
+    """The second absorb matmul of an MLA decode step: W_UV applied to the latent attention output, per head, laid out for
+    the output projection.  quant=False returns bfloat16 [T, H * 128]; quant=True returns the (x, x_scale) pair of
+    gemm_blockwise_fp8: (codes float8_e4m3fn [T, H * 128], scale float32 [T, H]) - a head's 128 columns are one block.
+
+    No reference counterpart; semantics = tests/mla_absorb_ref.py::unabsorb_o_statement.  fp32 accumulation, one rounding:
+
+        o[t, h * 128 + v] = bf16( sum_{c < 512} float(o_lat[t, h, c]) * float(w_uv[h, v, c]) ),   v < 128
+        quant:  scale[t, h] = amax_v |o| / 448      codes = e4m3fn( o * (1 / (scale + 1e-8)) )     on the bf16-rounded o
+
+    The quantised pair is bit-identical to hpc.blockwise_fp8_quant(hpc.mla_unabsorb_o(..., quant=False)), and the bf16 values
+    behind it are the same bits in both modes (the same accumulation order).
+
+    o_lat    bfloat16 [T, H, 512], the decode op's output; last dim contiguous, row and head strides multiples of 8 elements,
+             base 16-byte aligned;
+    w_uv     bfloat16 [H, 128, 512], last dim contiguous, head and row strides multiples of 8: the view
+             w_kv_b.view(H, 256, 512)[:, 128:] of the same kv_b weight, without a copy;
+    output   quant=False: bfloat16 [T, H * 128], last dim contiguous, row stride a multiple of 8 and >= H * 128;
+             quant=True: float8_e4m3fn [T, H * 128] and output_scale float32 [T, H], both contiguous.  Given, they are written
+             and returned (the same objects), nothing is allocated or read on the host and the call captures into a hipGraph.
+    1 <= H <= 128; T == 0 returns empty tensors without a launch; offsets are 64-bit.  No split-K, no atomics, no workspace:
+    bit-identical from call to call."""
+    o, s = torch.ops.hpc_mla.unabsorb_o(o_lat, w_uv, output, bool(quant), output_scale)
+    o = o if output is None else output
+    if not quant:
+        return o
+    return o, (s if output_scale is None else output_scale)
+
+
+@torch.library.register_fake("hpc_mla::unabsorb_o")
+def _mla_unabsorb_o_fake(o_lat, w_uv, output=None, quant=False, output_scale=None):
+    t, h = o_lat.shape[0], o_lat.shape[1]
+    if output_scale is not None and not quant:
+        raise RuntimeError("output_scale needs quant=True")
+    o = output if output is not None else torch.empty(
+        (t, h * 128), dtype=torch.float8_e4m3fn if quant else torch.bfloat16, device=o_lat.device)
+    if not quant:
+        return o, torch.empty((0,), dtype=torch.float32, device=o_lat.device)
+    s = output_scale if output_scale is not None else torch.empty((t, h), dtype=torch.float32, device=o_lat.device)
+    return o, s
+
+
 def mla_context_chunks(context_lens, workspace_rows: int):
     """Plan the context passes of chunked prefill on the host: cut every request's cached context [0, L_b) into passes so
     that one pass gathers at most workspace_rows rows in all (the bound of the mla_gather_ckv output and of the kv_b

@@ -619,6 +619,35 @@ int hpc_mla_gather_ckv_fp8_async(void* out, const void* ckv_cache, const int* bl
                                  int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes, int64_t out_row_stride,
                                  hpc_stream_t stream);
 
+/* ---- MLA absorb matmuls: W_UK into q, W_UV out of the latent attention output (csrc/mla_absorb.hip) -----------------------------
+ * No reference kernel; the statements are tests/mla_absorb_ref.py.  bf16 operands, fp32 accumulation, one rounding:
+ *   absorb_q     out[t, h, c] = bf16( sum_{d < 128} q_nope[t, h, d] * w_uk[h, d, c] ),  c < 512
+ *   unabsorb_o   o[t, h * 128 + v] = bf16( sum_{c < 512} o_lat[t, h, c] * w_uv[h, v, c] ),  v < 128
+ * q_nope [T, H, 128], o_lat [T, H, 512] and absorb_q's out [T, H, 512]: last dim contiguous, row and head strides in elements,
+ * multiples of 8 (views such as q[..., :128] of [T, H, 192] and q_abs[..., :512] of [T, H, 576]: the columns outside are
+ * neither read nor written).  w_uk / w_uv [H, 128, 512]: last dim contiguous, head and row strides multiples of 8, row
+ * stride >= 512 - the two halves of kv_b.view(H, 256, 512).  Every base 16-byte aligned.  unabsorb_o's out: quant == 0: bf16
+ * [T, H * 128] with a row stride >= H * 128, a multiple of 8; quant != 0: e4m3fn codes [T, H * 128] and out_scale f32 [T, H],
+ * both contiguous (out_row_stride == H * 128), the rule of hpc_blockwise_fp8_quant_async per (token, head) on the bf16-rounded
+ * o: scale = amax / 448, code = e4m3fn(o * (1 / (scale + 1e-8))) - bit for bit that op on the quant == 0 output.
+ * 1 <= H <= 128; num_tokens == 0 launches nothing; offsets are 64-bit.  No workspace, no atomics: the same bits on every call.
+ * Every check is made on the host before any device call (csrc/mla_absorb_route.h).  HPC_ERR_INVALID: a negative
+ * num_tokens, null pointers (num_tokens > 0), out_scale without quant; HPC_ERR_UNSUPPORTED: H, the strides, alignment, an
+ * output that shares bytes with an input.  hpc_mla_*_refusal return the refusal of the same call in words, one message per
+ * rule, or NULL for a call that is accepted: pure host functions. */
+const char* hpc_mla_absorb_q_refusal(const void* out, const void* q_nope, const void* w_uk, int64_t num_tokens, int num_head,
+                                     int64_t q_row_stride, int64_t q_head_stride, int64_t w_head_stride, int64_t w_row_stride,
+                                     int64_t out_row_stride, int64_t out_head_stride);
+int hpc_mla_absorb_q_async(void* out, const void* q_nope, const void* w_uk, int64_t num_tokens, int num_head,
+                           int64_t q_row_stride, int64_t q_head_stride, int64_t w_head_stride, int64_t w_row_stride,
+                           int64_t out_row_stride, int64_t out_head_stride, hpc_stream_t stream);
+const char* hpc_mla_unabsorb_o_refusal(const void* out, const float* out_scale, const void* o_lat, const void* w_uv,
+                                       int64_t num_tokens, int num_head, int64_t o_row_stride, int64_t o_head_stride,
+                                       int64_t w_head_stride, int64_t w_row_stride, int64_t out_row_stride, int quant);
+int hpc_mla_unabsorb_o_async(void* out, float* out_scale, const void* o_lat, const void* w_uv, int64_t num_tokens, int num_head,
+                             int64_t o_row_stride, int64_t o_head_stride, int64_t w_head_stride, int64_t w_row_stride,
+                             int64_t out_row_stride, int quant, hpc_stream_t stream);
+
 /* x_scale [rows, n = K/128] -> transposed, tile-padded, compact [n, m] layout that
  * hpc_group_gemm_blockwise_fp8_async reads (DeepEP-format inputs).
  * reference: reformat_x_scale_async, src/group_gemm/group_gemm.h:27-29 (entry src/group_gemm/entry.cc:170-222). */

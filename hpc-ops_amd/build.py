@@ -119,7 +119,9 @@ def build_torch_shim(force: bool = False, dev: bool = False):
 
     srcs = sorted(CSRC.glob("torch_*.cpp"))
     shim, lib = (SHIM_DEV, LIB_DEV) if dev else (SHIM, LIB)
-    deps = srcs + [CSRC / "torch_common.h", INCLUDE / "hpc_amd.h", Path(__file__)]
+    # every header, as _deps_newer: the shim's sources include more of csrc/*.h than torch_common.h
+    hdrs = list(CSRC.glob("*.h")) + list(INCLUDE.glob("*.h")) + [Path(__file__)]
+    deps = srcs + hdrs
     if not force and shim.exists() and all(d.stat().st_mtime <= shim.stat().st_mtime for d in deps) \
             and shim.stat().st_mtime >= lib.stat().st_mtime:
         return shim
@@ -132,8 +134,7 @@ def build_torch_shim(force: bool = False, dev: bool = False):
 
     def one(src):
         obj = OBJ / "torch" / (src.stem + ".o")
-        if not force and obj.exists() and all(d.stat().st_mtime <= obj.stat().st_mtime
-                                              for d in (src, CSRC / "torch_common.h", INCLUDE / "hpc_amd.h", Path(__file__))):
+        if not force and obj.exists() and all(d.stat().st_mtime <= obj.stat().st_mtime for d in [src] + hdrs):
             return obj
         r = subprocess.run(cc + ["-c", str(src), "-o", str(obj)], capture_output=True, text=True)
         if r.returncode != 0:

@@ -30,9 +30,10 @@
 // FP8 latent cache (kFp8, hpc_attention_decode_mla_fp8_async): the row of mla_fp8_format.h - 512 e4m3 codes, four fp32 scales,
 // the 64 RoPE columns in bf16, 656 B.  Only the gather differs: thread (rr, sub) stages per row the four 16-byte code chunks
 // sub + 8 i (chunk sub + 8 i lies in scale group i), the scale quad and RoPE chunk sub - 12 quads where the bf16 form stages
-// 18 - and the commit turns each code chunk into 16 bf16 (cvt to fp32, ONE fp32 multiply by the group's scale, RNE pack) stored
-// as two 16-byte quads at element column 16 (sub + 8 i).  The LDS image is byte for byte what the bf16 form builds from the
-// dequantised cache, and everything behind it is the same code: the two ops agree bit for bit on such a pair of caches.
+// 18 - and the commit turns each code chunk into 16 bf16 (dequant16 of mla_fp8_format.h, which mla_gather.hip uses too: cvt to
+// fp32, ONE fp32 multiply by the group's scale, RNE pack) stored as two 16-byte quads at element column 16 (sub + 8 i).  The
+// LDS image is byte for byte what the bf16 form builds from the dequantised cache, and everything behind it is the same code:
+// the two ops agree bit for bit on such a pair of caches.  The row's dimensions and the host rule for a cache: mla_cache.h.
 #include "attention_decode_mla_route.h"
 #include "mla_fp8_format.h"
 #include "hpc_amd.h"
@@ -45,11 +46,11 @@ constexpr int kThreads = 256;
 constexpr int kRowBytes = 1184;               // LDS pitch of a latent row (1,152 B of data)
 constexpr int kBufBytes = kMlaKvTile * kRowBytes;
 constexpr int kLds = 2 * kBufBytes;           // 151,552 B
-constexpr int kKSteps = kMlaDim / 32;         // 18 MFMA k-steps over the 576 columns
-constexpr int kColBlocks = kMlaDimV / 16;     // 32 output column blocks
+constexpr int kKSteps = kMlaRow / 32;         // 18 MFMA k-steps over the 576 columns
+constexpr int kColBlocks = kMlaLatent / 16;   // 32 output column blocks
 constexpr float kLn2 = 0.693147180559945309f;
 constexpr float kLog2e = 1.442695040888963407f;
-static_assert(4 * 16 * kMlaDimV * 4 + 4 * 16 * 2 * 4 <= kLds, "the narrow form's merge fits the tile images");
+static_assert(4 * 16 * kMlaLatent * 4 + 4 * 16 * 2 * 4 <= kLds, "the narrow form's merge fits the tile images");
 
 struct Args {
   const uint8_t* q;
@@ -80,10 +81,10 @@ __device__ __forceinline__ int piece_len(int len, int splits) {
 __device__ __forceinline__ void emit4(const Args& a, int piece, int64_t grow, int col, f32x4 v, float l) {
   if (a.splits == 1) {
     const float inv = 1.0f / l;
-    *reinterpret_cast<u32x2*>(a.out + grow * kMlaDimV + col) =
+    *reinterpret_cast<u32x2*>(a.out + grow * kMlaLatent + col) =
         u32x2{pack_bf16x2(v[0] * inv, v[1] * inv), pack_bf16x2(v[2] * inv, v[3] * inv)};
   } else {
-    *reinterpret_cast<f32x4*>(a.ws_o + (piece * a.total_rows + grow) * kMlaDimV + col) = v;
+    *reinterpret_cast<f32x4*>(a.ws_o + (piece * a.total_rows + grow) * kMlaLatent + col) = v;
   }
 }
 __device__ __forceinline__ void emit_ml(const Args& a, int piece, int64_t grow, float m, float l) {
@@ -92,20 +93,6 @@ __device__ __forceinline__ void emit_ml(const Args& a, int piece, int64_t grow, 
   } else {
     *reinterpret_cast<f32x2*>(a.ws_ml + (piece * a.total_rows + grow) * 2) = f32x2{m, l};
   }
-}
-
-// 16 e4m3 codes -> 16 bf16 = bf16_rne(fp32(code) * scale): the dequantisation of mla_fp8_format.h
-__device__ __forceinline__ void dequant16(const u32x4 codes, const float scale, u32x4& lo, u32x4& hi) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), false);
-    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), true);
-    w[2 * j] = pack_bf16x2(a[0] * scale, a[1] * scale);
-    w[2 * j + 1] = pack_bf16x2(b[0] * scale, b[1] * scale);
-  }
-  lo = u32x4{w[0], w[1], w[2], w[3]};
-  hi = u32x4{w[4], w[5], w[6], w[7]};
 }
 
 template <bool kNarrow, bool kFp8>
@@ -137,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
 
   bf16x8 qf[kKSteps];
   if (active) {
-    const uint8_t* qrow = a.q + grow * (kMlaDim * 2) + g * 16;
+    const uint8_t* qrow = a.q + grow * (kMlaRow * 2) + g * 16;
 #pragma unroll
     for (int ks = 0; ks < kKSteps; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + ks * 64);
   }
@@ -191,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
           *reinterpret_cast<u32x4*>(dst + sub * 16 + i * 256) = lo;
           *reinterpret_cast<u32x4*>(dst + sub * 16 + i * 256 + 16) = hi;
         }
-        *reinterpret_cast<u32x4*>(dst + kMlaDimV * 2) = stg[p][5];
+        *reinterpret_cast<u32x4*>(dst + kMlaLatent * 2) = stg[p][5];
       } else {
 #pragma unroll
         for (int i = 0; i < 9; ++i) *reinterpret_cast<u32x4*>(dst + i * 128) = stg[p][i];
@@ -304,7 +291,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   } else {
     // the four waves' states of the same 16 rows: scale to the common maximum, sum in wave order
     float* s_f = reinterpret_cast<float*>(s_mem);      // [4][16][512]
-    float* s_ml = s_f + 4 * 16 * kMlaDimV;             // [4][16][2]
+    float* s_ml = s_f + 4 * 16 * kMlaLatent;           // [4][16][2]
     l = row4_sum(l);
     if (g == 0) {
       s_ml[(wv * 16 + c16) * 2] = m;
@@ -317,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
     const float f = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mm);
 #pragma unroll
     for (int cb = 0; cb < kColBlocks; ++cb)
-      *reinterpret_cast<f32x4*>(s_f + (wv * 16 + c16) * kMlaDimV + 16 * cb + 4 * g) = acc[cb] * f;
+      *reinterpret_cast<f32x4*>(s_f + (wv * 16 + c16) * kMlaLatent + 16 * cb + 4 * g) = acc[cb] * f;
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -331,7 +318,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
       for (int w = 0; w < 4; ++w) {
         const float mw = s_ml[(w * 16 + row) * 2], lw = s_ml[(w * 16 + row) * 2 + 1];
         lt += (mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - mr)) * lw;
-        sum += *reinterpret_cast<const f32x4*>(s_f + (w * 16 + row) * kMlaDimV + col);
+        sum += *reinterpret_cast<const f32x4*>(s_f + (w * 16 + row) * kMlaLatent + col);
       }
       const int64_t gr = static_cast<int64_t>(b) * a.rows + row;
       emit4(a, piece, gr, col, sum, lt);
@@ -362,11 +349,11 @@ __global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const A
     if (ml[1] > 0.f) {
       const float f = __builtin_amdgcn_exp2f(ml[0] - mm);
       lt += f * ml[1];
-      sum += *reinterpret_cast<const f32x4*>(a.ws_o + (p * a.total_rows + grow) * kMlaDimV + col) * f;
+      sum += *reinterpret_cast<const f32x4*>(a.ws_o + (p * a.total_rows + grow) * kMlaLatent + col) * f;
     }
   }
   const float inv = 1.0f / lt;
-  *reinterpret_cast<u32x2*>(a.out + grow * kMlaDimV + col) =
+  *reinterpret_cast<u32x2*>(a.out + grow * kMlaLatent + col) =
       u32x2{pack_bf16x2(sum[0] * inv, sum[1] * inv), pack_bf16x2(sum[2] * inv, sum[3] * inv)};
   if (a.lse && threadIdx.x == 0) a.lse[grow] = (mm + __builtin_log2f(lt)) * kLn2;
 }
@@ -395,25 +382,27 @@ extern "C" int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int n
 }
 
 namespace {
-// Both launchers: the checks, the route and the launches.  The cache's strides come in units of `unit` bytes (2: the bf16
-// cache's elements, 1: the FP8 cache's bytes); a token's row is `row_units` of them and both strides are multiples of
-// `align_units` (16 bytes either way).
+// Both launchers: the checks, the route and the launches.  What a valid cache is - its page size, its strides in the kind's
+// units (bf16 elements or FP8 bytes) and its alignment - is mla_cache_check() of mla_cache.h.
 template <bool kFp8>
 int mla_decode_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr, const int* block_ids_ptr,
                       const int* num_seq_kvcache_ptr, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
                       int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale, int new_kv_included, int splits,
                       void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
   using namespace hpc::mla;
-  constexpr int unit = kFp8 ? 1 : 2, row_units = kFp8 ? hpc::kMlaFp8RowBytes : hpc::kMlaDim, align_units = 16 / unit;
+  constexpr hpc::MlaCacheKind kind = kFp8 ? hpc::kMlaCacheFp8 : hpc::kMlaCacheBf16;
   if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr) return HPC_ERR_INVALID;
-  if (splits < 0 || max_blocks < 0 || ckv_block_stride < 0) return HPC_ERR_INVALID;
+  // the cache's invalid argument (a negative block stride) is refused here with the others, what it does not support behind
+  // the shapes: a call with two faults keeps the code of the earlier check
+  const hpc::MlaCacheCheck cache =
+      hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_ptr), block_size, ckv_block_stride, ckv_token_stride);
+  if (splits < 0 || max_blocks < 0 || cache.code == HPC_ERR_INVALID) return HPC_ERR_INVALID;
   // the split count is the caller's, or with 0 the route's for this device; shapes are refused before the device is asked
   const hpc::MlaRoute shape = hpc::mla_route(num_batch, num_seq_q, num_head, splits > 0 ? splits : 1, 256);
   if (shape.code != HPC_OK) return shape.code;
-  if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
-  if (ckv_token_stride < row_units || ckv_token_stride % align_units || ckv_block_stride % align_units) return HPC_ERR_UNSUPPORTED;
+  if (cache.code != HPC_OK) return cache.code;
   if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(q_ptr) | reinterpret_cast<uintptr_t>(ckv_ptr)) & 15) return HPC_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(q_ptr) & 15) return HPC_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3)) return HPC_ERR_UNSUPPORTED;
   if (num_batch == 0) return HPC_OK;
   if (max_blocks == 0) return HPC_ERR_INVALID;
@@ -432,15 +421,15 @@ int mla_decode_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const vo
   a.lse = lse_ptr;
   a.ws_o = static_cast<float*>(workspace_ptr);
   a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
-  a.block_stride_bytes = ckv_block_stride * unit;
-  a.token_stride_bytes = ckv_token_stride * unit;
+  a.block_stride_bytes = ckv_block_stride * kind.unit;
+  a.token_stride_bytes = ckv_token_stride * kind.unit;
   a.total_rows = static_cast<int64_t>(num_batch) * r.rows;
   a.num_head = num_head;
   a.num_seq_q = num_seq_q;
   a.rows = r.rows;
   a.row_tiles = r.row_tiles;
   a.splits = r.splits;
-  a.page_shift = block_size == 16 ? 4 : (block_size == 32 ? 5 : (block_size == 64 ? 6 : 7));
+  a.page_shift = hpc::mla_page_shift(block_size);
   a.max_blocks = max_blocks;
   a.new_kv_included = new_kv_included ? 1 : 0;
   a.scale_log2 = softmax_scale * kLog2e;

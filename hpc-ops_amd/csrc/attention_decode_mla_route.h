@@ -7,11 +7,11 @@
 #include <stdint.h>
 
 #include "hpc_common.h"
+#include "mla_cache.h"
 
 namespace hpc {
 
-constexpr int kMlaDim = 576;        // latent row: 512 compressed KV + 64 RoPE
-constexpr int kMlaDimV = 512;       // the columns that are also V
+// the row's dimensions are mla_cache.h's: kMlaRow columns are K, the first kMlaLatent of them are also V
 constexpr int kMlaRowTile = 64;     // q rows (r = s * num_head + h) per workgroup: four waves x 16 rows
 constexpr int kMlaKvTile = 64;      // tokens per LDS image; piece lengths are multiples of it
 constexpr int kMlaMaxSplits = 64;   // pieces the merge sums at most
@@ -72,7 +72,7 @@ static inline MlaRoute mla_route(int num_batch, int num_seq_q, int num_head, int
   r.grid = static_cast<int>(w * r.splits);
   if (r.splits > 1) {
     r.merge_grid = static_cast<int>(total_rows);
-    r.ml_offset = static_cast<int64_t>(r.splits) * total_rows * kMlaDimV * 4;
+    r.ml_offset = static_cast<int64_t>(r.splits) * total_rows * kMlaLatent * 4;
     r.workspace_bytes = r.ml_offset + static_cast<int64_t>(r.splits) * total_rows * 2 * 4;
   }
   return r;

@@ -6,11 +6,12 @@
 #include <stdint.h>
 
 #include "hpc_common.h"
+#include "mla_cache.h"
 
 namespace hpc {
 
 constexpr int kMlaPrefillDimNope = 128;  // q / k columns without RoPE, and the v head
-constexpr int kMlaPrefillDimPe = 64;     // RoPE columns: behind the nope columns in q, one shared head in k_pe
+constexpr int kMlaPrefillDimPe = kMlaRope;  // RoPE columns: behind the nope columns in q, one shared head in k_pe
 constexpr int kMlaPrefillDimQk = kMlaPrefillDimNope + kMlaPrefillDimPe;
 constexpr int kMlaPrefillRowTile = 128;  // q positions of one head per workgroup: four waves x 32 rows
 constexpr int kMlaPrefillKvTile = 64;    // tokens per LDS image

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hpc_status.h"
+
 namespace hpc {
 
 constexpr int kWave = 64;
@@ -202,13 +204,7 @@ __device__ __forceinline__ u32x2 buf_ld8(rsrc_t rs, int voff, int soff) {
 
 }  // namespace hpc
 
-// Error convention of the C-ABI (include/hpc_amd.h): 0 = launched, negative = refused.
-#define HPC_OK 0
-#define HPC_ERR_UNSUPPORTED (-1)
-#define HPC_ERR_INVALID (-2)
-#define HPC_ERR_LAUNCH (-3)
-#define HPC_ERR_TIMEOUT (-4)
-
+// the status codes: hpc_status.h
 #define HPC_CHECK_LAUNCH()                               \
   do {                                                   \
     if (hipGetLastError() != hipSuccess) return HPC_ERR_LAUNCH; \

@@ -9,6 +9,7 @@
 // may be lse_a (in place): every lane has read what it needs before the workgroup's barrier and stores behind it.
 // Host side: the grid and the shape refusals are attention_prefill_mla_route.h::merge_route(); the overlap rule is checked here.
 #include "attention_prefill_mla_route.h"
+#include "byte_span.h"
 #include "hpc_common.h"
 #include "../../include/hpc_amd.h"
 
@@ -74,17 +75,6 @@ __global__ __launch_bounds__(kMergeThreads) void merge_attn_states_kernel(const 
 
 using namespace hpc;
 
-namespace {
-struct Span {
-  uintptr_t lo, hi;
-};
-Span span_of(const void* p, int64_t rows, int heads, int64_t row_stride, int64_t head_stride, int width, int elem) {
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-  return {lo, lo + static_cast<uintptr_t>(((rows - 1) * row_stride + (heads - 1) * head_stride + width) * elem)};
-}
-bool disjoint(Span x, Span y) { return x.hi <= y.lo || y.hi <= x.lo; }
-}  // namespace
-
 // no reference kernel; the statement is tests/mla_prefill_ref.py
 extern "C" int hpc_merge_attn_states_async(void* out, float* lse, const void* out_a, const float* lse_a, const void* out_b,
                                            const float* lse_b, int64_t num_rows, int num_head, int dim, int64_t out_row_stride,
@@ -97,14 +87,14 @@ extern "C" int hpc_merge_attn_states_async(void* out, float* lse, const void* ou
                                    strides);
   if (r.code != HPC_OK || r.empty) return r.code;
   // outputs may be the a side exactly (same base, same strides: in place); any other overlap of an output with an input is refused
-  const Span so = span_of(out, num_rows, num_head, out_row_stride, out_head_stride, dim, 2);
-  const Span sa = span_of(out_a, num_rows, num_head, a_row_stride, a_head_stride, dim, 2);
-  const Span sb = span_of(out_b, num_rows, num_head, b_row_stride, b_head_stride, dim, 2);
-  const Span sl = span_of(lse, num_rows, num_head, num_head, 1, 1, 4), sla = span_of(lse_a, num_rows, num_head, num_head, 1, 1, 4);
-  const Span slb = span_of(lse_b, num_rows, num_head, num_head, 1, 1, 4);
+  const ByteSpan so = byte_span(out, num_rows, out_row_stride, num_head, out_head_stride, dim, 2);
+  const ByteSpan sa = byte_span(out_a, num_rows, a_row_stride, num_head, a_head_stride, dim, 2);
+  const ByteSpan sb = byte_span(out_b, num_rows, b_row_stride, num_head, b_head_stride, dim, 2);
+  const ByteSpan sl = byte_span(lse, num_rows, num_head, num_head, 1, 1, 4), sla = byte_span(lse_a, num_rows, num_head, num_head, 1, 1, 4);
+  const ByteSpan slb = byte_span(lse_b, num_rows, num_head, num_head, 1, 1, 4);
   const bool o_in_place = out == out_a && out_row_stride == a_row_stride && out_head_stride == a_head_stride;
-  if (!(o_in_place || disjoint(so, sa)) || !disjoint(so, sb) || !(lse == lse_a || disjoint(sl, sla)) || !disjoint(sl, slb) ||
-      !disjoint(so, sla) || !disjoint(so, slb) || !disjoint(so, sl) || !disjoint(sl, sa) || !disjoint(sl, sb))
+  if ((!o_in_place && overlap(so, sa)) || overlap(so, sb) || (lse != lse_a && overlap(sl, sla)) || overlap(sl, slb) ||
+      overlap(so, sla) || overlap(so, slb) || overlap(so, sl) || overlap(sl, sa) || overlap(sl, sb))
     return HPC_ERR_UNSUPPORTED;
   const Args p{static_cast<uint16_t*>(out), lse, static_cast<const uint16_t*>(out_a), lse_a, static_cast<const uint16_t*>(out_b), lse_b,
                num_rows * num_head, num_head, r.lanes_per_row, r.rows_per_wg,

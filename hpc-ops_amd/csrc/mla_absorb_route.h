@@ -12,12 +12,14 @@
 #pragma once
 #include <stdint.h>
 
+#include "byte_span.h"
 #include "hpc_common.h"
+#include "mla_cache.h"
 
 namespace hpc {
 
 constexpr int kMlaAbsorbNope = 128;     // q_nope columns = rows of a head's w_uk = rows of a head's w_uv = the v head
-constexpr int kMlaAbsorbLatent = 512;   // latent columns
+constexpr int kMlaAbsorbLatent = kMlaLatent;  // latent columns
 constexpr int kMlaAbsorbMaxHead = 128;
 constexpr int kMlaAbsorbThreads = 256;
 constexpr int kMlaAbsorbTokTile = 64;   // tokens per workgroup: four blocks of 16, the weight fragments stay in registers
@@ -46,21 +48,9 @@ struct MlaAbsorbRoute {
   int threads;
 };
 
-namespace mla_absorb_detail {
-// bytes [lo, hi) of a [T, H, width] tensor of `elem`-byte elements
-struct Span {
-  uintptr_t lo, hi;
-};
-static inline Span span_of(uintptr_t base, int64_t t, int64_t rs, int64_t h, int64_t hs, int64_t width, int64_t elem) {
-  return Span{base, base + static_cast<uintptr_t>(elem * ((t - 1) * rs + (h - 1) * hs + width))};
-}
-static inline bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
-}  // namespace mla_absorb_detail
-
 // Refusals in this order (a call with two faults gets the earlier one); all before the empty call but the null pointers,
 // which an empty call may carry.  (static: the product and the development library may sit in one process)
 static inline MlaAbsorbRoute mla_absorb_route(const MlaAbsorbCall& c, bool unabsorb) {
-  using namespace mla_absorb_detail;
   MlaAbsorbRoute r{};
   auto refuse = [&r](int code, const char* why) { return r.code = code, r.why = why, r; };
   const int64_t T = c.num_tokens, H = c.num_head;
@@ -102,13 +92,13 @@ static inline MlaAbsorbRoute mla_absorb_route(const MlaAbsorbCall& c, bool unabs
   if ((c.out | c.x | c.w) & 15) return refuse(HPC_ERR_UNSUPPORTED, "a base address is not 16-byte aligned");
   if (c.out_scale & 3) return refuse(HPC_ERR_UNSUPPORTED, "output_scale is not 4-byte aligned");
   // an output that shares bytes with an input: other workgroups still read what one overwrites
-  const Span xs = span_of(c.x, T, c.x_row_stride, H, c.x_head_stride, x_width, 2);
-  const Span ws = span_of(c.w, 1, 0, H, c.w_head_stride, (kMlaAbsorbNope - 1) * c.w_row_stride + kMlaAbsorbLatent, 2);
-  const Span os = unabsorb ? span_of(c.out, T, c.out_row_stride, 1, 0, H * kMlaAbsorbNope, c.quant ? 1 : 2)
-                           : span_of(c.out, T, c.out_row_stride, H, c.out_head_stride, out_width, 2);
+  const ByteSpan xs = byte_span(c.x, T, c.x_row_stride, H, c.x_head_stride, x_width, 2);
+  const ByteSpan ws = byte_span(c.w, 1, 0, H, c.w_head_stride, (kMlaAbsorbNope - 1) * c.w_row_stride + kMlaAbsorbLatent, 2);
+  const ByteSpan os = unabsorb ? byte_span(c.out, T, c.out_row_stride, 1, 0, H * kMlaAbsorbNope, c.quant ? 1 : 2)
+                           : byte_span(c.out, T, c.out_row_stride, H, c.out_head_stride, out_width, 2);
   if (overlap(os, xs) || overlap(os, ws)) return refuse(HPC_ERR_UNSUPPORTED, "the output overlaps an input");
   if (c.quant) {
-    const Span ss = span_of(c.out_scale, T, H, 1, 0, H, 4);
+    const ByteSpan ss = byte_span(c.out_scale, T, H, 1, 0, H, 4);
     if (overlap(ss, xs) || overlap(ss, ws) || overlap(ss, os)) return refuse(HPC_ERR_UNSUPPORTED, "output_scale overlaps another tensor");
   }
   r.tok_tile = static_cast<int>(tok_tile);

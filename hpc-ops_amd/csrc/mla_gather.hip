@@ -3,7 +3,8 @@
 // Ours only (no reference kernel): the step between the cache that hpc_mla_rope_norm_store_kv[_fp8]_async writes and the kv_b
 // projection of a chunked-prefill context pass, whose output rows have the shape and meaning of the writer's out_ckv.
 // Semantics = the float-free PyTorch statement tests/mla_gather_ref.py: the bf16 cache is copied bit for bit, the FP8 cache is
-// dequantised as hpc_attention_decode_mla_fp8_async does it (c[d] = bf16_rne(fp32(code[d]) * scale[d / 128])).
+// dequantised by the code hpc_attention_decode_mla_fp8_async dequantises it with, dequant16 of mla_fp8_format.h
+// (c[d] = bf16_rne(fp32(code[d]) * scale[d / 128])).  The row's dimensions and the host rule for a cache: mla_cache.h.
 //
 // MI355X design: a pure stream, 1,152 bytes out per token - no LDS, no matrix instruction, 16-byte accesses only.  A 64-lane
 // wave owns kRowsPerWave = 8 consecutive output rows, a workgroup of four waves a tile of 32:
@@ -20,6 +21,7 @@
 // FP8, up to 32 waves per CU); the stores are plain vector stores.  Device values are never trusted with an address: the
 // output row comes from the grid and the host's num_rows alone, see `resolve`.
 #include "hpc_common.h"
+#include "mla_cache.h"
 #include "mla_fp8_format.h"
 #include "../../include/hpc_amd.h"
 
@@ -39,25 +41,9 @@ struct Args {
 
 constexpr int kThreads = 256;
 constexpr int kRowsPerWave = 8, kRowsPerBlock = kRowsPerWave * (kThreads / 64);
-constexpr int kLatent = 512, kRope = 64;
-constexpr int kRowBytes = 2 * (kLatent + kRope);   // 1,152: an output row, and a bf16 cache row
+constexpr int kRowBytes = 2 * kMlaRow;             // 1,152: an output row, and a bf16 cache row
 constexpr int kRowChunks = kRowBytes / 16;         // 72
 constexpr long kNotWritten = -1, kZeros = -2;      // marks in place of a row's cache offset (an offset is >= 0)
-
-// 16 e4m3 codes -> 16 bf16 = bf16_rne(fp32(code) * scale): the dequantisation of mla_fp8_format.h.  The twin of dequant16 in
-// attention_decode_mla.hip, copied so that file stays as it is; tests/test_mla_gather.py holds both to the same bits.
-__device__ __forceinline__ void dequant16(const u32x4 codes, const float scale, u32x4& lo, u32x4& hi) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), false);
-    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(codes[j]), true);
-    w[2 * j] = pack_bf16x2(a[0] * scale, a[1] * scale);
-    w[2 * j + 1] = pack_bf16x2(b[0] * scale, b[1] * scale);
-  }
-  lo = u32x4{w[0], w[1], w[2], w[3]};
-  hi = u32x4{w[4], w[5], w[6], w[7]};
-}
 
 // Where output row `row` comes from: its byte offset in the cache, kZeros for a row of a request whose token cannot be fetched,
 // kNotWritten for a row of no request.  Every index is checked against a host value before it is used: b stays in [0, num_req),
@@ -113,9 +99,9 @@ __global__ __launch_bounds__(kThreads) void mla_gather_kernel(const Args a) {
       if (src[i] != kNotWritten) st16(a.out + (row0 + r) * a.out_rs + 16 * k, src[i] >= 0 ? v[i] : zero);
     }
   } else {
-    constexpr int kCodeChunks = kLatent / 16;                // 32 per row
+    constexpr int kCodeChunks = kMlaLatent / 16;             // 32 per row
     constexpr int kN = kRowsPerWave * kCodeChunks / 64;      // 4 per lane
-    constexpr int kRopeChunks = 2 * kRope / 16;              // 8 per row: one per lane
+    constexpr int kRopeChunks = 2 * kMlaRope / 16;           // 8 per row: one per lane
     static_assert(kRowsPerWave * kRopeChunks == 64 && kMlaFp8Group % 16 == 0, "one RoPE chunk per lane, a chunk in one group");
     long src[kN];
     u32x4 codes[kN];
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void mla_gather_kernel(const Args a) {
         st16(dst + 16, src[i] >= 0 ? hi : zero);
       }
     }
-    if (rsrc != kNotWritten) st16(a.out + (row0 + rr) * a.out_rs + 2 * kLatent + 16 * rk, rsrc >= 0 ? rope : zero);
+    if (rsrc != kNotWritten) st16(a.out + (row0 + rr) * a.out_rs + 2 * kMlaLatent + 16 * rk, rsrc >= 0 ? rope : zero);
   }
 }
 
@@ -150,37 +136,32 @@ __global__ __launch_bounds__(kThreads) void mla_gather_kernel(const Args a) {
 }  // namespace hpc
 
 namespace {
-// Both launchers: the checks and the launch.  kFp8: the cache is the FP8 row and its two strides are in bytes (multiples of 16,
-// a token >= 656); otherwise they are in bf16 elements (multiples of 8, a token >= 576) - 16 bytes either way.
+// Both launchers: the checks and the launch.  What a valid cache is - its page size, its strides in the kind's units (bf16
+// elements or FP8 bytes) and its alignment - is mla_cache_check() of mla_cache.h.
 template <bool kFp8>
 int mla_gather_launch(void* out, const void* ckv_cache, const int* block_ids, const int* cu_seqlens, const int* seq_starts,
                       int num_rows, int num_req, int block_size, int max_blocks, int num_blocks, int64_t ckv_block_stride,
                       int64_t ckv_token_stride, int64_t out_row_stride, hipStream_t stream) {
+  using namespace hpc;
   using namespace hpc::mla_gather;
-  constexpr int64_t cache_row = kFp8 ? hpc::kMlaFp8RowBytes : kLatent + kRope, cache_align = kFp8 ? hpc::kMlaFp8Align : 8;
-  constexpr int64_t cache_elem = kFp8 ? 1 : 2;
+  constexpr MlaCacheKind kind = kFp8 ? kMlaCacheFp8 : kMlaCacheBf16;
   // every check on the host, before any device call
-  if (num_rows < 0 || num_req < 0 || max_blocks < 0 || num_blocks < 0 || ckv_block_stride < 0) return HPC_ERR_INVALID;
+  if (num_rows < 0 || num_req < 0 || max_blocks < 0 || num_blocks < 0) return HPC_ERR_INVALID;
   const bool work = num_rows > 0 && num_req > 0;
   if (work && (!out || !ckv_cache || !block_ids || !cu_seqlens)) return HPC_ERR_INVALID;
-  if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
-  const auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
-  const auto bad_cache_stride = [](int64_t s) { return s < 0 || s % cache_align != 0; };
-  if (misaligned(ckv_cache) || bad_cache_stride(ckv_block_stride) || bad_cache_stride(ckv_token_stride) ||
-      ckv_token_stride < cache_row)
-    return HPC_ERR_UNSUPPORTED;
-  if (misaligned(out) || out_row_stride < 0 || out_row_stride % 8 != 0) return HPC_ERR_UNSUPPORTED;
-  if (num_rows > 1 && out_row_stride < kLatent + kRope) return HPC_ERR_UNSUPPORTED;  // rows would overlap
+  const MlaCacheCheck cache =
+      mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_cache), block_size, ckv_block_stride, ckv_token_stride);
+  if (cache.code != HPC_OK) return cache.code;
+  if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || out_row_stride < 0 || out_row_stride % 8 != 0) return HPC_ERR_UNSUPPORTED;
+  if (num_rows > 1 && out_row_stride < kMlaRow) return HPC_ERR_UNSUPPORTED;  // rows would overlap
   // sizes beyond int32 (the grid's row arithmetic) and cache offsets beyond 64 bits
   if (num_rows > INT32_MAX - kRowsPerBlock || num_req == INT32_MAX) return HPC_ERR_UNSUPPORTED;
   constexpr int64_t kSpan = int64_t{1} << 60;  // bytes: page id x block stride + token x token stride stays below 2^61
-  if (ckv_token_stride > kSpan / cache_elem / 128 || out_row_stride > kSpan / 2 / INT32_MAX ||
-      (num_blocks > 0 && ckv_block_stride > kSpan / cache_elem / num_blocks))
+  if (ckv_token_stride > kSpan / kind.unit / 128 || out_row_stride > kSpan / 2 / INT32_MAX ||
+      (num_blocks > 0 && ckv_block_stride > kSpan / kind.unit / num_blocks))
     return HPC_ERR_UNSUPPORTED;
   if (!work) return HPC_OK;  // nothing to launch
 
-  int page_shift = 0;
-  while ((1 << page_shift) < block_size) ++page_shift;
   Args a{};
   a.cache = static_cast<const uint8_t*>(ckv_cache);
   // a row that fetches nothing still issues its loads, from an address that always holds a row: the cache's first cell, or
@@ -190,12 +171,12 @@ int mla_gather_launch(void* out, const void* ckv_cache, const int* block_ids, co
   a.cu_seqlens = cu_seqlens;
   a.seq_starts = seq_starts;
   a.out = static_cast<uint8_t*>(out);
-  a.cache_bs = ckv_block_stride * cache_elem;
-  a.cache_ts = ckv_token_stride * cache_elem;
+  a.cache_bs = ckv_block_stride * kind.unit;
+  a.cache_ts = ckv_token_stride * kind.unit;
   a.out_rs = out_row_stride * 2;
   a.num_rows = num_rows;
   a.num_req = num_req;
-  a.page_shift = page_shift;
+  a.page_shift = mla_page_shift(block_size);
   a.max_blocks = max_blocks;
   a.num_blocks = num_blocks;
   const int grid = (num_rows + kRowsPerBlock - 1) / kRowsPerBlock;

@@ -2,7 +2,8 @@
 //
 // Ours only (no reference kernel): the producer of hpc_attention_decode_mla_bf16_async's inputs, which defines their wire
 // format - one latent row of 576 bf16 per token (512 normalised compressed KV + 64 RoPE'd k_pe) in the paged cache, and the
-// RoPE columns of the absorbed-q buffer.  Semantics = the float64 PyTorch statement tests/mla_store_ref.py.
+// RoPE columns of the absorbed-q buffer.  Semantics = the float64 PyTorch statement tests/mla_store_ref.py.  The row's
+// dimensions and the host rule for a cache are mla_cache.h's, shared with the cache's readers.
 //
 // MI355X design: pure stream / latency work like rope.hip - no LDS, no matrix instruction.  One 64-lane wave per unit:
 //   latent unit (one per row)      lane l owns columns 8l..8l+7 of the 512 (one 16-byte load, its 8 norm weights loaded
@@ -21,7 +22,9 @@
 // a four-step xor-shuffle, the codes are the project's 128-column quantiser (act_quant.h) and leave as one 8-byte store per
 // lane, the scale as one 4-byte store per group, k_pe unquantised from lanes 0..7.  out_ckv and out_q_pe are the bf16 form's.
 #include "act_quant.h"
+#include "byte_span.h"
 #include "hpc_common.h"
+#include "mla_cache.h"
 #include "mla_fp8_format.h"
 #include "../../include/hpc_amd.h"
 
@@ -45,7 +48,6 @@ struct Args {
 };
 
 constexpr int kThreads = 256;
-constexpr int kLatent = 512, kRope = 64;
 constexpr int kHeadsPerGroup = 8;  // 8 lanes per 128-byte head: a wave takes 8 heads per pass
 // Groups of 8 heads a q-unit wave takes behind ONE position lookup, like rope.hip's kU = 2.  Measured at 1, 2 and 4
 // (profiles/mla_store.txt): 2 is within 0.8 us of the fastest at every size - 64 us against 84 us with 1 at 8192 rows x 128
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
 #pragma unroll
   for (int u = 0; u < kU; ++u) {
     pe[u].raw = u32x4{0u, 0u, 0u, 0u};
-    if (has_piece(u)) pe[u].load(latent ? src_row + kLatent : a.q_pe + row * a.q_rs + (head0 + u * kHeadsPerGroup) * a.q_hs, j);
+    if (has_piece(u)) pe[u].load(latent ? src_row + kMlaLatent : a.q_pe + row * a.q_rs + (head0 + u * kHeadsPerGroup) * a.q_hs, j);
   }
 
   // ---- request and position of this row (wave-uniform): last b with q_index[b] <= row ------------------------------
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
   }
   if (live) {
     const int tp = pos < a.max_pos ? pos : a.max_pos - 1;  // beyond the table: unspecified result, no read out of bounds
-    const float* cs = a.cos_sin + static_cast<long>(tp) * kRope + 4 * j;
+    const float* cs = a.cos_sin + static_cast<long>(tp) * kMlaRope + 4 * j;
     const f32x4 c = *reinterpret_cast<const f32x4*>(cs), s = *reinterpret_cast<const f32x4*>(cs + 32);
 #pragma unroll
     for (int u = 0; u < kU; ++u) pe[u].rotate(c, s);  // a piece that does not exist turns zeros
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-  const float r = rsqrtf(wave_sum(ss) * (1.0f / kLatent) + a.eps);
+  const float r = rsqrtf(wave_sum(ss) * (1.0f / kMlaLatent) + a.eps);
   u32x4 o;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
     }
   } else if (store) {
     st16(a.cache + cell + 8 * lane, o);
-    if (lane < 8) pe[0].store(a.cache + cell + kLatent, j);
+    if (lane < 8) pe[0].store(a.cache + cell + kMlaLatent, j);
   }
   if (a.out_ckv) {
     if (!live) {
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
     }
     uint16_t* dst = a.out_ckv + row * a.out_ckv_rs;
     st16(dst + 8 * lane, o);
-    if (lane < 8) pe[0].store(dst + kLatent, j);
+    if (lane < 8) pe[0].store(dst + kMlaLatent, j);
   }
 }
 
@@ -234,8 +236,8 @@ __global__ __launch_bounds__(kThreads) void mla_store_kernel(const Args a) {
 }  // namespace hpc
 
 namespace {
-// Both launchers: the checks and the launch.  kFp8: the cache is the FP8 row and its two strides are in bytes (multiples of 16,
-// a token >= 656); otherwise they are in bf16 elements (multiples of 8, a token >= 576) - 16 bytes either way.
+// Both launchers: the checks and the launch.  What a valid cache is - its page size, its strides in the kind's units (bf16
+// elements or FP8 bytes) and its alignment - is mla_cache_check() of mla_cache.h; a call without a cache skips it.
 template <bool kFp8>
 int mla_store_launch(void* ckv_cache, void* out_ckv, void* out_q_pe, const void* kv_a, const void* q_pe, const float* cos_sin,
                      const float* kv_norm_weight, const int* num_seqlen_per_req, const int* q_index, const int* block_ids,
@@ -243,47 +245,42 @@ int mla_store_launch(void* ckv_cache, void* out_ckv, void* out_q_pe, const void*
                      int64_t ckv_block_stride, int64_t ckv_token_stride, int64_t kv_a_row_stride, int64_t out_ckv_row_stride,
                      int64_t q_pe_row_stride, int64_t q_pe_head_stride, int64_t out_q_pe_row_stride,
                      int64_t out_q_pe_head_stride, float eps, int interleaved, hipStream_t stream) {
+  using namespace hpc;
   using namespace hpc::mla_store;
-  constexpr int64_t cache_row = kFp8 ? hpc::kMlaFp8RowBytes : kLatent + kRope, cache_align = kFp8 ? hpc::kMlaFp8Align : 8;
+  constexpr MlaCacheKind kind = kFp8 ? kMlaCacheFp8 : kMlaCacheBf16;
   // every check on the host, before any device call
   if (num_rows < 0 || num_req < 0 || num_head < 0 || max_blocks < 0 || num_blocks < 0 || max_pos < 0) return HPC_ERR_INVALID;
   if (!kv_a || !cos_sin || !kv_norm_weight || !num_seqlen_per_req || !q_index) return HPC_ERR_INVALID;
   if (!ckv_cache && !out_ckv) return HPC_ERR_INVALID;      // neither destination
   if ((q_pe == nullptr) != (out_q_pe == nullptr)) return HPC_ERR_INVALID;
-  if (ckv_cache && (!block_ids || ckv_block_stride < 0)) return HPC_ERR_INVALID;
+  if (ckv_cache && !block_ids) return HPC_ERR_INVALID;
   if (max_pos == 0) return HPC_ERR_INVALID;
+  if (ckv_cache) {  // behind every other invalid argument, in front of everything else that is not supported
+    const MlaCacheCheck cache =
+        mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_cache), block_size, ckv_block_stride, ckv_token_stride);
+    if (cache.code != HPC_OK) return cache.code;
+  }
   const auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
   const auto bad_stride = [](int64_t s) { return s < 0 || s % 8 != 0; };
   if (q_pe && (num_head < 1 || num_head > 128)) return HPC_ERR_UNSUPPORTED;
   if (misaligned(kv_a) || misaligned(cos_sin) || misaligned(kv_norm_weight) || bad_stride(kv_a_row_stride)) return HPC_ERR_UNSUPPORTED;
-  if (num_rows > 1 && kv_a_row_stride < kLatent + kRope) return HPC_ERR_UNSUPPORTED;
-  int page_shift = 0;
-  if (ckv_cache) {
-    if (block_size != 16 && block_size != 32 && block_size != 64 && block_size != 128) return HPC_ERR_UNSUPPORTED;
-    while ((1 << page_shift) < block_size) ++page_shift;
-    const auto bad_cache_stride = [](int64_t s) { return s < 0 || s % cache_align != 0; };
-    if (misaligned(ckv_cache) || bad_cache_stride(ckv_block_stride) || bad_cache_stride(ckv_token_stride) ||
-        ckv_token_stride < cache_row)
-      return HPC_ERR_UNSUPPORTED;
-  }
+  if (num_rows > 1 && kv_a_row_stride < kMlaRow) return HPC_ERR_UNSUPPORTED;
   if (out_ckv && (misaligned(out_ckv) || bad_stride(out_ckv_row_stride))) return HPC_ERR_UNSUPPORTED;
-  if (out_ckv && num_rows > 1 && out_ckv_row_stride < kLatent + kRope) return HPC_ERR_UNSUPPORTED;  // rows would overlap
+  if (out_ckv && num_rows > 1 && out_ckv_row_stride < kMlaRow) return HPC_ERR_UNSUPPORTED;  // rows would overlap
   if (q_pe && (misaligned(q_pe) || misaligned(out_q_pe) || bad_stride(q_pe_row_stride) || bad_stride(q_pe_head_stride) ||
                bad_stride(out_q_pe_row_stride) || bad_stride(out_q_pe_head_stride)))
     return HPC_ERR_UNSUPPORTED;
-  if (q_pe && ((num_head > 1 && (q_pe_head_stride < kRope || out_q_pe_head_stride < kRope)) ||
-               (num_rows > 1 && (q_pe_row_stride < kRope || out_q_pe_row_stride < kRope))))
+  if (q_pe && ((num_head > 1 && (q_pe_head_stride < kMlaRope || out_q_pe_head_stride < kMlaRope)) ||
+               (num_rows > 1 && (q_pe_row_stride < kMlaRope || out_q_pe_row_stride < kMlaRope))))
     return HPC_ERR_UNSUPPORTED;  // heads or rows would overlap
   if (q_pe && num_rows > 0) {
     // an output row must end before the next one starts, and out_q_pe may share memory with q_pe only as the same tensor
     // (in place: a lane reads and writes the same bytes); any other overlap would let one wave read what another wrote
-    const int64_t row_extent = (num_head - 1) * out_q_pe_head_stride + kRope;
-    if (num_rows > 1 && out_q_pe_row_stride < row_extent) return HPC_ERR_UNSUPPORTED;
+    if (num_rows > 1 && out_q_pe_row_stride < (num_head - 1) * out_q_pe_head_stride + kMlaRope) return HPC_ERR_UNSUPPORTED;
     const bool in_place = q_pe == out_q_pe && q_pe_row_stride == out_q_pe_row_stride && q_pe_head_stride == out_q_pe_head_stride;
-    const auto lo = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-    const uintptr_t in_hi = lo(q_pe) + 2 * ((num_rows - 1) * q_pe_row_stride + (num_head - 1) * q_pe_head_stride + kRope);
-    const uintptr_t out_hi = lo(out_q_pe) + 2 * ((num_rows - 1) * out_q_pe_row_stride + row_extent);
-    if (!in_place && lo(q_pe) < out_hi && lo(out_q_pe) < in_hi) return HPC_ERR_UNSUPPORTED;
+    const ByteSpan in = byte_span(q_pe, num_rows, q_pe_row_stride, num_head, q_pe_head_stride, kMlaRope, 2);
+    const ByteSpan out = byte_span(out_q_pe, num_rows, out_q_pe_row_stride, num_head, out_q_pe_head_stride, kMlaRope, 2);
+    if (!in_place && overlap(in, out)) return HPC_ERR_UNSUPPORTED;
   }
   const int q_units = q_pe ? (num_head + kHeadsPerGroup * kGroupsPerWave - 1) / (kHeadsPerGroup * kGroupsPerWave) : 0;
   const int64_t units = static_cast<int64_t>(num_rows) * (1 + q_units);  // one wave each
@@ -312,7 +309,7 @@ int mla_store_launch(void* ckv_cache, void* out_ckv, void* out_q_pe, const void*
   a.num_rows = num_rows;
   a.num_req = num_req;
   a.num_head = num_head;
-  a.page_shift = page_shift;
+  a.page_shift = ckv_cache ? mla_page_shift(block_size) : 0;
   a.max_blocks = ckv_cache ? max_blocks : 0;
   a.num_blocks = num_blocks;
   a.max_pos = max_pos;

@@ -4,46 +4,92 @@
 // given nothing is allocated per call beyond the cached scratch and the call captures into a hipGraph.  Nothing here reads the
 // values of num_seq_kvcache.  Below it rope_norm_store_kv, the op that writes that cache and the RoPE columns of q
 // (csrc/mla_store.hip).  Each has its twin over the FP8 latent cache (csrc/mla_fp8_format.h: a uint8 tensor of 656-byte rows,
-// strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's dtype, row width and
-// stride rule being the only difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
+// strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's kind (csrc/mla_cache.h:
+// row width, stride unit and the one host rule for a valid cache, which check_cache prints) and dtype being the only
+// difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
 // the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
 // kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  Either side of the decode attention the
 // two absorb matmuls, absorb_q and unabsorb_o (csrc/mla_absorb.hip).  No kernels here.
-#include "mla_fp8_format.h"
+#include "byte_span.h"
+#include "mla_cache.h"
 #include "torch_common.h"
 
 using namespace hpc_torch;
 
 namespace {
 
-// what distinguishes the two caches: dtype, row width and the 16-byte stride rule in the dtype's elements
-struct CacheKind {
-  bool fp8;
-  at::ScalarType dtype;
-  const char* dtype_name;
-  int64_t row, align;
-};
-constexpr CacheKind kCacheBf16{false, at::kBFloat16, "bfloat16", 576, 8};
-constexpr CacheKind kCacheFp8{true, at::kByte, "uint8", hpc::kMlaFp8RowBytes, hpc::kMlaFp8Align};
+// the nope / v head of the prompt side and the absorb matmuls (kMlaPrefillDimNope, kMlaAbsorbNope of their routes); the latent
+// row's 512 / 64 / 576 are csrc/mla_cache.h's
+constexpr int64_t kNope = 128;
 
-// [num_blocks, block_size, row] of the kind's dtype, last dim contiguous, both strides multiples of `align`, 16-byte aligned
-void check_cache(const at::Tensor& c, const CacheKind& kind) {
-  TORCH_CHECK(c.scalar_type() == kind.dtype, "ckv_cache dtype must be ", kind.dtype_name);
-  TORCH_CHECK(c.dim() == 3 && c.size(2) == kind.row, "ckv_cache must be [num_blocks, block_size, ", kind.row, "]");
-  const int64_t page = c.size(1);
-  TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128, "block_size must be 16, 32, 64 or 128, got ", page);
-  TORCH_CHECK(c.stride(2) == 1, "ckv_cache must have a contiguous last dim");
-  TORCH_CHECK(c.stride(1) >= kind.row && c.stride(1) % kind.align == 0 && c.stride(0) % kind.align == 0 && c.stride(0) >= 0,
-              "ckv_cache token stride must be >= ", kind.row, " and, like the block stride, a multiple of ", kind.align,
-              kind.fp8 ? " bytes" : " elements", "; got ", c.stride(1), " and ", c.stride(0));
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, "ckv_cache must be 16-byte aligned");
+const char* dtype_name(at::ScalarType dtype) {
+  switch (dtype) {
+    case at::kBFloat16: return "bfloat16";
+    case at::kFloat: return "float32";
+    case at::kInt: return "int32";
+    case at::kByte: return "uint8";
+    default: return c10::toString(dtype);
+  }
 }
 
-std::tuple<at::Tensor, at::Tensor> decode_mla(const CacheKind& kind, const char* op, const at::Tensor& q,
-                                              const at::Tensor& ckv_cache, const at::Tensor& block_ids,
-                                              const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
-                                              bool new_kv_included, const c10::optional<at::Tensor>& output,
-                                              const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
+// the cache's kind (csrc/mla_cache.h) and the one thing only torch knows of it, the dtype.  The ops over a cache are templates
+// on kFp8: one body each, registered once per kind.
+struct CacheKind : hpc::MlaCacheKind {
+  at::ScalarType dtype;
+};
+template <bool kFp8>
+constexpr CacheKind kCache = kFp8 ? CacheKind{hpc::kMlaCacheFp8, at::kByte} : CacheKind{hpc::kMlaCacheBf16, at::kBFloat16};
+
+// [num_blocks, block_size, row] of the kind's dtype with a contiguous last dim here; the page size, the strides and the
+// alignment are mla_cache_check's, the rule of the launchers, in its words
+void check_cache(const at::Tensor& c, const CacheKind& kind) {
+  TORCH_CHECK(c.scalar_type() == kind.dtype, "ckv_cache dtype must be ", dtype_name(kind.dtype));
+  TORCH_CHECK(c.dim() == 3 && c.size(2) == kind.row, "ckv_cache must be [num_blocks, block_size, ", kind.row, "]");
+  TORCH_CHECK(c.stride(2) == 1, "ckv_cache must have a contiguous last dim");
+  const int64_t page = c.size(1), bs = c.stride(0), ts = c.stride(1);
+  const hpc::MlaCacheCheck r = hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(c.data_ptr()), page, bs, ts);
+  TORCH_CHECK(r.code == HPC_OK, r.why, "; got block_size ", page, ", token stride ", ts, " and block stride ", bs);
+}
+
+// A data tensor: on `like`'s device, of `dtype` and `shape` (an entry of -1: any size), its last dim contiguous.  rows16 adds
+// what the cache's writer and gather ask of their bf16 rows (kv_a, out_ckv, the gather's output [rows, 576]; q_pe, out_q_pe
+// [rows, H, 64]): every other stride a multiple of 8 elements and wide enough that rows (and heads) do not overlap, base 16-byte
+// aligned.  The other ops leave strides and alignment to their route (csrc/attention_prefill_mla_route.h,
+// csrc/mla_absorb_route.h), whose refusal comes back in its words.
+constexpr bool kRows16 = true;
+bool fits(const at::Tensor& t, at::IntArrayRef shape) {
+  bool ok = t.dim() == static_cast<int64_t>(shape.size());
+  for (int64_t d = 0; ok && d < t.dim(); ++d) ok = shape[d] < 0 || t.size(d) == shape[d];
+  return ok;
+}
+void check_data(const at::Tensor& t, const char* name, const at::Tensor& like, at::ScalarType dtype, at::IntArrayRef shape,
+                bool rows16 = false) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on the device of the op's first tensor");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype_name(dtype));
+  TORCH_CHECK(fits(t, shape), name, " must have shape ", shape, " (-1: any size), got ", t.sizes());
+  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
+  if (!rows16) return;
+  const int64_t width = shape.back();
+  for (int64_t d = 0; d + 1 < t.dim(); ++d)
+    TORCH_CHECK(t.stride(d) % 8 == 0 && (t.stride(d) >= width || t.size(d) <= 1), name, " stride ", d,
+                " must be a multiple of 8 elements and at least ", width, ", got ", t.stride(d));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+// An index or table tensor: on `like`'s device, of `dtype` and `shape` (an entry of -1: any size), contiguous
+void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, at::ScalarType dtype, at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on the device of the op's first tensor");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype_name(dtype));
+  TORCH_CHECK(fits(t, shape) && t.is_contiguous(), name, " must be a contiguous tensor of shape ", shape, " (-1: any size), got ",
+              t.sizes());
+}
+
+template <bool kFp8>
+std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
+                                                        const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
+                                                        bool new_kv_included, const c10::optional<at::Tensor>& output,
+                                                        const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
+  const char* op = kFp8 ? "attention_decode_mla_fp8" : "attention_decode_mla_bf16";
   cuda_contig(q, "q");
   cuda_contig(block_ids, "block_ids");
   cuda_contig(num_seq_kvcache, "num_seq_kvcache");
@@ -51,23 +97,22 @@ std::tuple<at::Tensor, at::Tensor> decode_mla(const CacheKind& kind, const char*
   TORCH_CHECK(ckv_cache.device() == q.device() && block_ids.device() == q.device() && num_seq_kvcache.device() == q.device(),
               "ckv_cache, block_ids and num_seq_kvcache must be on q's device");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
-  TORCH_CHECK(ckv_cache.scalar_type() == kind.dtype, "ckv_cache dtype must be ", kind.dtype_name);
   TORCH_CHECK(block_ids.scalar_type() == at::kInt, "block_ids dtype must be int32");
   TORCH_CHECK(num_seq_kvcache.scalar_type() == at::kInt, "num_seq_kvcache dtype must be int32");
   TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
   const int64_t sq = mtp + 1;
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 576, "q must be [num_batch * num_seq_q, num_head, 576]");
-  TORCH_CHECK(ckv_cache.dim() == 3 && ckv_cache.size(2) == kind.row, "ckv_cache must be [num_blocks, block_size, ", kind.row, "]");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [num_batch * num_seq_q, num_head, 576]");
   TORCH_CHECK(block_ids.dim() == 2, "block_ids must be [num_batch, max_blocks]");
   TORCH_CHECK(num_seq_kvcache.dim() == 1, "num_seq_kvcache must be [num_batch]");
-  const int64_t b = num_seq_kvcache.size(0), h = q.size(1), page = ckv_cache.size(1);
+  const int64_t b = num_seq_kvcache.size(0), h = q.size(1);
   TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
   TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
   TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
-  check_cache(ckv_cache, kind);
+  check_cache(ckv_cache, kCache<kFp8>);
+  const int64_t page = ckv_cache.size(1);
   TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
   TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
-  at::Tensor out = out_or_new(output, q, {b * sq, h, 512}, at::kBFloat16, "output", kOnInputDevice);
+  at::Tensor out = out_or_new(output, q, {b * sq, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
   const bool want_lse = return_lse || output_lse.has_value();
   at::Tensor lse = want_lse ? out_or_new(output_lse, q, {b * sq, h}, at::kFloat, "output_lse", kOnInputDevice)
                             : at::empty({0}, q.options().dtype(at::kFloat));
@@ -82,7 +127,7 @@ std::tuple<at::Tensor, at::Tensor> decode_mla(const CacheKind& kind, const char*
   TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
   at::Tensor ws;
   if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: an unwritten piece is never read
-  const int rc = (kind.fp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
+  const int rc = (kFp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
       ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache),
       static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(num_seq_kvcache.data_ptr()), i32(b), i32(sq), i32(h),
       i32(page), i32(block_ids.size(1)), ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale),
@@ -91,69 +136,28 @@ std::tuple<at::Tensor, at::Tensor> decode_mla(const CacheKind& kind, const char*
   return {out, lse};
 }
 
-std::tuple<at::Tensor, at::Tensor> attention_decode_mla_bf16(const at::Tensor& q, const at::Tensor& ckv_cache,
-                                                             const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
-                                                             double softmax_scale, int64_t mtp, bool new_kv_included,
-                                                             const c10::optional<at::Tensor>& output,
-                                                             const c10::optional<at::Tensor>& output_lse, bool return_lse,
-                                                             int64_t splits) {
-  return decode_mla(kCacheBf16, "attention_decode_mla_bf16", q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp,
-                    new_kv_included, output, output_lse, return_lse, splits);
-}
-
-std::tuple<at::Tensor, at::Tensor> attention_decode_mla_fp8(const at::Tensor& q, const at::Tensor& ckv_cache,
-                                                            const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
-                                                            double softmax_scale, int64_t mtp, bool new_kv_included,
-                                                            const c10::optional<at::Tensor>& output,
-                                                            const c10::optional<at::Tensor>& output_lse, bool return_lse,
-                                                            int64_t splits) {
-  return decode_mla(kCacheFp8, "attention_decode_mla_fp8", q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp,
-                    new_kv_included, output, output_lse, return_lse, splits);
-}
-
 // ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------
-// A bf16 tensor whose last dim (of `width`) is contiguous, every other stride a multiple of 8 elements and wide enough that
-// rows (and heads) do not overlap, base 16-byte aligned: kv_a, out_ckv [rows, 576]; q_pe, out_q_pe [rows, H, 64].
-void check_rows_bf16(const at::Tensor& t, const char* name, const at::Tensor& like, at::IntArrayRef shape) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on the device of the op's first tensor");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
-  TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
-  const int64_t width = shape.back();
-  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
-  for (int64_t d = 0; d + 1 < t.dim(); ++d)
-    TORCH_CHECK(t.stride(d) % 8 == 0 && (t.stride(d) >= width || t.size(d) <= 1), name, " stride ", d,
-                " must be a multiple of 8 elements and at least ", width, ", got ", t.stride(d));
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
-}
-
-void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, at::ScalarType dtype, int64_t dim) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on the device of the op's first tensor");
-  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype == at::kInt ? "int32" : "float32");
-  TORCH_CHECK(t.dim() == dim && t.is_contiguous(), name, " must be a contiguous ", dim, "-d tensor");
-}
-
 // Returns out_q_pe (the caller's, or a fresh contiguous one); an empty tensor when q_pe is not given.  With out_q_pe (or no
 // q_pe) nothing is allocated and the call captures into a hipGraph.  Nothing here reads the values of num_seqlen_per_req,
 // q_index or block_ids.
-at::Tensor store_kv(const CacheKind& kind, const char* op, const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a,
-                    const at::Tensor& cos_sin, const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req,
-                    const at::Tensor& q_index, const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
-                    const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
-                    bool interleaved) {
+template <bool kFp8>
+at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
+                              const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index,
+                              const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
+                              const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
+                              bool interleaved) {
+  constexpr CacheKind kind = kCache<kFp8>;
   TORCH_CHECK(kv_a.is_cuda(), "kv_a tensor must be cuda");
-  TORCH_CHECK(kv_a.dim() == 2 && kv_a.size(1) == 576, "kv_a must be [rows, 576]");
+  TORCH_CHECK(kv_a.dim() == 2 && kv_a.size(1) == hpc::kMlaRow, "kv_a must be [rows, 576]");
   const int64_t rows = kv_a.size(0);
-  check_rows_bf16(kv_a, "kv_a", kv_a, {rows, 576});
-  check_table(cos_sin, "cos_sin", kv_a, at::kFloat, 2);
-  TORCH_CHECK(cos_sin.size(1) == 64 && cos_sin.size(0) > 0, "cos_sin must be [max_pos, 64] with max_pos > 0");
-  check_table(kv_norm_weight, "kv_norm_weight", kv_a, at::kFloat, 1);
-  TORCH_CHECK(kv_norm_weight.size(0) == 512, "kv_norm_weight must be [512]");
-  check_table(num_seqlen_per_req, "num_seqlen_per_req", kv_a, at::kInt, 1);
-  check_table(q_index, "q_index", kv_a, at::kInt, 1);
-  check_table(block_ids, "block_ids", kv_a, at::kInt, 2);
+  check_data(kv_a, "kv_a", kv_a, at::kBFloat16, {rows, hpc::kMlaRow}, kRows16);
+  check_table(cos_sin, "cos_sin", kv_a, at::kFloat, {-1, hpc::kMlaRope});
+  TORCH_CHECK(cos_sin.size(0) > 0, "cos_sin must be [max_pos, 64] with max_pos > 0");
+  check_table(kv_norm_weight, "kv_norm_weight", kv_a, at::kFloat, {hpc::kMlaLatent});
+  check_table(num_seqlen_per_req, "num_seqlen_per_req", kv_a, at::kInt, {-1});
   const int64_t num_req = num_seqlen_per_req.size(0);
-  TORCH_CHECK(q_index.size(0) == num_req + 1, "q_index must be [num_req + 1] = [", num_req + 1, "]");
-  TORCH_CHECK(block_ids.size(0) == num_req, "block_ids must have num_req = ", num_req, " rows");
+  check_table(q_index, "q_index", kv_a, at::kInt, {num_req + 1});
+  check_table(block_ids, "block_ids", kv_a, at::kInt, {num_req, -1});
   TORCH_CHECK(ckv_cache.has_value() || out_ckv.has_value(), "one of ckv_cache and out_ckv must be given");
   TORCH_CHECK(q_pe.has_value() || !out_q_pe.has_value(), "out_q_pe needs q_pe");
   TORCH_CHECK(cos_sin.size(0) <= INT32_MAX && rows <= INT32_MAX && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX,
@@ -167,134 +171,90 @@ at::Tensor store_kv(const CacheKind& kind, const char* op, const c10::optional<a
     page = c.size(1), block_stride = c.stride(0), token_stride = c.stride(1), num_blocks = c.size(0);
     TORCH_CHECK(num_blocks <= INT32_MAX, "sizes beyond int32");
   }
-  if (out_ckv.has_value()) check_rows_bf16(*out_ckv, "out_ckv", kv_a, {rows, 576});
+  if (out_ckv.has_value()) check_data(*out_ckv, "out_ckv", kv_a, at::kBFloat16, {rows, hpc::kMlaRow}, kRows16);
   int64_t h = 0;
   at::Tensor oq = at::empty({0}, kv_a.options());
   if (q_pe.has_value()) {
-    TORCH_CHECK(q_pe->dim() == 3 && q_pe->size(0) == rows && q_pe->size(2) == 64, "q_pe must be [rows, num_head, 64]");
+    TORCH_CHECK(q_pe->dim() == 3 && q_pe->size(0) == rows && q_pe->size(2) == hpc::kMlaRope, "q_pe must be [rows, num_head, 64]");
     h = q_pe->size(1);
     TORCH_CHECK(h >= 1 && h <= 128, "num_head must be 1 .. 128, got ", h);
-    check_rows_bf16(*q_pe, "q_pe", kv_a, {rows, h, 64});
+    check_data(*q_pe, "q_pe", kv_a, at::kBFloat16, {rows, h, hpc::kMlaRope}, kRows16);
     if (out_q_pe.has_value()) {
-      check_rows_bf16(*out_q_pe, "out_q_pe", kv_a, {rows, h, 64});
+      check_data(*out_q_pe, "out_q_pe", kv_a, at::kBFloat16, {rows, h, hpc::kMlaRope}, kRows16);
       oq = *out_q_pe;
-      TORCH_CHECK(rows <= 1 || oq.stride(0) >= (h - 1) * oq.stride(1) + 64, "out_q_pe stride 0 = ", oq.stride(0),
-                  " lets its rows overlap: num_head heads of stride ", oq.stride(1), " need ", (h - 1) * oq.stride(1) + 64);
+      const int64_t row_extent = (h - 1) * oq.stride(1) + hpc::kMlaRope;
+      TORCH_CHECK(rows <= 1 || oq.stride(0) >= row_extent, "out_q_pe stride 0 = ", oq.stride(0),
+                  " lets its rows overlap: num_head heads of stride ", oq.stride(1), " need ", row_extent);
       if (rows > 0) {  // q_pe and out_q_pe may share memory only as the same tensor (in place)
         const bool in_place = oq.data_ptr() == q_pe->data_ptr() && oq.strides() == q_pe->strides();
-        const auto lo = [](const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()); };
-        const auto hi = [&](const at::Tensor& t) { return lo(t) + 2 * ((rows - 1) * t.stride(0) + (h - 1) * t.stride(1) + 64); };
-        TORCH_CHECK(in_place || lo(oq) >= hi(*q_pe) || lo(*q_pe) >= hi(oq),
+        const auto span = [&](const at::Tensor& t) {
+          return hpc::byte_span(t.data_ptr(), rows, t.stride(0), h, t.stride(1), hpc::kMlaRope, 2);
+        };
+        TORCH_CHECK(in_place || !hpc::overlap(span(oq), span(*q_pe)),
                     "out_q_pe overlaps q_pe without being the same tensor: only the exact in-place form is supported");
       }
     } else {
-      oq = at::empty({rows, h, 64}, kv_a.options());
+      oq = at::empty({rows, h, hpc::kMlaRope}, kv_a.options());
     }
   }
   if (rows == 0 || num_req == 0) return oq;  // nothing to launch
   const bool with_q = q_pe.has_value();
-  const int rc = (kind.fp8 ? hpc_mla_rope_norm_store_kv_fp8_async : hpc_mla_rope_norm_store_kv_async)(
+  const int rc = (kFp8 ? hpc_mla_rope_norm_store_kv_fp8_async : hpc_mla_rope_norm_store_kv_async)(
       ptr(ckv_cache), ptr(out_ckv), with_q ? oq.data_ptr() : nullptr, ptr(kv_a), ptr(q_pe),
       static_cast<const float*>(cos_sin.data_ptr()), static_cast<const float*>(kv_norm_weight.data_ptr()),
       static_cast<const int*>(num_seqlen_per_req.data_ptr()), static_cast<const int*>(q_index.data_ptr()),
       static_cast<const int*>(block_ids.data_ptr()), i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)),
       i32(num_blocks), i32(cos_sin.size(0)), block_stride, token_stride, kv_a.stride(0),
-      out_ckv.has_value() ? out_ckv->stride(0) : 576, with_q ? q_pe->stride(0) : 0, with_q ? q_pe->stride(1) : 0,
+      out_ckv.has_value() ? out_ckv->stride(0) : hpc::kMlaRow, with_q ? q_pe->stride(0) : 0, with_q ? q_pe->stride(1) : 0,
       with_q ? oq.stride(0) : 0, with_q ? oq.stride(1) : 0, static_cast<float>(eps), interleaved ? 1 : 0, stream_of(kv_a));
-  HPC_LAUNCH_CHECK(rc, op);
+  HPC_LAUNCH_CHECK(rc, kFp8 ? "mla_rope_norm_store_kv_fp8" : "mla_rope_norm_store_kv");
   return oq;
-}
-
-at::Tensor rope_norm_store_kv(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
-                              const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index,
-                              const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
-                              const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv, double eps,
-                              bool interleaved) {
-  return store_kv(kCacheBf16, "mla_rope_norm_store_kv", ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
-                  block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
-}
-
-at::Tensor rope_norm_store_kv_fp8(const c10::optional<at::Tensor>& ckv_cache, const at::Tensor& kv_a, const at::Tensor& cos_sin,
-                                  const at::Tensor& kv_norm_weight, const at::Tensor& num_seqlen_per_req,
-                                  const at::Tensor& q_index, const at::Tensor& block_ids, const c10::optional<at::Tensor>& q_pe,
-                                  const c10::optional<at::Tensor>& out_q_pe, const c10::optional<at::Tensor>& out_ckv,
-                                  double eps, bool interleaved) {
-  return store_kv(kCacheFp8, "mla_rope_norm_store_kv_fp8", ckv_cache, kv_a, cos_sin, kv_norm_weight, num_seqlen_per_req, q_index,
-                  block_ids, q_pe, out_q_pe, out_ckv, eps, interleaved);
 }
 
 // ---- gather_ckv: the reader of that cache for the prompt side (csrc/mla_gather.hip), pinned to tests/mla_gather_ref.py ------------
 // Returns `output` (the caller's) or a fresh contiguous [num_rows, 576]; with `output` nothing is allocated and the call captures
 // into a hipGraph.  Nothing here reads the values of block_ids, cu_seqlens or seq_starts: the row count is the host's.
-at::Tensor gather(const CacheKind& kind, const char* op, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
-                  const at::Tensor& cu_seqlens, const c10::optional<at::Tensor>& seq_starts,
-                  const c10::optional<at::Tensor>& output, c10::optional<int64_t> num_rows) {
+template <bool kFp8>
+at::Tensor gather_ckv(const at::Tensor& ckv_cache, const at::Tensor& block_ids, const at::Tensor& cu_seqlens,
+                      const c10::optional<at::Tensor>& seq_starts, const c10::optional<at::Tensor>& output,
+                      c10::optional<int64_t> num_rows) {
   TORCH_CHECK(ckv_cache.is_cuda(), "ckv_cache tensor must be cuda");
-  check_cache(ckv_cache, kind);
-  check_table(block_ids, "block_ids", ckv_cache, at::kInt, 2);
-  check_table(cu_seqlens, "cu_seqlens", ckv_cache, at::kInt, 1);
+  check_cache(ckv_cache, kCache<kFp8>);
+  check_table(cu_seqlens, "cu_seqlens", ckv_cache, at::kInt, {-1});
   TORCH_CHECK(cu_seqlens.size(0) >= 1, "cu_seqlens must be [num_req + 1]");
   const int64_t num_req = cu_seqlens.size(0) - 1;
-  TORCH_CHECK(block_ids.size(0) == num_req, "block_ids must have num_req = ", num_req, " rows");
-  if (seq_starts.has_value()) {
-    check_table(*seq_starts, "seq_starts", ckv_cache, at::kInt, 1);
-    TORCH_CHECK(seq_starts->size(0) == num_req, "seq_starts must be [num_req] = [", num_req, "]");
-  }
+  check_table(block_ids, "block_ids", ckv_cache, at::kInt, {num_req, -1});
+  if (seq_starts.has_value()) check_table(*seq_starts, "seq_starts", ckv_cache, at::kInt, {num_req});
   TORCH_CHECK(output.has_value() || num_rows.has_value(), "one of output and num_rows must be given: the row count is a host value");
   at::Tensor out;
   if (output.has_value()) {
-    TORCH_CHECK(output->dim() == 2 && output->size(1) == 576, "output must be [num_rows, 576]");
+    TORCH_CHECK(output->dim() == 2 && output->size(1) == hpc::kMlaRow, "output must be [num_rows, 576]");
     TORCH_CHECK(!num_rows.has_value() || *num_rows == output->size(0), "num_rows = ", num_rows.value_or(0), " but output has ",
                 output->size(0), " rows");
-    check_rows_bf16(*output, "output", ckv_cache, {output->size(0), 576});
+    check_data(*output, "output", ckv_cache, at::kBFloat16, {output->size(0), hpc::kMlaRow}, kRows16);
     out = *output;
   } else {
     TORCH_CHECK(*num_rows >= 0, "num_rows must not be negative, got ", *num_rows);
-    out = at::empty({*num_rows, 576}, ckv_cache.options().dtype(at::kBFloat16));
+    out = at::empty({*num_rows, hpc::kMlaRow}, ckv_cache.options().dtype(at::kBFloat16));
   }
   const int64_t rows = out.size(0);
   TORCH_CHECK(rows <= INT32_MAX - 32 && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX && ckv_cache.size(0) <= INT32_MAX,
               "sizes beyond int32");
   if (rows == 0 || num_req == 0) return out;  // nothing to launch
-  const int rc = (kind.fp8 ? hpc_mla_gather_ckv_fp8_async : hpc_mla_gather_ckv_async)(
+  const int rc = (kFp8 ? hpc_mla_gather_ckv_fp8_async : hpc_mla_gather_ckv_async)(
       ptr(out), ptr(ckv_cache), static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(cu_seqlens.data_ptr()),
       seq_starts.has_value() ? static_cast<const int*>(seq_starts->data_ptr()) : nullptr, i32(rows), i32(num_req),
       i32(ckv_cache.size(1)), i32(block_ids.size(1)), i32(ckv_cache.size(0)), ckv_cache.stride(0), ckv_cache.stride(1),
       out.stride(0), stream_of(ckv_cache));
-  HPC_LAUNCH_CHECK(rc, op);
+  HPC_LAUNCH_CHECK(rc, kFp8 ? "mla_gather_ckv_fp8" : "mla_gather_ckv");
   return out;
 }
 
-at::Tensor gather_ckv(const at::Tensor& ckv_cache, const at::Tensor& block_ids, const at::Tensor& cu_seqlens,
-                      const c10::optional<at::Tensor>& seq_starts, const c10::optional<at::Tensor>& output,
-                      c10::optional<int64_t> num_rows) {
-  return gather(kCacheBf16, "mla_gather_ckv", ckv_cache, block_ids, cu_seqlens, seq_starts, output, num_rows);
-}
-
-at::Tensor gather_ckv_fp8(const at::Tensor& ckv_cache, const at::Tensor& block_ids, const at::Tensor& cu_seqlens,
-                          const c10::optional<at::Tensor>& seq_starts, const c10::optional<at::Tensor>& output,
-                          c10::optional<int64_t> num_rows) {
-  return gather(kCacheFp8, "mla_gather_ckv_fp8", ckv_cache, block_ids, cu_seqlens, seq_starts, output, num_rows);
-}
-
 // ---- attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip), pinned to tests/mla_prefill_ref.py -------------------------
-// bf16 on `like`'s device, last dim `width` and contiguous; the stride rules (multiples of 8, wide enough, 16-byte base) are the
-// route's (csrc/attention_prefill_mla_route.h) and come back as its refusal
-void check_prefill_operand(const at::Tensor& t, const char* name, const at::Tensor& like, int64_t dim, int64_t width) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on q's device");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
-  TORCH_CHECK(t.dim() == dim && t.size(-1) == width, name, " must be ", dim, "-d with a last dim of ", width);
-  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
-}
-
-void check_cu_seqlens(const at::Tensor& t, const char* name, const at::Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on q's device");
-  TORCH_CHECK(t.scalar_type() == at::kInt, name, " dtype must be int32");
-  TORCH_CHECK(t.dim() == 1 && t.size(0) >= 1 && t.is_contiguous(), name, " must be a contiguous [num_batch + 1] tensor");
-}
-
-// Nothing here reads the values of cu_seqlens_q / cu_seqlens_k; with output (and output_lse where an lse is wanted) given nothing
-// is allocated and the call captures into a hipGraph.
+// The stride rules of q, k_nope, k_pe and v (multiples of 8, wide enough, 16-byte base) are the route's
+// (csrc/attention_prefill_mla_route.h) and come back as its refusal.  Nothing here reads the values of cu_seqlens_q /
+// cu_seqlens_k; with output (and output_lse where an lse is wanted) given nothing is allocated and the call captures into a
+// hipGraph.
 std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_bf16(const at::Tensor& q, const at::Tensor& k_nope, const at::Tensor& k_pe,
                                                               const at::Tensor& v, const at::Tensor& cu_seqlens_q,
                                                               int64_t max_seqlens_q, double softmax_scale,
@@ -303,24 +263,24 @@ std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_bf16(const at::Tensor& 
                                                               const c10::optional<at::Tensor>& output,
                                                               const c10::optional<at::Tensor>& output_lse, bool return_lse) {
   TORCH_CHECK(q.is_cuda(), "q tensor must be cuda");
-  check_prefill_operand(q, "q", q, 3, 192);
+  check_data(q, "q", q, at::kBFloat16, {-1, -1, kNope + hpc::kMlaRope});
   const int64_t tq = q.size(0), h = q.size(1), tk = k_nope.dim() > 0 ? k_nope.size(0) : 0;
-  check_prefill_operand(k_nope, "k_nope", q, 3, 128);
-  check_prefill_operand(v, "v", q, 3, 128);
-  check_prefill_operand(k_pe, "k_pe", q, 2, 64);
+  check_data(k_nope, "k_nope", q, at::kBFloat16, {-1, -1, kNope});
+  check_data(v, "v", q, at::kBFloat16, {-1, -1, kNope});
+  check_data(k_pe, "k_pe", q, at::kBFloat16, {-1, hpc::kMlaRope});
   TORCH_CHECK(k_nope.size(1) == h && v.size(1) == h, "k_nope and v must have q's ", h, " heads");
   TORCH_CHECK(v.size(0) == tk && k_pe.size(0) == tk, "k_nope, k_pe and v must have the same number of rows");
-  check_cu_seqlens(cu_seqlens_q, "cu_seqlens_q", q);
+  check_table(cu_seqlens_q, "cu_seqlens_q", q, at::kInt, {-1});
+  TORCH_CHECK(cu_seqlens_q.size(0) >= 1, "cu_seqlens_q must be [num_batch + 1]");
   if (cu_seqlens_k.has_value()) {
-    check_cu_seqlens(*cu_seqlens_k, "cu_seqlens_k", q);
-    TORCH_CHECK(cu_seqlens_k->size(0) == cu_seqlens_q.size(0), "cu_seqlens_k must have cu_seqlens_q's length");
+    check_table(*cu_seqlens_k, "cu_seqlens_k", q, at::kInt, {cu_seqlens_q.size(0)});
     TORCH_CHECK(max_seqlens_k.has_value(), "cu_seqlens_k needs max_seqlens_k");
   }
   TORCH_CHECK(max_seqlens_q >= 0 && max_seqlens_q <= INT32_MAX && tq <= INT32_MAX && tk <= INT32_MAX &&
                   (!max_seqlens_k.has_value() || (*max_seqlens_k >= 0 && *max_seqlens_k <= INT32_MAX)),
               "max_seqlens_q / max_seqlens_k must be non-negative int32 counts");
   const int64_t b = cu_seqlens_q.size(0) - 1;
-  at::Tensor out = out_or_new(output, q, {tq, h, 128}, at::kBFloat16, "output", kOnInputDevice);
+  at::Tensor out = out_or_new(output, q, {tq, h, kNope}, at::kBFloat16, "output", kOnInputDevice);
   const bool want_lse = return_lse || output_lse.has_value();
   at::Tensor lse = want_lse ? out_or_new(output_lse, q, {tq, h}, at::kFloat, "output_lse", kOnInputDevice)
                             : at::empty({0}, q.options().dtype(at::kFloat));
@@ -331,8 +291,9 @@ std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_bf16(const at::Tensor& 
       ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), no_keys ? ptr(q) : ptr(k_nope),
       no_keys ? ptr(q) : ptr(k_pe), no_keys ? ptr(q) : ptr(v), static_cast<const int*>(cu_seqlens_q.data_ptr()),
       cu_seqlens_k.has_value() ? static_cast<const int*>(cu_seqlens_k->data_ptr()) : nullptr, i32(b), i32(h), i32(max_seqlens_q),
-      max_seqlens_k.has_value() ? i32(*max_seqlens_k) : -1, q.stride(0), q.stride(1), no_keys ? 128 * h : k_nope.stride(0),
-      no_keys ? 128 : k_nope.stride(1), no_keys ? 64 : k_pe.stride(0), no_keys ? 128 * h : v.stride(0), no_keys ? 128 : v.stride(1),
+      max_seqlens_k.has_value() ? i32(*max_seqlens_k) : -1, q.stride(0), q.stride(1), no_keys ? kNope * h : k_nope.stride(0),
+      no_keys ? kNope : k_nope.stride(1), no_keys ? hpc::kMlaRope : k_pe.stride(0), no_keys ? kNope * h : v.stride(0),
+      no_keys ? kNope : v.stride(1),
       static_cast<float>(softmax_scale), causal ? 1 : 0, stream_of(q));
   HPC_LAUNCH_CHECK(rc, "attention_prefill_mla_bf16");
   return {out, lse};
@@ -345,27 +306,16 @@ std::tuple<at::Tensor, at::Tensor> merge_attn_states(const at::Tensor& out_a, co
   TORCH_CHECK(out_a.is_cuda(), "out_a tensor must be cuda");
   TORCH_CHECK(out_a.dim() == 3, "out_a must be [T, H, D]");
   const int64_t t = out_a.size(0), h = out_a.size(1), d = out_a.size(2);
-  const auto check_state = [&](const at::Tensor& x, const char* name) {
-    TORCH_CHECK(x.is_cuda() && x.device() == out_a.device(), name, " must be on out_a's device");
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16, name, " dtype must be bfloat16");
-    TORCH_CHECK(x.sizes() == out_a.sizes(), name, " must have out_a's shape ", out_a.sizes());
-    TORCH_CHECK(x.stride(2) == 1, name, " must have a contiguous last dim");
-  };
-  const auto check_lse = [&](const at::Tensor& x, const char* name) {
-    TORCH_CHECK(x.is_cuda() && x.device() == out_a.device(), name, " must be on out_a's device");
-    TORCH_CHECK(x.scalar_type() == at::kFloat, name, " dtype must be float32");
-    TORCH_CHECK(x.dim() == 2 && x.size(0) == t && x.size(1) == h && x.is_contiguous(), name, " must be a contiguous [T, H] tensor");
-  };
-  check_state(out_a, "out_a");
-  check_state(out_b, "out_b");
-  check_lse(lse_a, "lse_a");
-  check_lse(lse_b, "lse_b");
+  check_data(out_a, "out_a", out_a, at::kBFloat16, {t, h, d});
+  check_data(out_b, "out_b", out_a, at::kBFloat16, {t, h, d});
+  check_table(lse_a, "lse_a", out_a, at::kFloat, {t, h});
+  check_table(lse_b, "lse_b", out_a, at::kFloat, {t, h});
   TORCH_CHECK(d > 0 && d % 8 == 0 && d <= 512, "D must be a multiple of 8, 8 .. 512, got ", d);
   TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
   at::Tensor out = output.has_value() ? *output : at::empty({t, h, d}, out_a.options());
   at::Tensor lse = output_lse.has_value() ? *output_lse : at::empty({t, h}, lse_a.options());
-  if (output.has_value()) check_state(out, "output");
-  if (output_lse.has_value()) check_lse(lse, "output_lse");
+  if (output.has_value()) check_data(out, "output", out_a, at::kBFloat16, {t, h, d});
+  if (output_lse.has_value()) check_table(lse, "output_lse", out_a, at::kFloat, {t, h});
   if (t == 0 || h == 0) return {out, lse};
   const int rc = hpc_merge_attn_states_async(ptr(out), static_cast<float*>(lse.data_ptr()), ptr(out_a),
                                              static_cast<const float*>(lse_a.data_ptr()), ptr(out_b),
@@ -378,27 +328,19 @@ std::tuple<at::Tensor, at::Tensor> merge_attn_states(const at::Tensor& out_a, co
 // ---- absorb_q / unabsorb_o (csrc/mla_absorb.hip), pinned to tests/mla_absorb_ref.py --------------------------------------------
 // dtype, device, shape and the contiguous last dim here; strides, alignment, H and overlap are the route's
 // (csrc/mla_absorb_route.h) and come back in its words.  With the outputs given nothing is allocated and nothing is read on the host.
-void check_absorb_operand(const at::Tensor& t, const char* name, const at::Tensor& like, at::IntArrayRef shape,
-                          at::ScalarType dtype = at::kBFloat16) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be a cuda tensor on the first tensor's device");
-  TORCH_CHECK(t.scalar_type() == dtype, name, " dtype must be ", dtype);
-  TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", got ", t.sizes());
-  TORCH_CHECK(t.stride(-1) == 1, name, " must have a contiguous last dim");
-}
-
 at::Tensor absorb_q(const at::Tensor& q_nope, const at::Tensor& w_uk, const c10::optional<at::Tensor>& output) {
   TORCH_CHECK(q_nope.is_cuda(), "q_nope tensor must be cuda");
-  TORCH_CHECK(q_nope.dim() == 3 && q_nope.size(2) == 128, "q_nope must be [T, num_head, 128]");
+  TORCH_CHECK(q_nope.dim() == 3 && q_nope.size(2) == kNope, "q_nope must be [T, num_head, 128]");
   const int64_t t = q_nope.size(0), h = q_nope.size(1);
   TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
-  check_absorb_operand(q_nope, "q_nope", q_nope, {t, h, 128});
-  check_absorb_operand(w_uk, "w_uk", q_nope, {h, 128, 512});
+  check_data(q_nope, "q_nope", q_nope, at::kBFloat16, {t, h, kNope});
+  check_data(w_uk, "w_uk", q_nope, at::kBFloat16, {h, kNope, hpc::kMlaLatent});
   at::Tensor out;
   if (output.has_value()) {
-    check_absorb_operand(*output, "output", q_nope, {t, h, 512});
+    check_data(*output, "output", q_nope, at::kBFloat16, {t, h, hpc::kMlaLatent});
     out = *output;
   } else {
-    out = at::empty({t, h, 512}, q_nope.options());
+    out = at::empty({t, h, hpc::kMlaLatent}, q_nope.options());
   }
   const char* why = hpc_mla_absorb_q_refusal(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1),
                                              w_uk.stride(0), w_uk.stride(1), out.stride(0), out.stride(1));
@@ -414,31 +356,30 @@ at::Tensor absorb_q(const at::Tensor& q_nope, const at::Tensor& w_uk, const c10:
 std::tuple<at::Tensor, at::Tensor> unabsorb_o(const at::Tensor& o_lat, const at::Tensor& w_uv, const c10::optional<at::Tensor>& output,
                                               bool quant, const c10::optional<at::Tensor>& output_scale) {
   TORCH_CHECK(o_lat.is_cuda(), "o_lat tensor must be cuda");
-  TORCH_CHECK(o_lat.dim() == 3 && o_lat.size(2) == 512, "o_lat must be [T, num_head, 512]");
+  TORCH_CHECK(o_lat.dim() == 3 && o_lat.size(2) == hpc::kMlaLatent, "o_lat must be [T, num_head, 512]");
   const int64_t t = o_lat.size(0), h = o_lat.size(1);
   TORCH_CHECK(h <= INT32_MAX, "sizes beyond int32");
-  check_absorb_operand(o_lat, "o_lat", o_lat, {t, h, 512});
-  check_absorb_operand(w_uv, "w_uv", o_lat, {h, 128, 512});
+  check_data(o_lat, "o_lat", o_lat, at::kBFloat16, {t, h, hpc::kMlaLatent});
+  check_data(w_uv, "w_uv", o_lat, at::kBFloat16, {h, kNope, hpc::kMlaLatent});
   TORCH_CHECK(quant || !output_scale.has_value(), "output_scale needs quant=True");
   const at::ScalarType odt = quant ? kF8 : at::kBFloat16;
   at::Tensor out, scale = at::empty({0}, o_lat.options().dtype(at::kFloat));
   if (output.has_value()) {
-    check_absorb_operand(*output, "output", o_lat, {t, h * 128}, odt);
+    check_data(*output, "output", o_lat, odt, {t, h * kNope});
     out = *output;
   } else {
-    out = at::empty({t, h * 128}, o_lat.options().dtype(odt));
+    out = at::empty({t, h * kNope}, o_lat.options().dtype(odt));
   }
   if (quant) {
     if (output_scale.has_value()) {
-      check_absorb_operand(*output_scale, "output_scale", o_lat, {t, h}, at::kFloat);
-      TORCH_CHECK(output_scale->is_contiguous(), "output_scale must be contiguous");
+      check_table(*output_scale, "output_scale", o_lat, at::kFloat, {t, h});
       scale = *output_scale;
     } else {
       scale = at::empty({t, h}, o_lat.options().dtype(at::kFloat));
     }
   }
   // a [1, N] or [0, N] tensor carries any row stride: the route is told the contiguous one
-  const int64_t out_rs = t > 1 ? out.stride(0) : h * 128;
+  const int64_t out_rs = t > 1 ? out.stride(0) : h * kNope;
   float* sp = quant ? static_cast<float*>(scale.data_ptr()) : nullptr;
   const char* why = hpc_mla_unabsorb_o_refusal(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1),
                                                w_uv.stride(0), w_uv.stride(1), out_rs, quant ? 1 : 0);
@@ -483,14 +424,14 @@ TORCH_LIBRARY(hpc_mla, m) {
 }
 
 TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
-  m.impl("attention_decode_mla_bf16", &attention_decode_mla_bf16);
-  m.impl("rope_norm_store_kv", &rope_norm_store_kv);
-  m.impl("attention_decode_mla_fp8", &attention_decode_mla_fp8);
-  m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv_fp8);
+  m.impl("attention_decode_mla_bf16", &attention_decode_mla<false>);
+  m.impl("rope_norm_store_kv", &rope_norm_store_kv<false>);
+  m.impl("attention_decode_mla_fp8", &attention_decode_mla<true>);
+  m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv<true>);
   m.impl("attention_prefill_mla_bf16", &attention_prefill_mla_bf16);
   m.impl("merge_attn_states", &merge_attn_states);
-  m.impl("gather_ckv", &gather_ckv);
-  m.impl("gather_ckv_fp8", &gather_ckv_fp8);
+  m.impl("gather_ckv", &gather_ckv<false>);
+  m.impl("gather_ckv_fp8", &gather_ckv<true>);
   m.impl("absorb_q", &absorb_q);
   m.impl("unabsorb_o", &unabsorb_o);
 }

@@ -197,6 +197,10 @@ UNSUPPORTED, INVALID = -1, -2
     (dict(sq=-1), INVALID), (dict(H=-16), INVALID), (dict(max_blocks=-1), INVALID), (dict(out=0), INVALID),
     (dict(q=0), INVALID), (dict(ckv=0), INVALID), (dict(bid=0), INVALID), (dict(lens=0), INVALID),
     (dict(splits=2, ws=None), INVALID), (dict(splits=2, ws=4096 + 4, ws_bytes=1 << 30), UNSUPPORTED),
+    # the cache's rule (csrc/mla_cache.h), as the writer's and the gather's tables pin it: it holds for an empty batch too, and
+    # a negative block stride is an invalid argument that wins over whatever is merely unsupported
+    (dict(token_stride=-576), UNSUPPORTED), (dict(P=8), UNSUPPORTED), (dict(P=256), UNSUPPORTED), (dict(P=0), UNSUPPORTED),
+    (dict(B=0, P=48), UNSUPPORTED), (dict(H=8, block_stride=-64 * 576), INVALID), (dict(block_stride=-64 * 576), INVALID),
 ])
 def test_cabi_refuses_on_the_host(lib, kwargs, code):
     assert call(lib, **kwargs) == code

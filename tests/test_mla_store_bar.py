@@ -189,6 +189,10 @@ def _launch(**kw):
     (dict(num_req=-1), INVALID), (dict(H=-1), INVALID), (dict(max_blocks=-1), INVALID), (dict(num_blocks=-1), INVALID),
     (dict(max_pos=0), INVALID), (dict(bs=-64 * 576), INVALID),
     (dict(rows=0), 0), (dict(num_req=0), 0), (dict(cache=0, out_ckv=4096, bid=0, rows=0), 0), (dict(q_pe=0, out_q_pe=0, H=0, rows=0), 0),
+    # the cache's rule (csrc/mla_cache.h), as the readers' tables pin it: it holds for a call without rows too, a negative
+    # block stride is an invalid argument that wins over whatever is merely unsupported, and an absent cache has no page size
+    (dict(ts=-576), UNSUPPORTED), (dict(P=8), UNSUPPORTED), (dict(P=0), UNSUPPORTED), (dict(rows=0, P=48), UNSUPPORTED),
+    (dict(P=48, bs=-64 * 576), INVALID), (dict(rows=0, cache=0, out_ckv=4096, P=48), 0),
 ])
 def test_cabi_refuses_on_the_host(kwargs, code):
     assert _launch(**kwargs) == code

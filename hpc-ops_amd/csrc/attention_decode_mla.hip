@@ -34,7 +34,10 @@
 // fp32, ONE fp32 multiply by the group's scale, RNE pack) stored as two 16-byte quads at element column 16 (sub + 8 i).  The
 // LDS image is byte for byte what the bf16 form builds from the dequantised cache, and everything behind it is the same code:
 // the two ops agree bit for bit on such a pair of caches.  The row's dimensions and the host rule for a cache: mla_cache.h.
+#include <type_traits>
+
 #include "attention_decode_mla_route.h"
+#include "attention_decode_mla_sparse_route.h"
 #include "mla_fp8_format.h"
 #include "hpc_amd.h"
 #include "hpc_common.h"
@@ -66,6 +69,14 @@ struct Args {
   float scale_log2;  // softmax_scale * log2(e)
 };
 
+// The token-sparse form adds the lists: row b * num_seq_q + s of `indices` names the token positions q row (b, s) attends to
+struct SparseArgs : Args {
+  const int* indices;  // [num_batch * num_seq_q, topk]
+  int topk, plen, num_blocks;  // plen: list slots per piece, a multiple of kMlaKvTile (a host value, as topk is)
+};
+template <bool kSparse>
+using ArgsOf = std::conditional_t<kSparse, SparseArgs, Args>;
+
 // tokens of request b including the new ones, never beyond the page table's reach
 __device__ __forceinline__ int request_len(const Args& a, int b) {
   const int64_t cap = static_cast<int64_t>(a.max_blocks) << a.page_shift;
@@ -76,11 +87,21 @@ __device__ __forceinline__ int request_len(const Args& a, int b) {
 __device__ __forceinline__ int piece_len(int len, int splits) {
   return ((len + splits - 1) / splits + kMlaKvTile - 1) & ~(kMlaKvTile - 1);
 }
+// positions a list entry of q row (b, s) may name: [0, vis), vis = L_b - num_seq_q + s + 1 from the UNCLAMPED length, never
+// beyond the page table's reach (so idx < vis implies idx >> page_shift < max_blocks)
+__device__ __forceinline__ int sparse_vis(const SparseArgs& a, int b, int s) {
+  const int64_t cap = static_cast<int64_t>(a.max_blocks) << a.page_shift;
+  int64_t vis = static_cast<int64_t>(a.num_seq[b]) + (a.new_kv_included ? 0 : a.num_seq_q) - a.num_seq_q + s + 1;
+  vis = vis < 0 ? 0 : (vis > cap ? cap : vis);
+  return static_cast<int>(vis);
+}
 
 // one result quad: the final bf16 output (one piece) or the piece's unnormalised fp32 partial
+// kZeroRow (the sparse form): a row that saw no token (l == 0, every v 0) is written as zeros, not as 0 x inf
+template <bool kZeroRow>
 __device__ __forceinline__ void emit4(const Args& a, int piece, int64_t grow, int col, f32x4 v, float l) {
   if (a.splits == 1) {
-    const float inv = 1.0f / l;
+    const float inv = kZeroRow && !(l > 0.f) ? 0.f : 1.0f / l;
     *reinterpret_cast<u32x2*>(a.out + grow * kMlaLatent + col) =
         u32x2{pack_bf16x2(v[0] * inv, v[1] * inv), pack_bf16x2(v[2] * inv, v[3] * inv)};
   } else {
@@ -95,9 +116,17 @@ __device__ __forceinline__ void emit_ml(const Args& a, int piece, int64_t grow, 
   }
 }
 
-template <bool kNarrow, bool kFp8>
-__global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Args a) {
+// kSparse: the token loop runs over the slots [piece * plen, min(topk, (piece + 1) * plen)) of the q row's list instead of a
+// token range, and the workgroup's rows are the heads of ONE q row (b, s) - lists differ per s.  Thread (rr, sub) fetches the
+// rows named by slots rr and rr + 32 of a tile.  A slot is valid when 0 <= idx < vis(b, s) and its page id lies in
+// [0, num_blocks); an invalid slot (padding, a slot past topk) writes zeros into the image, is never loaded and is masked by
+// score through a byte per slot beside the image.  The list entries are loaded two tiles ahead and the page ids one tile
+// ahead, so neither the page lookup nor the row loads wait for a dependent load.  A tile without a valid slot issues no cache
+// load and is not computed.  Everything behind the image is the dense code.
+template <bool kNarrow, bool kFp8, bool kSparse>
+__global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const ArgsOf<kSparse> a) {
   __shared__ __attribute__((aligned(16))) uint8_t s_mem[kLds];
+  __shared__ __attribute__((aligned(16))) uint8_t s_valid[kSparse ? 2 * kMlaKvTile : 1];  // sparse: slot validity per image
   constexpr int kTB = kNarrow ? 1 : 4;  // 16-token blocks a wave takes of a tile
   constexpr int kKS = kNarrow ? 1 : 2;  // 32-token k-steps of the second product
 
@@ -106,21 +135,34 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   int id = blockIdx.x;
   const int piece = id % a.splits;
   id /= a.splits;
-  const int tile = id % a.row_tiles, b = id / a.row_tiles;
+  // unit: the request (dense) or the q row b * num_seq_q + s (sparse) whose a.rows rows this workgroup's tile is cut from
+  const int tile = id % a.row_tiles, unit = id / a.row_tiles;
+  const int b = kSparse ? unit / a.num_seq_q : unit;
 
-  const int len = request_len(a, b);
-  const int plen = piece_len(len, a.splits);
-  const int p0 = piece * plen;
-  if (p0 >= len) return;  // an empty piece writes nothing; the merge does not read it
-  const int p1 = p0 + plen < len ? p0 + plen : len;
+  int p0, p1, vis = 0;  // dense: the piece's tokens; sparse: the piece's list slots and the positions they may name
+  [[maybe_unused]] int len = 0;
+  if constexpr (kSparse) {
+    p0 = piece * a.plen;  // < topk: the host launches no piece past the list
+    p1 = p0 + a.plen < a.topk ? p0 + a.plen : a.topk;
+    vis = sparse_vis(a, b, unit - b * a.num_seq_q);
+  } else {
+    len = request_len(a, b);
+    const int plen = piece_len(len, a.splits);
+    p0 = piece * plen;
+    if (p0 >= len) return;  // an empty piece writes nothing; the merge does not read it
+    p1 = p0 + plen < len ? p0 + plen : len;
+  }
   const int n_tiles = (p1 - p0 + kMlaKvTile - 1) / kMlaKvTile;
 
   const int rb = kNarrow ? 0 : tile * kMlaRowTile + 16 * wv;  // first q row of this wave
   const bool active = rb < a.rows;                           // rows is a multiple of 16: all 16 rows exist or none
-  const int64_t grow = static_cast<int64_t>(b) * a.rows + rb + c16;
-  // causal limit of this lane's q row, cut at the piece's end
-  int lim = len - a.num_seq_q + (rb + c16) / a.num_head + 1;
-  lim = lim < p1 ? lim : p1;
+  const int64_t grow = static_cast<int64_t>(unit) * a.rows + rb + c16;
+  // causal limit of this lane's q row, cut at the piece's end (sparse: validity says it, slot by slot)
+  [[maybe_unused]] int lim = 0;
+  if constexpr (!kSparse) {
+    lim = len - a.num_seq_q + (rb + c16) / a.num_head + 1;
+    lim = lim < p1 ? lim : p1;
+  }
 
   bf16x8 qf[kKSteps];
   if (active) {
@@ -136,18 +178,47 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   u32x4 stg[2][kStage];
   // the page ids of the rows this thread loads next, looked up one tile ahead: the row loads do not wait for the page table
   int page[2];
+  // sparse: the positions of the rows this thread loads next (-1: nothing to load), the list entries one tile further, and
+  // whether the rows staged in stg are real
+  [[maybe_unused]] int pos[2] = {-1, -1}, nidx[2] = {-1, -1};
+  [[maybe_unused]] bool real[2] = {false, false};
+  [[maybe_unused]] const int* list = nullptr;
+  if constexpr (kSparse) list = a.indices + static_cast<int64_t>(unit) * a.topk;
+  auto load_idx = [&](int t0) {  // sparse only: slots at or past the piece's end read nothing and are invalid
+    if constexpr (kSparse) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const int slot = t0 + rr + 32 * p;
+        nidx[p] = slot < p1 ? list[slot] : -1;
+      }
+    }
+  };
   auto lookup = [&](int t0) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      const int tok = t0 + rr + 32 * p;
-      page[p] = tok < p1 ? pages[tok >> a.page_shift] : 0;
+      if constexpr (kSparse) {
+        const int i = nidx[p];  // of tile t0, loaded a tile ago
+        const bool ok = static_cast<unsigned>(i) < static_cast<unsigned>(vis);  // vis <= max_blocks << page_shift
+        pos[p] = ok ? i : -1;
+        page[p] = ok ? pages[i >> a.page_shift] : -1;  // checked against num_blocks where it is used, a tile later
+      } else {
+        const int tok = t0 + rr + 32 * p;
+        page[p] = tok < p1 ? pages[tok >> a.page_shift] : 0;
+      }
     }
+    load_idx(t0 + kMlaKvTile);
   };
   auto gather_issue = [&](int t0) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      const int tok = t0 + rr + 32 * p;
-      if (tok < p1) {
+      int tok = t0 + rr + 32 * p;
+      bool load = tok < p1;
+      if constexpr (kSparse) {
+        tok = pos[p];
+        load = tok >= 0 && static_cast<unsigned>(page[p]) < static_cast<unsigned>(a.num_blocks);
+        real[p] = load;
+      }
+      if (load) {
         const uint8_t* src = a.ckv + static_cast<int64_t>(page[p]) * a.block_stride_bytes +
                              static_cast<int64_t>(tok & ((1 << a.page_shift) - 1)) * a.token_stride_bytes + sub * 16;
         if constexpr (kFp8) {
@@ -183,6 +254,9 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
 #pragma unroll
         for (int i = 0; i < 9; ++i) *reinterpret_cast<u32x4*>(dst + i * 128) = stg[p][i];
       }
+      if constexpr (kSparse) {
+        if (sub == 0) s_valid[buf * kMlaKvTile + rr + 32 * p] = real[p] ? 1 : 0;
+      }
     }
   };
 
@@ -195,6 +269,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   const int tr_off = (4 * g + (c16 >> 2)) * kRowBytes + (c16 & 3) * 8;
   const int rd_off = c16 * kRowBytes + g * 16;
 
+  load_idx(p0);
   lookup(p0);
   gather_issue(p0);
   gather_commit(0);
@@ -205,7 +280,14 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
     const int cur = it & 1;
     const bool more = it + 1 < n_tiles;
     if (more) gather_issue(t0 + kMlaKvTile);
-    if (active) {
+    // sparse: a wave whose slots of this tile are all invalid (padding) has nothing to add - every score would be -inf, which
+    // leaves (m, l, O) as they are.  Wave-uniform, read from the validity bytes: all 64 (wide) or the wave's own 16 (narrow)
+    bool any_seen = true;
+    if constexpr (kSparse) {
+      const uint32_t* vb = reinterpret_cast<const uint32_t*>(s_valid) + cur * (kMlaKvTile / 4);
+      any_seen = __any((kNarrow ? vb[4 * wv + (lane & 3)] : vb[lane & 15]) != 0);
+    }
+    if (active && any_seen) {
       const uint8_t* img = s_mem + cur * kBufBytes;
       // ---- S^T = C Q^T ----
       f32x4 s[kTB];
@@ -224,10 +306,18 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
 #pragma unroll
       for (int t = 0; t < kTB; ++t) {
         const int tb = kNarrow ? wv : t;
+        [[maybe_unused]] uint32_t vw = 0;  // sparse: the validity bytes of this lane's four slots
+        if constexpr (kSparse) vw = *reinterpret_cast<const uint32_t*>(s_valid + cur * kMlaKvTile + 16 * tb + 4 * g);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int tok = t0 + 16 * tb + 4 * g + i;
-          s[t][i] = tok < lim ? s[t][i] * a.scale_log2 : -INFINITY;
+          bool seen;
+          if constexpr (kSparse) {
+            seen = (vw >> (8 * i)) & 1;
+          } else {
+            const int tok = t0 + 16 * tb + 4 * g + i;
+            seen = tok < lim;
+          }
+          s[t][i] = seen ? s[t][i] * a.scale_log2 : -INFINITY;
           mx = fmaxf(mx, s[t][i]);
         }
       }
@@ -286,7 +376,7 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
     if (!active) return;
     l = row4_sum(l);
 #pragma unroll
-    for (int cb = 0; cb < kColBlocks; ++cb) emit4(a, piece, grow, 16 * cb + 4 * g, acc[cb], l);
+    for (int cb = 0; cb < kColBlocks; ++cb) emit4<kSparse>(a, piece, grow, 16 * cb + 4 * g, acc[cb], l);
     if (g == 0) emit_ml(a, piece, grow, m, l);
   } else {
     // the four waves' states of the same 16 rows: scale to the common maximum, sum in wave order
@@ -320,8 +410,8 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
         lt += (mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - mr)) * lw;
         sum += *reinterpret_cast<const f32x4*>(s_f + (w * 16 + row) * kMlaLatent + col);
       }
-      const int64_t gr = static_cast<int64_t>(b) * a.rows + row;
-      emit4(a, piece, gr, col, sum, lt);
+      const int64_t gr = static_cast<int64_t>(unit) * a.rows + row;
+      emit4<kSparse>(a, piece, gr, col, sum, lt);
       if (col == 0) emit_ml(a, piece, gr, mr, lt);
     }
   }
@@ -329,13 +419,19 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
 
 // Sums the pieces of one output row in piece order.  Pieces at or past the request's end were never written and are not read;
 // a piece in which this row saw no token (its sum is 0) is skipped.
-__global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const Args a) {
+// kSparse: every launched piece wrote (the host launches none past the list), and a row whose pieces all saw no token is
+// written as zeros with lse = -inf.
+template <bool kSparse>
+__global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const ArgsOf<kSparse> a) {
   const int64_t grow = blockIdx.x;
-  const int b = static_cast<int>(grow / a.rows);
-  const int len = request_len(a, b);
-  if (len == 0) return;
-  const int plen = piece_len(len, a.splits);
-  const int np = (len + plen - 1) / plen;  // <= splits
+  int np = a.splits;
+  if constexpr (!kSparse) {
+    const int b = static_cast<int>(grow / a.rows);
+    const int len = request_len(a, b);
+    if (len == 0) return;
+    const int plen = piece_len(len, a.splits);
+    np = (len + plen - 1) / plen;  // <= splits
+  }
   const int col = threadIdx.x * 4;
   float mm = -INFINITY;
   for (int p = 0; p < np; ++p) {
@@ -352,7 +448,7 @@ __global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const A
       sum += *reinterpret_cast<const f32x4*>(a.ws_o + (p * a.total_rows + grow) * kMlaLatent + col) * f;
     }
   }
-  const float inv = 1.0f / lt;
+  const float inv = kSparse && !(lt > 0.f) ? 0.f : 1.0f / lt;
   *reinterpret_cast<u32x2*>(a.out + grow * kMlaLatent + col) =
       u32x2{pack_bf16x2(sum[0] * inv, sum[1] * inv), pack_bf16x2(sum[2] * inv, sum[3] * inv)};
   if (a.lse && threadIdx.x == 0) a.lse[grow] = (mm + __builtin_log2f(lt)) * kLn2;
@@ -434,12 +530,12 @@ int mla_decode_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const vo
   a.new_kv_included = new_kv_included ? 1 : 0;
   a.scale_log2 = softmax_scale * kLog2e;
   if (r.narrow)
-    attention_decode_mla_kernel<true, kFp8><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<true, kFp8, false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
   else
-    attention_decode_mla_kernel<false, kFp8><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<false, kFp8, false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   if (r.splits > 1) {
-    attention_decode_mla_merge_kernel<<<dim3(r.merge_grid), 128, 0, stream>>>(a);
+    attention_decode_mla_merge_kernel<false><<<dim3(r.merge_grid), 128, 0, stream>>>(a);
     HPC_CHECK_LAUNCH();
   }
   return HPC_OK;
@@ -467,4 +563,116 @@ extern "C" int hpc_attention_decode_mla_fp8_async(void* out_ptr, float* lse_ptr,
   return mla_decode_launch<true>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, num_batch, num_seq_q,
                                  num_head, block_size, max_blocks, ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale,
                                  new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+}
+
+// ---- the token-sparse form: each q row attends to the tokens its list names --------------------------------------------------
+// What a call of hpc_attention_decode_mla_sparse_{bf16,fp8}_async with this `splits_wanted` runs with and needs:
+// mla_sparse_route() (attention_decode_mla_sparse_route.h).  *splits is the EFFECTIVE piece count; grid (workgroups of the
+// attention launch) and narrow (1: the 16-head form) may be null.  num_cu <= 0: the current device's (256 without a device).
+extern "C" int hpc_attention_decode_mla_sparse_plan(int num_batch, int num_seq_q, int num_head, int topk, int splits_wanted,
+                                                    int num_cu, int* splits, int* max_splits, int64_t* workspace_bytes,
+                                                    int* grid, int* narrow) {
+  if (!splits || !max_splits || !workspace_bytes) return HPC_ERR_INVALID;
+  hpc::MlaSparseRoute r = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, splits_wanted, num_cu > 0 ? num_cu : 256);
+  if (r.code == HPC_OK && num_cu <= 0 && splits_wanted == 0 && num_batch > 0)
+    r = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, 0, mla_current_cu_count());
+  *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes;
+  if (grid) *grid = r.grid;
+  if (narrow) *narrow = r.narrow;
+  return r.code;
+}
+
+namespace {
+// Both sparse launchers: the dense launchers' checks in their order, with the list's beside them.
+template <bool kFp8>
+int mla_sparse_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr, const int* block_ids_ptr,
+                      const int* num_seq_kvcache_ptr, const int* indices_ptr, int num_batch, int num_seq_q, int num_head, int topk,
+                      int block_size, int max_blocks, int num_blocks, int64_t ckv_block_stride, int64_t ckv_token_stride,
+                      float softmax_scale, int new_kv_included, int splits, void* workspace_ptr, int64_t workspace_bytes,
+                      hipStream_t stream) {
+  using namespace hpc::mla;
+  constexpr hpc::MlaCacheKind kind = kFp8 ? hpc::kMlaCacheFp8 : hpc::kMlaCacheBf16;
+  if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr || !indices_ptr) return HPC_ERR_INVALID;
+  const hpc::MlaCacheCheck cache =
+      hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_ptr), block_size, ckv_block_stride, ckv_token_stride);
+  if (splits < 0 || max_blocks < 0 || num_blocks < 0 || cache.code == HPC_ERR_INVALID) return HPC_ERR_INVALID;
+  const hpc::MlaSparseRoute shape = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, splits > 0 ? splits : 1, 256);
+  if (shape.code != HPC_OK) return shape.code;
+  if (cache.code != HPC_OK) return cache.code;
+  if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(q_ptr) & 15) return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3) ||
+      (reinterpret_cast<uintptr_t>(indices_ptr) & 3))
+    return HPC_ERR_UNSUPPORTED;
+  if (num_batch == 0) return HPC_OK;
+  if (max_blocks == 0) return HPC_ERR_INVALID;
+  const hpc::MlaSparseRoute r =
+      splits > 0 ? shape : hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, 0, mla_current_cu_count());
+  if (r.code != HPC_OK) return r.code;
+  if (r.splits > 1) {
+    if (!workspace_ptr || workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(workspace_ptr) & 15) return HPC_ERR_UNSUPPORTED;
+  }
+  SparseArgs a;
+  a.q = static_cast<const uint8_t*>(q_ptr);
+  a.ckv = static_cast<const uint8_t*>(ckv_ptr);
+  a.block_ids = block_ids_ptr;
+  a.num_seq = num_seq_kvcache_ptr;
+  a.out = static_cast<uint16_t*>(out_ptr);
+  a.lse = lse_ptr;
+  a.ws_o = static_cast<float*>(workspace_ptr);
+  a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
+  a.block_stride_bytes = ckv_block_stride * kind.unit;
+  a.token_stride_bytes = ckv_token_stride * kind.unit;
+  a.total_rows = static_cast<int64_t>(num_batch) * num_seq_q * r.rows;
+  a.num_head = num_head;
+  a.num_seq_q = num_seq_q;
+  a.rows = r.rows;
+  a.row_tiles = r.head_tiles;
+  a.splits = r.splits;
+  a.page_shift = hpc::mla_page_shift(block_size);
+  a.max_blocks = max_blocks;
+  a.new_kv_included = new_kv_included ? 1 : 0;
+  a.scale_log2 = softmax_scale * kLog2e;
+  a.indices = indices_ptr;
+  a.topk = topk;
+  a.plen = r.plen;
+  a.num_blocks = num_blocks;
+  if (r.narrow)
+    attention_decode_mla_kernel<true, kFp8, true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+  else
+    attention_decode_mla_kernel<false, kFp8, true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+  HPC_CHECK_LAUNCH();
+  if (r.splits > 1) {
+    attention_decode_mla_merge_kernel<true><<<dim3(r.merge_grid), 128, 0, stream>>>(a);
+    HPC_CHECK_LAUNCH();
+  }
+  return HPC_OK;
+}
+}  // namespace
+
+extern "C" int hpc_attention_decode_mla_sparse_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                          const int* block_ids_ptr, const int* num_seq_kvcache_ptr,
+                                                          const int* indices_ptr, int num_batch, int num_seq_q, int num_head,
+                                                          int topk, int block_size, int max_blocks, int num_blocks,
+                                                          int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                                          int new_kv_included, int splits, void* workspace_ptr,
+                                                          int64_t workspace_bytes, hipStream_t stream) {
+  return mla_sparse_launch<false>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, num_batch,
+                                  num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride,
+                                  softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+}
+
+// the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
+extern "C" int hpc_attention_decode_mla_sparse_fp8_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                         const int* block_ids_ptr, const int* num_seq_kvcache_ptr,
+                                                         const int* indices_ptr, int num_batch, int num_seq_q, int num_head,
+                                                         int topk, int block_size, int max_blocks, int num_blocks,
+                                                         int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
+                                                         float softmax_scale, int new_kv_included, int splits,
+                                                         void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
+  return mla_sparse_launch<true>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, num_batch,
+                                 num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride_bytes,
+                                 ckv_token_stride_bytes, softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes,
+                                 stream);
 }

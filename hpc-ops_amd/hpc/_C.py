@@ -103,6 +103,9 @@ _sig("hpc_gemm_blockwise_fp8_async", I, P, P, P, P, P, I, I, I, L, I, P, L, P, P
 _sig("hpc_attention_decode_mla_plan", I, I, I, I, I, I, IP, IP, ctypes.POINTER(c_int64))
 _sig("hpc_attention_decode_mla_bf16_async", I, P, P, P, P, IP, IP, I, I, I, I, I, L, L, F, I, I, P, L, P)
 _sig("hpc_attention_decode_mla_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I, L, L, F, I, I, P, L, P)
+_sig("hpc_attention_decode_mla_sparse_plan", I, I, I, I, I, I, I, IP, IP, ctypes.POINTER(c_int64), IP, IP)
+_sig("hpc_attention_decode_mla_sparse_bf16_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, I, P, L, P)
+_sig("hpc_attention_decode_mla_sparse_fp8_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, I, P, L, P)
 _sig("hpc_mla_rope_norm_store_kv_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_mla_rope_norm_store_kv_fp8_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_attention_prefill_mla_bf16_async", I, P, P, P, P, P, P, IP, IP, I, I, I, I, L, L, L, L, L, L, L, F, I, P)

@@ -433,6 +433,101 @@ def attention_decode_mla_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, nu
 torch.library.register_fake("hpc_mla::attention_decode_mla_fp8")(_attention_decode_mla_bf16_fake)
 
 
+def _decode_mla_result(out, lse, output, output_lse, return_lse):
+    out = out if output is None else output
+    if not (return_lse or output_lse is not None):
+        return out
+    return out, (lse if output_lse is None else output_lse)
+
+
+def attention_decode_mla_sparse_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,
+                                     indices: Tensor, softmax_scale: float, mtp: int = 0, new_kv_included: bool = False, *,
+                                     output: Tensor = None, output_lse: Tensor = None, return_lse: bool = False,
+                                     splits: int = 0):
+    """Token-sparse MLA decode over the paged latent KV cache, bfloat16: every q row attends to the cache tokens its list
+    names, not to the whole context (the attention of a DeepSeek-V3.2 / DSA decode step, whose indexer picks topk = 2048
+    tokens per query token).  Returns out bf16 [B * Sq, H, 512], or (out, lse) with return_lse or output_lse - what
+    attention_decode_mla_bf16 returns.  The indexer is not part of this op: the indices are taken as given.
+
+    No reference counterpart; semantics = the PyTorch statement tests/mla_sparse_ref.py, in float64.  With Sq = mtp + 1,
+    L_b the tokens of request b including the Sq new ones (the new_kv_included convention of attention_decode_mla_bf16)
+    and vis(b, s) = L_b - Sq + s + 1, the list of row (b, s) is indices[b * Sq + s, :], shared by all H heads:
+
+        z_k = softmax_scale * sum_{d < 576} q[b * Sq + s, h, d] * c_b[idx_k, d]      over valid k
+        out[b * Sq + s, h, :] = bf16( sum_k softmax(z)_k * c_b[idx_k, :512] )
+        lse[b * Sq + s, h]    = log sum_k exp(z_k)                                   (float32, natural log)
+
+    indices          int32 [B * Sq, topk], contiguous, on q's device: LOGICAL token positions in the request - what an
+                     indexer's top-k yields.  The kernel translates pages through block_ids; no conversion kernel is
+                     needed.  topk = indices.shape[1] is a host value, 1 <= topk <= 65536, and need not be a multiple
+                     of 64.
+    valid entry      0 <= idx_k < vis(b, s), idx_k // P < max_blocks, and its page id in [0, num_blocks).  Every other
+                     entry contributes nothing and causes no memory access: -1 padding, any other negative, positions
+                     at or past vis (later new tokens included), positions beyond the page table, poisoned page ids.
+                     Every address is checked against a host value.
+    duplicates       a position listed twice counts twice: the sum runs over entries.
+    empty row        a row with no valid entry writes out = 0 and lse = -inf (the convention of
+                     attention_prefill_mla_bf16; hpc.merge_attn_states passes the other side through for it).
+
+    q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale (explicit), output and output_lse are those of
+    attention_decode_mla_bf16, with its limits: H % 16 == 0, 16 <= H <= 128; mtp 0..3; P in {16, 32, 64, 128}; B == 0
+    returns empty tensors without a launch.  Nothing on the host reads num_seq_kvcache, block_ids or indices: with
+    output (and output_lse) given nothing is allocated beyond the cached scratch and the call captures into a hipGraph,
+    which replayed after lengths, pages, cache and indices changed in place gives the new result.
+
+    splits cuts the LIST, not the context: piece p covers slots [p * plen, min(topk, (p + 1) * plen)) with
+    plen = ceil(topk / splits) rounded up to the kernel's tile of 64 slots, computed on the host.  Pieces that would
+    start at or past topk are not launched.  0 = the library chooses (one piece when B * Sq * ceil(H / 64) workgroups
+    fill the CUs, else about two workgroups per CU, never more pieces than the list has tiles); 1 .. max = the caller's
+    count, max = 64; beyond it the call is refused.  More than one piece goes through the cached scratch buffer that
+    attention_decode_mla_bf16 uses (hpc.release_decode_workspaces() drops it) and a merge launch that sums the pieces
+    in piece order, skipping a piece that saw no token.
+
+    Determinism: no float atomics; for given shapes, splits and CU count the result is bit-identical from call to call.
+    Behind the gather the kernel is attention_decode_mla_bf16's: with mtp = 0, splits = 1 and the list 0 .. L_b - 1
+    (then -1) the result is bit-identical to attention_decode_mla_bf16 at splits = 1."""
+    out, lse = torch.ops.hpc_mla.attention_decode_mla_sparse_bf16(q, ckv_cache, block_ids, num_seq_kvcache, indices,
+                                                                  float(softmax_scale), int(mtp), bool(new_kv_included),
+                                                                  output, output_lse, bool(return_lse), int(splits))
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
+
+
+@torch.library.register_fake("hpc_mla::attention_decode_mla_sparse_bf16")
+def _attention_decode_mla_sparse_fake(q, ckv_cache, block_ids, num_seq_kvcache, indices, softmax_scale, mtp, new_kv_included,
+                                      output=None, output_lse=None, return_lse=False, splits=0):
+    return _attention_decode_mla_bf16_fake(q, ckv_cache, block_ids, num_seq_kvcache, softmax_scale, mtp, new_kv_included,
+                                           output, output_lse, return_lse, splits)
+
+
+def attention_decode_mla_sparse_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,
+                                    indices: Tensor, softmax_scale: float, mtp: int = 0, new_kv_included: bool = False, *,
+                                    output: Tensor = None, output_lse: Tensor = None, return_lse: bool = False,
+                                    splits: int = 0):
+    """attention_decode_mla_sparse_bf16 over the FP8 latent KV cache of attention_decode_mla_fp8: a torch.uint8 tensor,
+    logical [num_blocks, P, 656] (512 e4m3 codes, four float32 scales, 64 bf16 RoPE columns per token) - the row
+    DeepSeek-V3.2's sparse attention reads.  Returns out bf16 [B * Sq, H, 512], or (out, lse) with return_lse or
+    output_lse.
+
+    Semantics = the statement of attention_decode_mla_sparse_bf16 (tests/mla_sparse_ref.py) applied to the dequantised
+    cache exactly as attention_decode_mla_fp8 does it: c[d] = bf16_rne( fp32(code[d]) * scale[d // 128] ).  indices
+    (int32 [B * Sq, topk] logical token positions, 1 <= topk <= 65536), the valid-entry rule (0 <= idx_k < vis(b, s),
+    inside the page table, page id in [0, num_blocks); -1 padding and every other invalid entry contribute nothing and
+    cause no memory access), the duplicate rule (a position listed twice counts twice), the empty row (out = 0,
+    lse = -inf), the limits (H % 16 == 0,
+    16 <= H <= 128; mtp 0..3; P in {16, 32, 64, 128}), the splits rule over the list (0 .. 64), the cached scratch that
+    hpc.release_decode_workspaces() drops and hipGraph capture with caller-provided outputs are all those of
+    attention_decode_mla_sparse_bf16; the cache's stride rule is attention_decode_mla_fp8's.  Only the gather differs:
+    for given shapes, splits and CU count the result is bit-identical to attention_decode_mla_sparse_bf16 on the
+    dequantised cache, and bit-identical from call to call."""
+    out, lse = torch.ops.hpc_mla.attention_decode_mla_sparse_fp8(q, ckv_cache, block_ids, num_seq_kvcache, indices,
+                                                                 float(softmax_scale), int(mtp), bool(new_kv_included),
+                                                                 output, output_lse, bool(return_lse), int(splits))
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
+
+
+torch.library.register_fake("hpc_mla::attention_decode_mla_sparse_fp8")(_attention_decode_mla_sparse_fake)
+
+
 def attention_prefill_mla_bf16(q: Tensor, k_nope: Tensor, k_pe: Tensor, v: Tensor, cu_seqlens_q: Tensor, max_seqlens_q: int,
                                softmax_scale: float, *, cu_seqlens_k: Tensor = None, max_seqlens_k: int = None,
                                causal: bool = True, output: Tensor = None, output_lse: Tensor = None,

@@ -506,6 +506,40 @@ int hpc_attention_decode_mla_fp8_async(void* out, float* lse, const void* q, con
                                        float softmax_scale, int new_kv_included, int splits, void* workspace,
                                        int64_t workspace_bytes, hpc_stream_t stream);
 
+/* ---- Token-sparse MLA decode attention: each q row attends to the tokens its list names (csrc/attention_decode_mla.hip) ------
+ * The attention of a DeepSeek-V3.2 (DSA) decode step; the statement is tests/mla_sparse_ref.py.  indices int32
+ * [num_batch * num_seq_q, topk] contiguous ON THE DEVICE: row b * num_seq_q + s lists LOGICAL token positions of request b (what
+ * an indexer's top-k yields; the kernel translates pages through block_ids), shared by all heads of that q row.  With
+ * vis(b, s) = L_b - num_seq_q + s + 1, entry k is valid when 0 <= idx_k < vis(b, s), idx_k / block_size < max_blocks and its
+ * page id lies in [0, num_blocks); every other entry (-1 padding, any negative, a position at or past vis or beyond the table, a
+ * poisoned page id) contributes nothing and causes no memory access - every address is checked against a host value.
+ *   z_k = softmax_scale * sum_{d < 576} q[b * num_seq_q + s, h, d] * c_b[idx_k, d]        over valid k
+ *   out[b * num_seq_q + s, h, :] = bf16( sum_k softmax(z)_k * c_b[idx_k, :512] )         lse = log sum_k exp(z_k)
+ * A position listed twice counts twice; a row without a valid entry gets out = 0 and lse = -inf.  The FP8 call applies the same
+ * to the dequantised cache, as hpc_attention_decode_mla_fp8_async does, and agrees with the bf16 call on it bit for bit.
+ * 1 <= topk <= 65536, any value; num_blocks = pages in the cache's pool; every other argument, limit and refusal is the dense
+ * call's, in its order, plus HPC_ERR_INVALID for null indices, topk <= 0 and num_blocks < 0 and HPC_ERR_UNSUPPORTED for
+ * topk > 65536.  splits cuts the LIST: piece p covers slots [p * plen, min(topk, (p + 1) * plen)), plen = ceil(topk / splits)
+ * rounded up to 64, a host value; pieces that would start at or past topk are not launched, and
+ * hpc_attention_decode_mla_sparse_plan reports the effective count in *splits, the workspace bytes that go with it and, where
+ * asked (grid and narrow may be NULL), the attention launch's workgroups and whether it takes the 16-head form.  The
+ * merge sums the pieces in piece order, skipping a piece that saw no token - no float atomics, bit-identical from call to call.
+ * Nothing on the host reads num_seq_kvcache, block_ids or indices. */
+int hpc_attention_decode_mla_sparse_plan(int num_batch, int num_seq_q, int num_head, int topk, int splits_wanted, int num_cu,
+                                         int* splits, int* max_splits, int64_t* workspace_bytes, int* grid, int* narrow);
+int hpc_attention_decode_mla_sparse_bf16_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                               const int* num_seq_kvcache, const int* indices, int num_batch, int num_seq_q,
+                                               int num_head, int topk, int block_size, int max_blocks, int num_blocks,
+                                               int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                               int new_kv_included, int splits, void* workspace, int64_t workspace_bytes,
+                                               hpc_stream_t stream);
+int hpc_attention_decode_mla_sparse_fp8_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                              const int* num_seq_kvcache, const int* indices, int num_batch, int num_seq_q,
+                                              int num_head, int topk, int block_size, int max_blocks, int num_blocks,
+                                              int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
+                                              float softmax_scale, int new_kv_included, int splits, void* workspace,
+                                              int64_t workspace_bytes, hpc_stream_t stream);
+
 /* ---- MLA latent-cache write: kv_a RMSNorm + RoPE + paged store, bf16 (csrc/mla_store.hip) ------------------------------------
  * No reference kernel exists; the semantics are the PyTorch statement tests/mla_store_ref.py.  The producer of the cache and of
  * the RoPE columns of q that hpc_attention_decode_mla_bf16_async reads.  Row r of kv_a is one new token; its request b is the

@@ -1,0 +1,595 @@
+// The DSA lightning indexer of a DeepSeek-V3.2 decode step - gfx950: the writer of the paged FP8 index-key cache, the FP8 MQA
+// logits over it and the top-k that turns them into the `indices` of hpc_attention_decode_mla_sparse_*_async.
+//
+// Ours only (no reference kernel).  Semantics = the float64 PyTorch statement tests/mla_indexer_ref.py; the cache's layout, the
+// host rule for a cache and the one route (grid, chunking, scratch, refusals in words) are mla_indexer_route.h's.
+//
+// MI355X design.
+//   store    a stream: 16 lanes own one row of 128 bf16 (one 16-byte load each), the row's abs-max is four xor steps inside the
+//            16 lanes, the codes are the project's 128-column quantiser (act_quant.h: bit for bit hpc_blockwise_fp8_quant_async
+//            on the row) and leave as one 8-byte store per lane, the scale as one 4-byte store per row.  The request and position
+//            of a row are mla_store.hip's: binary search in q_index, one page-table entry, every index checked against a host
+//            value before it is used.
+//   logits   a 132 B/token stream with one v_mfma_f32_16x16x128_f8f6f4 per 16 heads x 16 tokens: A = q (heads on the rows), B =
+//            keys straight from global memory (tokens on the columns, 32 contiguous bytes per lane, no LDS).  Lane (n, g) of the
+//            result holds heads 4 g .. 4 g + 3 of token n, so ReLU, the weight and the sum over a lane's heads stay in the lane -
+//            in a fixed order - and two xor steps (16, 32) finish the head sum: no atomics, the same bits on every call.  A wave
+//            takes 64 tokens per step, four 16-token blocks each inside one page (pages are >= 16 tokens), whose page ids are
+//            wave-uniform scalar loads issued one step ahead; lane (n, g) then stores block g's token n: 256 contiguous bytes per
+//            wave and q row.  q and the weights of all num_seq_q rows of the request stay in registers, so a key tile is read
+//            once for all of them.  A workgroup owns a host-sized chunk of one request's context and leaves at once when the
+//            chunk starts at or past the request's end; columns at or past a row's visible length are never written.
+//   top-k    one workgroup of 1024 threads per q row.  A row that sees no more than topk tokens writes 0 .. n - 1 and -1 without
+//            reading a logit.  Otherwise a radix select over the 32-bit torch_topk_key (ordered_key.h) in four passes of 8 bits
+//            with an LDS histogram (integer atomics: the counts do not depend on their order) finds the threshold key and how
+//            many of its ties are taken; a last pass compacts in POSITION order by wave ballots and prefix counts - keys above
+//            the threshold and the first `need` ties - so the list ascends and ties go to the smaller position.
+#include "act_quant.h"
+#include "hpc_common.h"
+#include "mla_indexer_route.h"
+#include "ordered_key.h"
+#include "../../include/hpc_amd.h"
+
+namespace hpc {
+namespace mla_indexer {
+
+// ---- store ------------------------------------------------------------------------------------------------------------------------
+struct StoreArgs {
+  const uint16_t* k;     // [rows, 128] bf16, row stride k_rs elements
+  uint8_t* cache;        // page p at cache + p * cache_bs bytes
+  const int* seqlen;     // [num_req] total length incl. the new tokens
+  const int* q_index;    // [num_req + 1]
+  const int* block_ids;  // [num_req, max_blocks]
+  long k_rs, cache_bs;
+  int num_rows, num_req, page_shift, max_blocks, num_blocks;
+};
+
+constexpr int kStoreThreads = 256, kStoreLanes = 16, kStoreRows = kStoreThreads / kStoreLanes;
+
+__global__ __launch_bounds__(kStoreThreads) void store_kernel(const StoreArgs a) {
+  const int sub = threadIdx.x & (kStoreLanes - 1);
+  const int row = blockIdx.x * kStoreRows + (threadIdx.x >> 4);  // the host keeps num_rows + kStoreRows within int32
+  const bool in = row < a.num_rows;
+  u32x4 raw = u32x4{0u, 0u, 0u, 0u};
+  if (in) raw = ld16(a.k + row * a.k_rs + 8 * sub);  // in flight before the lookup
+
+  // request and position of this row, as mla_store.hip: last b with q_index[b] <= row.  Nothing is stored for a row of no
+  // request, a token whose page the table does not hold, or whose page id is not a page.
+  bool store = false;
+  long cell = 0, scale_at = 0;
+  if (in) {
+    bool live = row < a.q_index[a.num_req];
+    int lo = 0, hi = a.num_req;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (a.q_index[mid + 1] <= row) lo = mid + 1; else hi = mid;
+    }
+    const int req = lo < a.num_req ? lo : a.num_req - 1;  // a q_index that does not ascend must not index past seqlen
+    const long pos = static_cast<long>(a.seqlen[req]) - (static_cast<long>(a.q_index[req + 1]) - row);
+    live = live && pos >= 0;
+    const long blk = pos >> a.page_shift;
+    if (live && blk < a.max_blocks) {
+      const int phys = a.block_ids[static_cast<long>(req) * a.max_blocks + blk];
+      store = phys >= 0 && phys < a.num_blocks;  // frameworks pad tables with -1
+      const long t = pos & ((1L << a.page_shift) - 1);
+      cell = phys * a.cache_bs + t * kIdxDim;
+      scale_at = phys * a.cache_bs + (static_cast<long>(kIdxDim) << a.page_shift) + 4 * t;
+    }
+  }
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = bf16lo_to_f32(raw[i]);
+    v[2 * i + 1] = bf16hi_to_f32(raw[i]);
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+  for (int d = 1; d < kStoreLanes; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));  // every lane takes part
+  const float scale = e4m3_block_scale(amax), inv = e4m3_block_inv(scale);
+  if (!store) return;
+  *reinterpret_cast<u32x2*>(a.cache + cell + 8 * sub) =
+      u32x2{quant_4xe4m3(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv), quant_4xe4m3(v[4] * inv, v[5] * inv, v[6] * inv, v[7] * inv)};
+  if (sub == 0) *reinterpret_cast<float*>(a.cache + scale_at) = scale;
+}
+
+// ---- logits -----------------------------------------------------------------------------------------------------------------------
+struct LogitsArgs {
+  const uint8_t* q;      // [B * Sq, Hi, 128] e4m3 codes, contiguous
+  const float* w;        // [B * Sq, Hi]
+  const uint8_t* cache;  // page p at cache + p * cache_bs bytes
+  const int* block_ids;  // [B, max_blocks]
+  const int* lens;       // [B]
+  float* out;            // row r at out + r * out_rs floats
+  long cache_bs, out_rs;
+  int page_shift, max_blocks, num_blocks, cols, chunk, chunks, nki;
+};
+
+constexpr int kLogitsThreads = 64 * kIdxWaves;
+constexpr int kSub = kIdxTile / 16;  // 16-token blocks of a wave's step
+static_assert(kSub == 4, "lane group g stores block g");
+
+__device__ __forceinline__ int clamp_len(long v, int cols) { return static_cast<int>(v < 0 ? 0 : (v > cols ? cols : v)); }
+
+template <int kHB, int kSq>
+__global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs a) {
+  constexpr int kHi = 16 * kHB;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int n = lane & 15, g = lane >> 4;
+  const int b = blockIdx.x / a.chunks, piece = blockIdx.x % a.chunks;  // b < num_batch: the grid is num_batch * chunks
+
+  // L_b and the rows' visible lengths, clamped to the table: device values never reach an address unchecked
+  const long len = static_cast<long>(as_const(a.lens)[b]) + (a.nki ? 0 : kSq);
+  int vis[kSq];
+#pragma unroll
+  for (int s = 0; s < kSq; ++s) vis[s] = clamp_len(len - kSq + s + 1, a.cols);
+  const int lim = vis[kSq - 1];  // the longest of them
+  const int c0 = piece * a.chunk;
+  if (c0 >= lim) return;
+  const int c1 = min(c0 + a.chunk, lim);
+
+  // q and the weights of the request's rows: lane (n, g) holds bytes 32 g .. 32 g + 31 of head 16 hb + n (the A operand) and the
+  // weights of heads 16 hb + 4 g .. + 3 (the rows of the result it holds)
+  i32x8 qf[kSq][kHB];
+  f32x4 wt[kSq][kHB];
+#pragma unroll
+  for (int s = 0; s < kSq; ++s) {
+    const long r = static_cast<long>(b) * kSq + s;
+#pragma unroll
+    for (int hb = 0; hb < kHB; ++hb) {
+      const uint8_t* p = a.q + (r * kHi + 16 * hb + n) * kIdxDim + 32 * g;
+      const u32x4 x = ld16(p), y = ld16(p + 16);
+      qf[s][hb] = i32x8{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3]),
+                        static_cast<int>(y[0]), static_cast<int>(y[1]), static_cast<int>(y[2]), static_cast<int>(y[3])};
+      wt[s][hb] = *reinterpret_cast<const f32x4*>(a.w + r * kHi + 16 * hb + 4 * g);
+    }
+  }
+
+  const cint_ptr table = as_const(a.block_ids) + static_cast<long>(b) * a.max_blocks;
+  // page ids of the four blocks of the step at t0 (wave-uniform); -1 for a block at or past c1.  (t0 + 16 u) >> shift <
+  // max_blocks because t0 + 16 u < c1 <= cols = max_blocks << shift.
+  const auto lookup = [&](int t0, int (&phys)[kSub]) {
+#pragma unroll
+    for (int u = 0; u < kSub; ++u) {
+      const int j0 = t0 + 16 * u;
+      phys[u] = j0 < c1 ? table[j0 >> a.page_shift] : -1;
+    }
+  };
+  const int mask = (1 << a.page_shift) - 1;
+  const long scales_at = static_cast<long>(kIdxDim) << a.page_shift;
+
+  int phys[kSub] = {-1, -1, -1, -1}, next[kSub] = {-1, -1, -1, -1};
+  int t0 = c0 + wave * kIdxTile;
+  if (t0 < c1) lookup(t0, phys);
+  for (; t0 < c1; t0 += kIdxTile * kIdxWaves) {
+    const int t1 = t0 + kIdxTile * kIdxWaves;
+    if (t1 < c1) lookup(t1, next);  // a step ahead of its keys
+
+    i32x8 kv[kSub];
+    float sc[kSub];
+    bool ok[kSub];
+#pragma unroll
+    for (int u = 0; u < kSub; ++u) {
+      ok[u] = phys[u] >= 0 && phys[u] < a.num_blocks;  // a block at or past c1, -1 padding, a poisoned id: its page is never loaded
+      kv[u] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
+      sc[u] = 0.f;
+      if (ok[u]) {
+        const uint8_t* page = a.cache + phys[u] * a.cache_bs;
+        const int t = (t0 + 16 * u + n) & mask;
+        const u32x4 x = ld16(page + t * kIdxDim + 32 * g), y = ld16(page + t * kIdxDim + 32 * g + 16);
+        kv[u] = i32x8{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3]),
+                      static_cast<int>(y[0]), static_cast<int>(y[1]), static_cast<int>(y[2]), static_cast<int>(y[3])};
+        sc[u] = *reinterpret_cast<const float*>(page + scales_at + 4 * t);
+      }
+    }
+    const int j = t0 + 16 * g + n;  // the column this lane stores
+#pragma unroll
+    for (int s = 0; s < kSq; ++s) {
+      float val[kSub];
+#pragma unroll
+      for (int u = 0; u < kSub; ++u) {
+        float acc = 0.f;
+#pragma unroll
+        for (int hb = 0; hb < kHB; ++hb) {
+          const f32x4 d =
+              __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(qf[s][hb], kv[u], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc = fmaf(wt[s][hb][i], fmaxf(d[i], 0.f), acc);
+        }
+        acc += __shfl_xor(acc, 16, 64);
+        acc += __shfl_xor(acc, 32, 64);
+        val[u] = ok[u] ? sc[u] * acc : -__builtin_inff();
+      }
+      const float mine = g == 0 ? val[0] : g == 1 ? val[1] : g == 2 ? val[2] : val[3];
+      if (j < vis[s]) a.out[(static_cast<long>(b) * kSq + s) * a.out_rs + j] = mine;
+    }
+#pragma unroll
+    for (int u = 0; u < kSub; ++u) phys[u] = next[u];
+  }
+}
+
+// ---- top-k ------------------------------------------------------------------------------------------------------------------------
+struct TopkArgs {
+  const float* logits;  // row r at logits + r * rs floats
+  const int* lens;      // [B]
+  int* out;             // [B * Sq, topk]
+  long rs;
+  int sq, cols, topk, nki;
+};
+
+constexpr int kTopkThreads = 1024, kTopkWaves = kTopkThreads / 64, kTopkBatch = 4;
+
+__global__ __launch_bounds__(kTopkThreads) void topk_kernel(const TopkArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t found[2];  // the prefix with the pass's digit behind it, and what is still needed inside it
+  __shared__ uint32_t wave_gt[kTopkWaves], wave_tie[kTopkWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x, b = r / a.sq, s = r % a.sq;
+  const long len = static_cast<long>(a.lens[b]) + (a.nki ? 0 : a.sq);
+  const int n = clamp_len(len - a.sq + s + 1, a.cols);
+  int* o = a.out + static_cast<long>(r) * a.topk;
+  if (n <= a.topk) {  // the identity list: no logit is read
+    for (int i = tid; i < a.topk; i += kTopkThreads) o[i] = i < n ? i : -1;
+    return;
+  }
+  const float* x = a.logits + r * a.rs;
+
+  // radix select: after pass p `prefix` holds the top 8 (p + 1) bits of the threshold key and `need` how many keys with that
+  // prefix are still to be taken (every key with a larger prefix is taken)
+  uint32_t prefix = 0, need = static_cast<uint32_t>(a.topk);
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    // kTopkBatch loads in flight per thread before the first is counted: a long row is one workgroup's stream from L2.
+    // (Measured: adding a wave's population of a bin at once - ballots on the first uncounted lane's bin, four rounds, the rest
+    // lane by lane - made the 64k row 1.8 x SLOWER than one LDS atomic per lane, 215 against 122 us; not kept.)
+    for (int i0 = tid; i0 < n; i0 += kTopkBatch * kTopkThreads) {
+      float v[kTopkBatch];
+#pragma unroll
+      for (int u = 0; u < kTopkBatch; ++u) {
+        const int i = i0 + u * kTopkThreads;  // n <= 2^30: no overflow
+        v[u] = i < n ? x[i] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kTopkBatch; ++u) {
+        const uint32_t key = torch_topk_key(v[u]);
+        if (i0 + u * kTopkThreads < n && (pass == 0 || (key >> (shift + 8)) == prefix)) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      // lane l owns digits 255 - 4 l .. 252 - 4 l: ascending lanes descend the digits
+      uint32_t c[4], sum = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        c[k] = hist[255 - 4 * lane - k];
+        sum += c[k];
+      }
+      uint32_t incl = sum;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+      }
+      uint32_t run = incl - sum;  // keys with a larger digit
+      if (run < need && need <= incl) {  // exactly one lane: the histogram holds at least `need` keys
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (run < need && need <= run + c[k]) {
+            found[0] = (prefix << 8) | static_cast<uint32_t>(255 - 4 * lane - k);
+            found[1] = need - run;
+          }
+          run += c[k];
+        }
+      }
+    }
+    __syncthreads();
+    prefix = found[0];
+    need = found[1];
+  }
+  const uint32_t thr = prefix;  // the threshold key; `need` of its ties are taken, the first in position order
+
+  // compaction in position order: entry = (keys above the threshold before i) + min(ties before i, need)
+  uint32_t gt_base = 0, tie_base = 0;
+  for (int base = 0; base < n; base += kTopkThreads) {
+    const int i = base + tid;
+    const uint32_t key = i < n ? torch_topk_key(x[i]) : 0u;  // 0 is below the key of every float
+    const bool gt = key > thr, tie = i < n && key == thr;
+    const uint64_t mg = __ballot(gt), mt = __ballot(tie);
+    const uint64_t below = (uint64_t{1} << lane) - 1;
+    if (lane == 0) {
+      wave_gt[wave] = __popcll(mg);
+      wave_tie[wave] = __popcll(mt);
+    }
+    __syncthreads();
+    uint32_t gb = gt_base + __popcll(mg & below), tb = tie_base + __popcll(mt & below), tot_g = 0, tot_t = 0;
+#pragma unroll
+    for (int w = 0; w < kTopkWaves; ++w) {
+      const uint32_t cg = wave_gt[w], ct = wave_tie[w];
+      if (w < wave) {
+        gb += cg;
+        tb += ct;
+      }
+      tot_g += cg;
+      tot_t += ct;
+    }
+    const uint32_t at = gb + (tb < need ? tb : need);  // < topk: keys above + need = topk
+    if ((gt || (tie && tb < need)) && at < static_cast<uint32_t>(a.topk)) o[at] = i;
+    gt_base += tot_g;
+    tie_base += tot_t;
+    __syncthreads();  // the counts are rewritten by the next step
+  }
+}
+
+}  // namespace mla_indexer
+}  // namespace hpc
+
+namespace {
+using hpc::MlaIndexerCheck;
+
+int current_cu_count() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
+}
+bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+constexpr int64_t kSpan = int64_t{1} << 60;  // bytes: page id x block stride stays below 2^61
+
+// ---- the host rules, one function per call: the refusal code and its reason in words, no device call ------------------------------
+MlaIndexerCheck store_check(const void* k_cache, const void* k, const int* num_seqlen_per_req, const int* q_index,
+                            const int* block_ids, int num_rows, int num_req, int block_size, int max_blocks, int num_blocks,
+                            int64_t block_stride, int64_t k_row_stride) {
+  using namespace hpc;
+  if (num_rows < 0 || num_req < 0 || max_blocks < 0 || num_blocks < 0)
+    return {HPC_ERR_INVALID, "num_rows, num_req, max_blocks and num_blocks must not be negative"};
+  const bool work = num_rows > 0 && num_req > 0;
+  if (work && (!k_cache || !k || !num_seqlen_per_req || !q_index || !block_ids))
+    return {HPC_ERR_INVALID, "k_cache, k, num_seqlen_per_req, q_index and block_ids must not be null"};
+  const MlaIndexerCheck cache = mla_indexer_cache_check(reinterpret_cast<uintptr_t>(k_cache), block_size, block_stride);
+  if (cache.code != HPC_OK) return cache;
+  if (misaligned(k, 16)) return {HPC_ERR_UNSUPPORTED, "k must be 16-byte aligned"};
+  if (k_row_stride < 0 || k_row_stride % 8 != 0 || (num_rows > 1 && k_row_stride < kIdxDim))
+    return {HPC_ERR_UNSUPPORTED, "k row stride must be a multiple of 8 elements and at least 128"};
+  if (num_rows > INT32_MAX - mla_indexer::kStoreRows || num_req == INT32_MAX) return {HPC_ERR_UNSUPPORTED, "sizes beyond int32"};
+  if (k_row_stride > kSpan / 2 / INT32_MAX || (num_blocks > 0 && block_stride > kSpan / num_blocks))
+    return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+
+MlaIndexerCheck logits_check(const float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
+                             const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size,
+                             int max_blocks, int num_blocks, int64_t block_stride, int64_t logits_row_stride) {
+  using namespace hpc;
+  const MlaIndexerRoute r = mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, 0, true, 256);
+  if (r.code != HPC_OK) return {r.code, r.why};
+  if (num_blocks < 0) return {HPC_ERR_INVALID, "num_blocks must not be negative"};
+  const MlaIndexerCheck cache = mla_indexer_cache_check(reinterpret_cast<uintptr_t>(k_cache), block_size, block_stride);
+  if (cache.code != HPC_OK) return cache;
+  if (num_batch > 0 && (!logits || !q || !weights || !k_cache || !block_ids || !num_seq_kvcache))
+    return {HPC_ERR_INVALID, "logits, q, weights, k_cache, block_ids and num_seq_kvcache must not be null"};
+  if (num_batch > 0 && max_blocks == 0) return {HPC_ERR_INVALID, "block_ids has no columns"};
+  if (misaligned(q, 16) || misaligned(weights, 16) || misaligned(logits, 4))
+    return {HPC_ERR_UNSUPPORTED, "q and weights must be 16-byte aligned, logits 4-byte"};
+  if (logits_row_stride < r.cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least max_blocks * block_size"};
+  if (logits_row_stride > kSpan / 4 / INT32_MAX || (num_blocks > 0 && block_stride > kSpan / num_blocks))
+    return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+
+MlaIndexerCheck topk_check(const int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                           int64_t num_cols, int topk, int64_t logits_row_stride) {
+  using namespace hpc;
+  if (num_batch < 0) return {HPC_ERR_INVALID, "num_batch must not be negative"};
+  if (num_seq_q <= 0) return {HPC_ERR_INVALID, "num_seq_q must be positive"};
+  if (num_cols < 0) return {HPC_ERR_INVALID, "the logits' column count must not be negative"};
+  if (num_seq_q > kIdxMaxSeqQ) return {HPC_ERR_UNSUPPORTED, "mtp must be 0 .. 3"};
+  if (topk < 1 || topk > kIdxMaxTopk) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
+  if (num_cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "logits reach beyond 2^30 columns"};
+  if (static_cast<int64_t>(num_batch) * num_seq_q > INT32_MAX) return {HPC_ERR_UNSUPPORTED, "num_batch * num_seq_q beyond int32"};
+  // a row that sees no more than topk tokens reads no logit, so a call over zero columns needs no logits at all
+  if (num_batch > 0 && (!indices || !num_seq_kvcache || (!logits && num_cols > 0)))
+    return {HPC_ERR_INVALID, "indices, logits and num_seq_kvcache must not be null"};
+  if (misaligned(indices, 4) || misaligned(logits, 4)) return {HPC_ERR_UNSUPPORTED, "indices and logits must be 4-byte aligned"};
+  if (logits_row_stride < num_cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least the column count"};
+  if (logits_row_stride > kSpan / 4 / INT32_MAX) return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+
+MlaIndexerCheck fused_check(const int* indices, const void* q, const float* weights, const void* k_cache, const int* block_ids,
+                            const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
+                            int num_blocks, int64_t block_stride, int topk, const void* workspace, int64_t workspace_bytes) {
+  using namespace hpc;
+  const MlaIndexerRoute r = mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, false, 256);
+  if (r.code != HPC_OK) return {r.code, r.why};
+  // the scratch stands in for the logits; without work neither is looked at
+  const float* ws = num_batch > 0 ? static_cast<const float*>(workspace) : nullptr;
+  if (num_batch > 0 && (!workspace || workspace_bytes < r.scratch.bytes))
+    return {HPC_ERR_INVALID, "the workspace is missing or smaller than hpc_mla_indexer_plan's workspace_bytes"};
+  const MlaIndexerCheck a = logits_check(ws, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
+                                         block_size, max_blocks, num_blocks, block_stride, r.scratch.row_stride);
+  if (a.code != HPC_OK) return a;
+  return topk_check(indices, ws, num_seq_kvcache, num_batch, num_seq_q, r.cols, topk, r.scratch.row_stride);
+}
+
+// ---- the launches behind the checks -----------------------------------------------------------------------------------------------
+template <int kHB>
+void launch_logits_sq(const hpc::mla_indexer::LogitsArgs& a, int num_seq_q, int grid, hipStream_t stream) {
+  using namespace hpc::mla_indexer;
+  switch (num_seq_q) {
+    case 1: logits_kernel<kHB, 1><<<grid, kLogitsThreads, 0, stream>>>(a); break;
+    case 2: logits_kernel<kHB, 2><<<grid, kLogitsThreads, 0, stream>>>(a); break;
+    case 3: logits_kernel<kHB, 3><<<grid, kLogitsThreads, 0, stream>>>(a); break;
+    default: logits_kernel<kHB, 4><<<grid, kLogitsThreads, 0, stream>>>(a); break;
+  }
+}
+
+int launch_logits(float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
+                  const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
+                  int num_blocks, int64_t block_stride, int64_t logits_row_stride, int new_kv_included, hipStream_t stream) {
+  using namespace hpc;
+  const MlaIndexerRoute r =
+      mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, 0, true, current_cu_count());
+  if (r.code != HPC_OK) return r.code;
+  mla_indexer::LogitsArgs a{};
+  a.q = static_cast<const uint8_t*>(q);
+  a.w = weights;
+  a.cache = static_cast<const uint8_t*>(k_cache);
+  a.block_ids = block_ids;
+  a.lens = num_seq_kvcache;
+  a.out = logits;
+  a.cache_bs = block_stride;
+  a.out_rs = logits_row_stride;
+  a.page_shift = mla_page_shift(block_size);
+  a.max_blocks = max_blocks;
+  a.num_blocks = num_blocks;
+  a.cols = static_cast<int>(r.cols);
+  a.chunk = r.chunk;
+  a.chunks = r.chunks;
+  a.nki = new_kv_included ? 1 : 0;
+  switch (r.head_blocks) {
+    case 1: launch_logits_sq<1>(a, num_seq_q, r.grid, stream); break;
+    case 2: launch_logits_sq<2>(a, num_seq_q, r.grid, stream); break;
+    default: launch_logits_sq<4>(a, num_seq_q, r.grid, stream); break;
+  }
+  HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+
+int launch_topk(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q, int64_t num_cols,
+                int topk, int64_t logits_row_stride, int new_kv_included, hipStream_t stream) {
+  using namespace hpc::mla_indexer;
+  TopkArgs a{};
+  a.logits = logits;
+  a.lens = num_seq_kvcache;
+  a.out = indices;
+  a.rs = logits_row_stride;
+  a.sq = num_seq_q;
+  a.cols = static_cast<int>(num_cols);
+  a.topk = topk;
+  a.nki = new_kv_included ? 1 : 0;
+  topk_kernel<<<num_batch * num_seq_q, kTopkThreads, 0, stream>>>(a);
+  HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+}  // namespace
+
+// ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
+extern "C" int hpc_mla_indexer_plan(int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks, int topk, int num_cu,
+                                    int* grid, int* chunk, int* topk_grid, int64_t* logits_row_stride, int64_t* workspace_bytes) {
+  if (!grid || !chunk || !topk_grid || !logits_row_stride || !workspace_bytes) return HPC_ERR_INVALID;
+  const bool logits_only = topk == 0;
+  hpc::MlaIndexerRoute r = hpc::mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, logits_only,
+                                                  num_cu > 0 ? num_cu : 256);
+  if (r.code == HPC_OK && num_cu <= 0 && num_batch > 0)
+    r = hpc::mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, logits_only, current_cu_count());
+  *grid = r.grid, *chunk = r.chunk, *topk_grid = r.topk_grid;
+  *logits_row_stride = r.scratch.row_stride, *workspace_bytes = r.scratch.bytes;
+  return r.code;
+}
+
+extern "C" const char* hpc_mla_indexer_store_k_fp8_refusal(const void* k_cache, const void* k, const int* num_seqlen_per_req,
+                                                           const int* q_index, const int* block_ids, int num_rows, int num_req,
+                                                           int block_size, int max_blocks, int num_blocks,
+                                                           int64_t k_cache_block_stride_bytes, int64_t k_row_stride) {
+  return store_check(k_cache, k, num_seqlen_per_req, q_index, block_ids, num_rows, num_req, block_size, max_blocks, num_blocks,
+                     k_cache_block_stride_bytes, k_row_stride)
+      .why;
+}
+
+extern "C" int hpc_mla_indexer_store_k_fp8_async(void* k_cache, const void* k, const int* num_seqlen_per_req, const int* q_index,
+                                                 const int* block_ids, int num_rows, int num_req, int block_size, int max_blocks,
+                                                 int num_blocks, int64_t k_cache_block_stride_bytes, int64_t k_row_stride,
+                                                 hipStream_t stream) {
+  using namespace hpc;
+  using namespace hpc::mla_indexer;
+  const MlaIndexerCheck c = store_check(k_cache, k, num_seqlen_per_req, q_index, block_ids, num_rows, num_req, block_size,
+                                        max_blocks, num_blocks, k_cache_block_stride_bytes, k_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (num_rows == 0 || num_req == 0) return HPC_OK;  // nothing to launch
+  StoreArgs a{};
+  a.k = static_cast<const uint16_t*>(k);
+  a.cache = static_cast<uint8_t*>(k_cache);
+  a.seqlen = num_seqlen_per_req;
+  a.q_index = q_index;
+  a.block_ids = block_ids;
+  a.k_rs = k_row_stride;
+  a.cache_bs = k_cache_block_stride_bytes;
+  a.num_rows = num_rows;
+  a.num_req = num_req;
+  a.page_shift = mla_page_shift(block_size);
+  a.max_blocks = max_blocks;
+  a.num_blocks = num_blocks;
+  store_kernel<<<(num_rows + kStoreRows - 1) / kStoreRows, kStoreThreads, 0, stream>>>(a);
+  HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+
+extern "C" const char* hpc_mla_indexer_logits_fp8_refusal(const float* logits, const void* q, const float* weights,
+                                                          const void* k_cache, const int* block_ids, const int* num_seq_kvcache,
+                                                          int num_batch, int num_seq_q, int num_head, int block_size,
+                                                          int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes,
+                                                          int64_t logits_row_stride) {
+  return logits_check(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
+                      max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride)
+      .why;
+}
+
+extern "C" int hpc_mla_indexer_logits_fp8_async(float* logits, const void* q, const float* weights, const void* k_cache,
+                                                const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                                                int num_head, int block_size, int max_blocks, int num_blocks,
+                                                int64_t k_cache_block_stride_bytes, int64_t logits_row_stride,
+                                                int new_kv_included, hipStream_t stream) {
+  const MlaIndexerCheck c = logits_check(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
+                                         block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (num_batch == 0) return HPC_OK;  // nothing to launch
+  return launch_logits(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
+                       max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride, new_kv_included, stream);
+}
+
+extern "C" const char* hpc_mla_indexer_topk_refusal(const int* indices, const float* logits, const int* num_seq_kvcache,
+                                                    int num_batch, int num_seq_q, int64_t num_cols, int topk,
+                                                    int64_t logits_row_stride) {
+  return topk_check(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride).why;
+}
+
+extern "C" int hpc_mla_indexer_topk_async(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch,
+                                          int num_seq_q, int64_t num_cols, int topk, int64_t logits_row_stride, int new_kv_included,
+                                          hipStream_t stream) {
+  const MlaIndexerCheck c = topk_check(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (num_batch == 0) return HPC_OK;  // nothing to launch
+  return launch_topk(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride, new_kv_included,
+                     stream);
+}
+
+extern "C" const char* hpc_mla_indexer_topk_fp8_refusal(const int* indices, const void* q, const float* weights,
+                                                        const void* k_cache, const int* block_ids, const int* num_seq_kvcache,
+                                                        int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
+                                                        int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
+                                                        const void* workspace, int64_t workspace_bytes) {
+  return fused_check(indices, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
+                     max_blocks, num_blocks, k_cache_block_stride_bytes, topk, workspace, workspace_bytes)
+      .why;
+}
+
+extern "C" int hpc_mla_indexer_topk_fp8_async(int* indices, const void* q, const float* weights, const void* k_cache,
+                                              const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                                              int num_head, int block_size, int max_blocks, int num_blocks,
+                                              int64_t k_cache_block_stride_bytes, int topk, int new_kv_included, void* workspace,
+                                              int64_t workspace_bytes, hipStream_t stream) {
+  const MlaIndexerCheck c = fused_check(indices, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
+                                        block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, topk, workspace,
+                                        workspace_bytes);
+  if (c.code != HPC_OK) return c.code;
+  if (num_batch == 0) return HPC_OK;  // nothing to launch
+  const hpc::MlaIndexerScratch ws =
+      hpc::mla_indexer_scratch(static_cast<int64_t>(num_batch) * num_seq_q, static_cast<int64_t>(max_blocks) * block_size);
+  float* logits = static_cast<float*>(workspace);
+  const int rc = launch_logits(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
+                               max_blocks, num_blocks, k_cache_block_stride_bytes, ws.row_stride, new_kv_included, stream);
+  if (rc != HPC_OK) return rc;
+  return launch_topk(indices, logits, num_seq_kvcache, num_batch, num_seq_q, ws.row_stride, topk, ws.row_stride, new_kv_included,
+                     stream);
+}

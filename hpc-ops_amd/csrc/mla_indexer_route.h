@@ -1,0 +1,106 @@
+// The DSA lightning indexer (mla_indexer.hip), stated once: the paged index-key cache, the host rule for a cache a launcher
+// accepts, and the one route of the logits / top-k ops - the grid, the chunking of the context, the scratch of the fused call and
+// every refusal with its reason in words.  Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip,
+// hpc_mla_indexer_plan and the torch shim (torch_mla_indexer.cpp) all read it.
+//
+// The index-key cache.  Every token of every request has ONE index key of 128 columns, shared by all index heads: 128
+// float8_e4m3fn codes and one float32 scale, column d = fp32(code[d]) * scale, for any finite non-negative scale.  The cache is
+// a uint8 tensor, logically [num_blocks, P * 132], addressed through the block_ids page table of the latent cache.  Within a page
+// the codes of its P tokens come first, [P, 128] at byte 0 (token t at byte 128 t), and the P float32 scales follow at byte
+// 128 P (token t at byte 128 P + 4 t): every 16-byte access of a key is aligned without padding a row to 144 bytes.
+// P in {16, 32, 64, 128}; block stride >= 132 P bytes and a multiple of 16; base 16-byte aligned.
+#pragma once
+#include <stdint.h>
+
+#include "hpc_status.h"
+#include "mla_cache.h"
+
+namespace hpc {
+
+constexpr int kIdxDim = 128;                      // columns of an index key, and of a q head
+constexpr int kIdxTokenBytes = kIdxDim + 4;       // 132: codes + scale, what a token costs a page
+constexpr int kIdxMaxTopk = 65536;                // list entries per q row at most, as the sparse attention takes
+constexpr int kIdxMaxSeqQ = 4;                    // mtp + 1 at most
+constexpr int kIdxTile = 64;                      // tokens a wave takes per step: four 16 x 16 blocks
+constexpr int kIdxWaves = 4;                      // waves of a logits workgroup
+constexpr int kIdxMinChunk = kIdxTile * kIdxWaves * 2;  // 512 tokens: the shortest piece of a context a workgroup owns
+constexpr int kIdxMaxChunk = 8192;
+constexpr int64_t kIdxMaxCols = int64_t{1} << 30;  // max_blocks * P at most, as the MLA decode ops
+
+constexpr int64_t mla_indexer_scales_at(int64_t block_size) { return block_size * kIdxDim; }
+constexpr int64_t mla_indexer_page_bytes(int64_t block_size) { return block_size * kIdxTokenBytes; }
+
+struct MlaIndexerCheck {
+  int code;         // HPC_OK or the refusal
+  const char* why;  // the refusal in words (null when accepted)
+};
+
+// The one host check of an index-key cache, for a call with or without work.  `base` is never dereferenced; null passes
+// (whether a cache may be absent is the launcher's rule).  (static: product and development library may sit in one process)
+static inline MlaIndexerCheck mla_indexer_cache_check(uintptr_t base, int64_t block_size, int64_t block_stride) {
+  if (block_stride < 0) return {HPC_ERR_INVALID, "k_cache block stride must not be negative"};
+  if (mla_page_shift(block_size) < 0) return {HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128"};
+  if (block_stride < mla_indexer_page_bytes(block_size))
+    return {HPC_ERR_UNSUPPORTED, "k_cache block stride must be at least block_size * 132 bytes"};
+  if (block_stride % 16) return {HPC_ERR_UNSUPPORTED, "k_cache block stride must be a multiple of 16 bytes"};
+  if (base % 16) return {HPC_ERR_UNSUPPORTED, "k_cache must be 16-byte aligned"};
+  return {HPC_OK, nullptr};
+}
+
+// The scratch of the fused call (logits then top-k): one float32 row per q row, rows of row_stride floats.  Sizer
+// (hpc_mla_indexer_plan), launcher (hpc_mla_indexer_topk_fp8_async) and shim all take it from here.
+struct MlaIndexerScratch {
+  int64_t row_stride;  // floats: the logits' columns (a multiple of 16 already: max_blocks * P)
+  int64_t bytes;       // rows * row_stride * 4; never zeroed: the top-k reads only the columns the logits op wrote
+};
+static inline MlaIndexerScratch mla_indexer_scratch(int64_t rows, int64_t cols) { return {cols, rows * cols * 4}; }
+
+struct MlaIndexerRoute {
+  int code;          // HPC_OK or the refusal; the rest is set either way (zeros where it has no meaning)
+  const char* why;   // the refusal in words (null when accepted)
+  int head_blocks;   // num_head / 16: matrix instructions per 16 tokens and q row
+  int64_t cols;      // max_blocks * block_size: the logits' columns
+  int chunk;         // tokens of a request's context one logits workgroup owns (a multiple of 256)
+  int chunks;        // ceil(cols / chunk)
+  int grid;          // logits workgroups, one dimension: id = b * chunks + piece; a piece at or past the request's end leaves at once
+  int topk_grid;     // top-k workgroups: one per q row
+  MlaIndexerScratch scratch;  // of the fused call
+};
+
+// logits_only: the list length has no part in the call and topk is not looked at; otherwise 1 .. 65536.  The chunk: 512 tokens, doubled while
+// the grid is beyond 16 workgroups per CU, up to 8192 - a host value: nothing here or on the device depends on the lengths of
+// the requests for it.  cu_count <= 0: 256.
+static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
+                                                int topk, bool logits_only, int cu_count) {
+  MlaIndexerRoute r{};
+  const auto refuse = [&](int code, const char* why) {
+    r.code = code;
+    r.why = why;
+    return r;
+  };
+  if (num_batch < 0) return refuse(HPC_ERR_INVALID, "num_batch must not be negative");
+  if (num_seq_q <= 0) return refuse(HPC_ERR_INVALID, "num_seq_q must be positive");
+  if (max_blocks < 0) return refuse(HPC_ERR_INVALID, "max_blocks must not be negative");
+  if (num_seq_q > kIdxMaxSeqQ) return refuse(HPC_ERR_UNSUPPORTED, "mtp must be 0 .. 3");
+  if (num_head != 16 && num_head != 32 && num_head != 64) return refuse(HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64");
+  if (mla_page_shift(block_size) < 0) return refuse(HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128");
+  if (!logits_only && (topk < 1 || topk > kIdxMaxTopk)) return refuse(HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536");
+  r.head_blocks = num_head / 16;
+  r.cols = static_cast<int64_t>(max_blocks) * block_size;
+  if (r.cols > kIdxMaxCols) return refuse(HPC_ERR_UNSUPPORTED, "block_ids reaches beyond 2^30 tokens");
+  const int64_t rows = static_cast<int64_t>(num_batch) * num_seq_q;
+  if (rows > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "num_batch * num_seq_q beyond int32");
+  r.topk_grid = static_cast<int>(rows);
+  r.scratch = mla_indexer_scratch(rows, r.cols);
+  const int cus = cu_count > 0 ? cu_count : 256;
+  int64_t chunk = kIdxMinChunk;
+  while (chunk < kIdxMaxChunk && num_batch * ((r.cols + chunk - 1) / chunk) > 16ll * cus) chunk *= 2;
+  r.chunk = static_cast<int>(chunk);
+  r.chunks = static_cast<int>((r.cols + chunk - 1) / chunk);
+  const int64_t grid = static_cast<int64_t>(num_batch) * r.chunks;
+  if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
+  r.grid = static_cast<int>(grid);
+  return r;
+}
+
+}  // namespace hpc

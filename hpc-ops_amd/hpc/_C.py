@@ -106,6 +106,16 @@ _sig("hpc_attention_decode_mla_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I,
 _sig("hpc_attention_decode_mla_sparse_plan", I, I, I, I, I, I, I, IP, IP, ctypes.POINTER(c_int64), IP, IP)
 _sig("hpc_attention_decode_mla_sparse_bf16_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, I, P, L, P)
 _sig("hpc_attention_decode_mla_sparse_fp8_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, I, P, L, P)
+LP = ctypes.POINTER(c_int64)
+_sig("hpc_mla_indexer_plan", I, I, I, I, I, I, I, I, IP, IP, IP, LP, LP)
+_sig("hpc_mla_indexer_store_k_fp8_refusal", c_char_p, P, P, IP, IP, IP, I, I, I, I, I, L, L)
+_sig("hpc_mla_indexer_store_k_fp8_async", I, P, P, IP, IP, IP, I, I, I, I, I, L, L, P)
+_sig("hpc_mla_indexer_logits_fp8_refusal", c_char_p, P, P, P, P, IP, IP, I, I, I, I, I, I, L, L)
+_sig("hpc_mla_indexer_logits_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I, I, L, L, I, P)
+_sig("hpc_mla_indexer_topk_refusal", c_char_p, P, P, IP, I, I, L, I, L)
+_sig("hpc_mla_indexer_topk_async", I, P, P, IP, I, I, L, I, L, I, P)
+_sig("hpc_mla_indexer_topk_fp8_refusal", c_char_p, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, P, L)
+_sig("hpc_mla_indexer_topk_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, I, P, L, P)
 _sig("hpc_mla_rope_norm_store_kv_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_mla_rope_norm_store_kv_fp8_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_attention_prefill_mla_bf16_async", I, P, P, P, P, P, P, IP, IP, I, I, I, I, L, L, L, L, L, L, L, F, I, P)

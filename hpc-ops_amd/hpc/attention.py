@@ -127,8 +127,8 @@ def task_workspace_bytes(num_cu, max_num_batch, max_seqlen, num_head_kv, min_pro
 
 def release_decode_workspaces():
     """Drop EVERY zero-once scratch buffer the host library caches per (purpose, device, stream, hipGraph capture) - the
-    decode workspaces, the router GEMM's split-K ticket buffers and the MLA decode's split-KV partials alike
-    (csrc/torch_common.h::release_cached_scratch) -
+    decode workspaces, the router GEMM's split-K ticket buffers, the MLA decode's split-KV partials and the MLA indexer's
+    logits alike (csrc/torch_common.h::release_cached_scratch) -
     e.g. after the streams / graphs that used them are gone.  Buffers of captures that have ended are dropped on the
     next call on their stream anyway."""
     torch.ops.hpc._release_decode_workspaces()

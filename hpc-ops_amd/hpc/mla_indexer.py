@@ -1,0 +1,126 @@
+"""The DSA lightning indexer of a DeepSeek-V3.2 decode step: the paged FP8 index-key cache, its writer, the FP8 MQA logits over it
+and the top-k that yields the `indices` of hpc.attention_decode_mla_sparse_bf16 / _fp8 (csrc/mla_indexer.hip).
+
+No reference counterpart: the ops are registered under torch.ops.hpc_mla.* and pinned to the float64 PyTorch statement
+tests/mla_indexer_ref.py.  The index key's LayerNorm, RoPE and rotation in front of the store are the caller's.
+"""
+import torch
+from torch import Tensor
+
+from . import _C  # noqa: F401  (loads the libraries that register torch.ops.hpc_mla.*)
+
+
+def mla_indexer_store_k_fp8(k_cache: Tensor, k: Tensor, num_seqlen_per_req: Tensor, q_index: Tensor, block_ids: Tensor) -> None:
+    """Quantise the index keys of the new tokens and store them in the paged index-key cache.  Returns None.
+
+    The index-key cache: every token of every request has ONE index key of 128 columns, shared by all index heads, stored
+    as 128 float8_e4m3fn codes and one float32 scale; a column is fp32(code[d]) * scale.  k_cache is a torch.uint8 tensor,
+    logically [num_blocks, P * 132], addressed through the same block_ids page table as the latent cache.  Within a page
+    the codes of its P tokens come first ([P, 128] at byte 0), the P float32 scales follow at byte P * 128, so every
+    16-byte access is aligned without padding a row to 144 bytes.  P in {16, 32, 64, 128}; the block stride
+    (k_cache.stride(0)) is at least P * 132 and a multiple of 16 bytes; the base is 16-byte aligned.  The readers take any
+    finite non-negative scale, so a cache written by another producer of this layout works.
+
+    k                 bf16 [T, 128]: the index key after the caller's own norm, RoPE and rotation.  The last dim is
+                      contiguous, the row stride a multiple of 8 elements, the base 16-byte aligned.
+    quantisation      the convention of hpc.blockwise_fp8_quant, a row being exactly one 128-block, every step in fp32:
+                      scale = amax / 448, code = e4m3fn(x * (1 / (scale + 1e-8))) - bit-identical to
+                      tests/blockwise_quant_ref.py::quant(k).
+    destination       as hpc.mla_rope_norm_store_kv: row r belongs to the last request b with q_index[b] <= r, at position
+                      num_seqlen_per_req[b] - (q_index[b + 1] - r).  num_seqlen_per_req int32 [num_req] (total lengths
+                      including the new tokens), q_index int32 [num_req + 1], block_ids int32 [num_req, max_blocks].  Rows
+                      of no request store nothing, a page id outside [0, num_blocks) stores nothing, a position beyond the
+                      table stores nothing; only the 128 + 4 bytes of a new token are written, page tails are not cleared.
+
+    Everything is read on the device: the call allocates nothing and captures into a hipGraph.  T == 0 or num_req == 0
+    returns without a launch."""
+    torch.ops.hpc_mla.mla_indexer_store_k_fp8(k_cache, k, num_seqlen_per_req, q_index, block_ids)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_store_k_fp8")
+def _mla_indexer_store_k_fp8_fake(k_cache, k, num_seqlen_per_req, q_index, block_ids):
+    return None
+
+
+def mla_indexer_logits_fp8(q: Tensor, weights: Tensor, k_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor, mtp: int = 0,
+                           new_kv_included: bool = False, *, output: Tensor = None) -> Tensor:
+    """The indexer's FP8 MQA logits over the paged index-key cache.  Returns float32 [B * Sq, max_blocks * P].
+
+    Semantics = the PyTorch statement tests/mla_indexer_ref.py, in float64.  With Sq = mtp + 1, L_b the tokens of request b
+    including the Sq new ones (the new_kv_included convention of attention_decode_mla_sparse_bf16) and
+    vis(b, s) = L_b - Sq + s + 1, for 0 <= j < min(vis(b, s), max_blocks * P):
+
+        logit[b*Sq+s, j] = kscale_b[j] * sum_h weights[b*Sq+s, h] * relu( sum_{d<128} q[b*Sq+s, h, d] * kcode_b[j, d] )
+
+    q                float8_e4m3fn [B * Sq, Hi, 128], contiguous, Hi in {16, 32, 64}.
+    weights          float32 [B * Sq, Hi].  The caller folds the q scales, the softmax scale and Hi ** -0.5 into it, as
+                     DeepSeek's reference does; weights may be negative (in the model they are):
+                         q8, q_scale = hpc.blockwise_fp8_quant(q_idx.view(T * Hi, 128))      # codes, per-(token, head) scales
+                         weights = head_weights * q_scale.view(T, Hi) * softmax_scale * Hi ** -0.5
+                         logits = hpc.mla_indexer_logits_fp8(q8.view(T, Hi, 128), weights, k_cache, block_ids, lens)
+    k_cache          the cache of mla_indexer_store_k_fp8: torch.uint8 [num_blocks, P * 132], P in {16, 32, 64, 128}.
+    poisoned pages   a position whose page id lies outside [0, num_blocks) gets -inf, and its page is never loaded.
+    unwritten        columns at or past min(vis, max_blocks * P) are NOT written (mla_indexer_topk never reads them): a
+                     fresh output holds whatever the allocator left there.
+    limits           mtp 0..3; max_blocks * P <= 2^30; B == 0 returns an empty tensor without a launch.
+
+    Nothing on the host reads lengths or pages and every address is checked against a host value: with output given
+    nothing is allocated and the call captures into a hipGraph.  No float atomics, and the head sum has a fixed order:
+    the result is bit-identical from call to call."""
+    return torch.ops.hpc_mla.mla_indexer_logits_fp8(q, weights, k_cache, block_ids, num_seq_kvcache, int(mtp), bool(new_kv_included),
+                                                    output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_logits_fp8")
+def _mla_indexer_logits_fp8_fake(q, weights, k_cache, block_ids, num_seq_kvcache, mtp, new_kv_included, output=None):
+    if output is not None:
+        return output
+    return q.new_empty((q.shape[0], block_ids.shape[1] * (k_cache.shape[1] // 132)), dtype=torch.float32)
+
+
+def mla_indexer_topk(logits: Tensor, num_seq_kvcache: Tensor, topk: int, mtp: int = 0, new_kv_included: bool = False, *,
+                     output: Tensor = None) -> Tensor:
+    """The indexer's top-k: the positions of the topk best logits per q row.  Returns int32 [B * Sq, topk] - the `indices`
+    of attention_decode_mla_sparse_bf16 / _fp8.
+
+    Semantics = tests/mla_indexer_ref.py::topk_statement.  A pure selection over row r's columns [0, n_r), with
+    n_r = clamp(vis(b, s), 0, logits.shape[1]) and vis(b, s) = L_b - Sq + s + 1 as in mla_indexer_logits_fp8.
+
+    selection        the min(topk, n_r) best positions under (logit descending, position ascending): ties go to the
+                     smaller position.  Values are ordered as torch.topk orders them: -0.0 == +0.0, NaN ranks above +inf;
+                     -inf is an ordinary lowest value (the attention drops unreadable positions itself).
+    output           the positions in ASCENDING position order, then -1 to the end of the row: the list is deterministic
+                     (the sparse attention sums in list order) and page-local.  When n_r <= topk the list is exactly
+                     0 .. n_r - 1 then -1 - the identity list on which the sparse op is bit-equal to the dense op - and
+                     the logits are not read at all.  Columns at or past n_r are never read.
+    logits           float32 [B * Sq, columns], last dim contiguous, row stride >= columns <= 2^30.
+    limits           topk 1..65536, any value; mtp 0..3; B == 0 returns an empty tensor without a launch.
+
+    Nothing on the host reads lengths or logits: with output given nothing is allocated and the call captures into a
+    hipGraph.  Integer arithmetic only: the result is bit-identical from call to call."""
+    return torch.ops.hpc_mla.mla_indexer_topk(logits, num_seq_kvcache, int(topk), int(mtp), bool(new_kv_included), output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_topk")
+def _mla_indexer_topk_fake(logits, num_seq_kvcache, topk, mtp, new_kv_included, output=None):
+    return output if output is not None else logits.new_empty((logits.shape[0], topk), dtype=torch.int32)
+
+
+def mla_indexer_topk_fp8(q: Tensor, weights: Tensor, k_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor, topk: int,
+                         mtp: int = 0, new_kv_included: bool = False, *, output: Tensor = None) -> Tensor:
+    """mla_indexer_logits_fp8 then mla_indexer_topk in one call.  Returns int32 [B * Sq, topk]: what goes into
+    attention_decode_mla_sparse_bf16 / _fp8 as `indices`.
+
+    The logits go through a cached scratch buffer of float32 [B * Sq, max_blocks * P] per (device, stream, hipGraph
+    capture) that hpc.release_decode_workspaces() drops; it is never zeroed, the top-k reads only the columns the logits
+    wrote.  Arguments, limits and rules are those of the two ops; the result is bit-identical to calling them one after
+    the other, and from call to call.  With output given nothing is allocated beyond the scratch and the call captures
+    into a hipGraph, which replayed after lengths, page table, cache contents and q changed in place gives the new result.
+    Two launches: nothing is fused between them."""
+    return torch.ops.hpc_mla.mla_indexer_topk_fp8(q, weights, k_cache, block_ids, num_seq_kvcache, int(topk), int(mtp),
+                                                  bool(new_kv_included), output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_topk_fp8")
+def _mla_indexer_topk_fp8_fake(q, weights, k_cache, block_ids, num_seq_kvcache, topk, mtp, new_kv_included, output=None):
+    return output if output is not None else q.new_empty((q.shape[0], topk), dtype=torch.int32)

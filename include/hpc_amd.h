@@ -540,6 +540,79 @@ int hpc_attention_decode_mla_sparse_fp8_async(void* out, float* lse, const void*
                                               float softmax_scale, int new_kv_included, int splits, void* workspace,
                                               int64_t workspace_bytes, hpc_stream_t stream);
 
+/* ---- The DSA lightning indexer: FP8 index-key cache, MQA logits, top-k (csrc/mla_indexer.hip) --------------------------------
+ * What yields the `indices` of the token-sparse attention above.  No reference kernel; the statement is
+ * tests/mla_indexer_ref.py, the layout and the one route csrc/mla_indexer_route.h.
+ * The index-key cache: every token has one key of 128 columns shared by all index heads, 128 float8_e4m3fn codes and one fp32
+ * scale, column d = fp32(code[d]) * scale for ANY finite non-negative scale.  Page p lies at k_cache + p *
+ * k_cache_block_stride_bytes: the codes of its block_size tokens first (token t at byte 128 t), then the block_size fp32 scales
+ * (token t at byte 128 * block_size + 4 t).  block_size 16 / 32 / 64 / 128, block stride >= 132 * block_size and a multiple of
+ * 16 bytes, base 16-byte aligned; pages are addressed through the block_ids of the latent cache.
+ *
+ * hpc_mla_indexer_store_k_fp8_async: row r of k (bf16 [num_rows, 128], row stride in elements, a multiple of 8, base 16-byte
+ * aligned) is one new token; its request and position are those of hpc_mla_rope_norm_store_kv_async (num_seqlen_per_req,
+ * q_index, block_ids ON THE DEVICE, never read by the host).  In fp32: scale = max |k[r]| / 448, code[d] = e4m3fn_sat(k[r, d] *
+ * (1 / (scale + 1e-8))) - bit for bit hpc_blockwise_fp8_quant_async on the row.  Only the 128 + 4 bytes of a new token are
+ * written; rows of no request, positions beyond the table and page ids outside [0, num_blocks) store nothing.
+ *
+ * hpc_mla_indexer_logits_fp8_async: q e4m3 [num_batch * num_seq_q, num_head, 128] contiguous, weights fp32 [num_batch *
+ * num_seq_q, num_head] (the caller folds the q scales, the softmax scale and num_head^-0.5 into them; they may be negative),
+ * both 16-byte aligned; num_head 16 / 32 / 64; num_seq_q 1 .. 4.  With L_b and vis(b, s) = L_b - num_seq_q + s + 1 as in the
+ * sparse attention (num_seq_kvcache, new_kv_included), for 0 <= j < min(vis(b, s), max_blocks * block_size):
+ *   logits[(b * num_seq_q + s) * logits_row_stride + j] = kscale_b[j] * sum_h weights[., h] * relu( sum_d q[., h, d] * kcode_b[j, d] )
+ * and -inf where the page id of j lies outside [0, num_blocks) (its page is never loaded).  Columns at or past that bound are
+ * NOT written.  logits fp32, row stride in floats >= max_blocks * block_size <= 2^30.  The head sum has a fixed order, there are
+ * no float atomics: the same bits on every call.  Every address is checked against a host value.
+ *
+ * hpc_mla_indexer_topk_async: a pure selection over row r's columns [0, n_r), n_r = clamp(vis, 0, num_cols): the min(topk, n_r)
+ * best positions under (logit descending, position ascending) in torch.topk's order of values (-0.0 == +0.0, NaN above +inf,
+ * -inf an ordinary lowest value), written to indices int32 [num_batch * num_seq_q, topk] in ASCENDING position order, then -1.
+ * With n_r <= topk the list is 0 .. n_r - 1 and no logit is read; columns at or past n_r are never read.  1 <= topk <= 65536.
+ *
+ * hpc_mla_indexer_topk_fp8_async: the two back to back through `workspace` (fp32 rows of logits_row_stride floats,
+ * workspace_bytes >= the plan's, 4-byte aligned, never zeroed); bit-identical to the two calls.
+ *
+ * hpc_mla_indexer_plan(..., topk (0: a logits call), num_cu (<= 0: the current device's), ...) gives the logits launch's
+ * workgroups and the tokens of a request's context each owns (a host value: 512, doubled up to 8192 while the grid is beyond 16
+ * per CU), the top-k launch's workgroups, and the fused call's scratch: its row stride in floats and its bytes.  It returns what
+ * the calls would for these arguments.
+ * HPC_ERR_INVALID: negative counts, num_seq_q <= 0, a negative block stride, null pointers (with work), max_blocks == 0 with
+ * work, a workspace that is missing or too small; HPC_ERR_UNSUPPORTED: num_seq_q > 4, num_head, block_size, topk outside
+ * 1 .. 65536, the strides, alignment, sizes beyond int32 or 2^30 columns.  num_batch == 0 (store: num_rows == 0 or num_req == 0)
+ * launches nothing.  Every check is made on the host before any device call; hpc_mla_indexer_*_refusal return the refusal of the
+ * same call in words, or NULL for a call that is accepted: pure host functions.  Nothing on the host reads lengths or pages. */
+int hpc_mla_indexer_plan(int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks, int topk, int num_cu,
+                         int* grid, int* chunk, int* topk_grid, int64_t* logits_row_stride, int64_t* workspace_bytes);
+const char* hpc_mla_indexer_store_k_fp8_refusal(const void* k_cache, const void* k, const int* num_seqlen_per_req,
+                                                const int* q_index, const int* block_ids, int num_rows, int num_req,
+                                                int block_size, int max_blocks, int num_blocks,
+                                                int64_t k_cache_block_stride_bytes, int64_t k_row_stride);
+int hpc_mla_indexer_store_k_fp8_async(void* k_cache, const void* k, const int* num_seqlen_per_req, const int* q_index,
+                                      const int* block_ids, int num_rows, int num_req, int block_size, int max_blocks,
+                                      int num_blocks, int64_t k_cache_block_stride_bytes, int64_t k_row_stride,
+                                      hpc_stream_t stream);
+const char* hpc_mla_indexer_logits_fp8_refusal(const float* logits, const void* q, const float* weights, const void* k_cache,
+                                               const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                                               int num_head, int block_size, int max_blocks, int num_blocks,
+                                               int64_t k_cache_block_stride_bytes, int64_t logits_row_stride);
+int hpc_mla_indexer_logits_fp8_async(float* logits, const void* q, const float* weights, const void* k_cache,
+                                     const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head,
+                                     int block_size, int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes,
+                                     int64_t logits_row_stride, int new_kv_included, hpc_stream_t stream);
+const char* hpc_mla_indexer_topk_refusal(const int* indices, const float* logits, const int* num_seq_kvcache, int num_batch,
+                                         int num_seq_q, int64_t num_cols, int topk, int64_t logits_row_stride);
+int hpc_mla_indexer_topk_async(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                               int64_t num_cols, int topk, int64_t logits_row_stride, int new_kv_included, hpc_stream_t stream);
+const char* hpc_mla_indexer_topk_fp8_refusal(const int* indices, const void* q, const float* weights, const void* k_cache,
+                                             const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q,
+                                             int num_head, int block_size, int max_blocks, int num_blocks,
+                                             int64_t k_cache_block_stride_bytes, int topk, const void* workspace,
+                                             int64_t workspace_bytes);
+int hpc_mla_indexer_topk_fp8_async(int* indices, const void* q, const float* weights, const void* k_cache, const int* block_ids,
+                                   const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size,
+                                   int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
+                                   int new_kv_included, void* workspace, int64_t workspace_bytes, hpc_stream_t stream);
+
 /* ---- MLA latent-cache write: kv_a RMSNorm + RoPE + paged store, bf16 (csrc/mla_store.hip) ------------------------------------
  * No reference kernel exists; the semantics are the PyTorch statement tests/mla_store_ref.py.  The producer of the cache and of
  * the RoPE columns of q that hpc_attention_decode_mla_bf16_async reads.  Row r of kv_a is one new token; its request b is the

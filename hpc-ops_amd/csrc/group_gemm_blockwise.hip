@@ -185,7 +185,9 @@ __global__ __launch_bounds__(64 * kWaves, (kWaves == 8 || kMT * kR >= 8) ? 1 : 2
         for (int kbl = 0; kbl < 2; ++kbl) {
           const int kb = 2 * st + kbl;
           const int kbc = kb < KB ? kb : KB - 1;
-          const float wsk = kb < KB ? __int_as_float(ws_row[kbc * a.ws_kb_stride]) : 0.f;
+          // (one scale per group, has_xs == 0: the k-blocks are summed unscaled, the scale multiplies the sum once - below)
+          const float wsl = __int_as_float(ws_row[kbc * a.ws_kb_stride]);
+          const float wsk = kb < KB ? (a.has_xs ? wsl : 1.f) : 0.f;
           // token blocks two at a time: their MFMA chains (4 dependent k-steps each) interleave
           constexpr int kPair = (kMT % 2 == 0) ? 2 : 1;
 #pragma unroll
@@ -233,6 +235,16 @@ __global__ __launch_bounds__(64 * kWaves, (kWaves == 8 || kMT * kR >= 8) ? 1 : 2
       }
     }
 
+    // One scale per group: y = bf16((x w^T) * scale), the fp32 sum rounded ONCE by the scale, as the reference's kernel and the
+    // 256-wide kernels have it (scaled k-block by k-block the running sum is rounded at every block: an output near a bf16 tie
+    // then depends on the kernel the route picked).
+    if (!a.has_xs) {
+      const float ys = __int_as_float(ws_row[0]);
+#pragma unroll
+      for (int rb = 0; rb < kR; ++rb)
+#pragma unroll
+        for (int mt = 0; mt < kMT; ++mt) tot[rb][mt] *= ys;
+    }
 #pragma unroll
     for (int mt = 0; mt < kMT; ++mt) {
       const int slot = p * kTok + mt * 16 + r16;
@@ -391,7 +403,9 @@ __global__ __launch_bounds__(256, 2) void gemm_blockwise_stream2_kernel(const Ar
         __syncthreads();
         u32x4 b0[2][kMT], b1[2][kMT];
         float f[2][kMT];
-        const float wsk[2] = {kb_a < KB ? __int_as_float(wsi_a) : 0.f, kb_b < KB ? __int_as_float(wsi_b) : 0.f};
+        // (one scale per group: the k-blocks are summed unscaled, the scale multiplies the sum once - below, as in the kernel above)
+        const float wsk[2] = {kb_a < KB ? (has_xs ? __int_as_float(wsi_a) : 1.f) : 0.f,
+                              kb_b < KB ? (has_xs ? __int_as_float(wsi_b) : 1.f) : 0.f};
         auto read_b = [&](int kbl) {
 #pragma unroll
           for (int q = 0; q < kMT; ++q) {
@@ -451,6 +465,11 @@ __global__ __launch_bounds__(256, 2) void gemm_blockwise_stream2_kernel(const Ar
       }
     }
 
+    if (!has_xs) {
+      const float ys = __int_as_float(ws_row[0]);
+#pragma unroll
+      for (int mt = 0; mt < kMT; ++mt) tot[mt] *= ys;
+    }
 #pragma unroll
     for (int mt = 0; mt < kMT; ++mt) {
       const int slot = p * kTok + mt * 16 + r16;

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_fp8_tiled_kernel(const Args 
     float f[4];
     const float wsk = __int_as_float(ws_row[kb * a.ws_kb_stride]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = a.has_xs ? a.xs[xs_term[j] + kb * a.xs_kb_stride] * wsk : wsk;
+    for (int j = 0; j < 4; ++j) f[j] = a.has_xs ? a.xs[xs_term[j] + kb * a.xs_kb_stride] * wsk : 1.f;  // (else: scaled once, below)
 
     f32x4 part[4][4];
 #pragma unroll
@@ -140,6 +140,16 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_fp8_tiled_kernel(const Args 
     __syncthreads();
   }
 
+  // One scale per group (has_xs == 0): the k-blocks were summed unscaled and the scale multiplies the sum once,
+  // y = bf16((x w^T) * scale) with ONE fp32 rounding in front of the bf16 one, as the reference's kernel and the 256-wide kernels
+  // have it (group_gemm_blockwise.hip, the streaming kernels' epilogue, says what the other order costs).
+  if (!a.has_xs) {
+    const float ys = __int_as_float(ws_row[0]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tot[i][j] *= ys;
+  }
   // ---- epilogue: lane holds rows n = i*16 + g4*4 + r of token column j*16 + r16 -----------------------
 #pragma unroll
   for (int j = 0; j < 4; ++j) {

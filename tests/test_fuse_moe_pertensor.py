@@ -396,6 +396,8 @@ def test_masked_act_variants():
     gt = omoe.act_mul_and_quant(gate_up, scale, use_bf16_mul=False)
     assert my.data_ptr() == out.data_ptr()
     assert allclose(gt.float()[keep], my.cpu().float()[keep], atol=0.15, rtol=0.13)
+    agree = (gt.view(torch.uint8)[keep] == my.cpu().view(torch.uint8)[keep]).float().mean().item()
+    assert agree > 0.995, agree  # the rate test_act_mul_and_quant holds the unmasked form to
     assert torch.equal(my.cpu().view(torch.uint8)[~keep], sentinel.view(torch.uint8)[~keep])
     qb, sb = hpc.masked_act_mul_and_blockwise_quant(gate_up.cuda(), cnt.cuda())
     gq, gs = omoe.act_mul_and_blockwise_quant(gate_up)

@@ -130,6 +130,63 @@ def rope_close(ref64, got, mult=None, slack=ROPE_SLACK, label=""):
     return ok
 
 
+NORM_SLACK = 2.0 ** -19
+"""fp32 slack of the RMSNorm quantiser's bar (quant_close in tests/test_normalization_bar.py), relative to each element.
+
+Measured: the fp32 oracle (oracle/normalization.py::rmsnorm_fp32, then `* (1 / scale)` in fp32) against the float64
+statement (tests/quant_ref.py::rmsnorm_ref64) on every input of tests/test_normalization_bar.py (15 hidden sizes x 1 / 3 /
+5 / 9 rows, both scale pairs) has a worst quant_excess of 2.22e-7 on the fp32 output and 8.8e-8 on the e4m3 outputs
+(test_fp32_oracle_passes_and_its_excess prints them again and holds the constant to them).  8 x 2.22e-7 = 1.78e-6, and the
+next power of two at or above that is 2^-19 = 1.91e-6.  The margin is for what a correct kernel may do differently from the oracle: another order
+of the sum of squares, the hardware reciprocal square root, `1.0f / scale` and a multiply where the oracle multiplies
+the same reciprocal, and its two fp32 multiplies.  Cap: 2^-18; a kernel that needs more is a finding."""
+
+ACT_SLACK = 2.0 ** -19
+"""fp32 slack of the activation quantisers' bar (tests/test_act_quant_bar.py), relative to each element.
+
+Measured: a CPU model of the device formula g / (1 + __expf(-g)) in fp32 (tests/quant_ref.py::silu_device_model: the
+exponential evaluated in float64, rounded to fp32 and moved by +1 / 0 / -1 fp32 ulp - the microarchitecture guide states
+no accuracy for the hardware exponential, so +-1 ulp is used - then the add, the divide, `* u` and `* scale` each
+rounded to fp32) against the float64 silu(g) * u * scale over the test's random gates (|g| <= 8) has a worst
+quant_excess of 2.75e-7 on the fp32 value in front of the cast (no half-ulp term: the model's fp32 error itself) and of
+1.1e-8 on its e4m3 codes (positive only on the few elements an fp32 error carries over an e4m3 tie, so it falls with the
+element count; the larger figure counts).  test_device_model_passes_and_its_excess prints both again and holds the
+constant to them.  4 x 2.75e-7 = 1.1e-6, rounded up to a power of two: 2^-19 = 1.91e-6.  Cap: 2^-16; a kernel that
+needs more is a finding."""
+
+
+def quant_excess(t64, got, ulp):
+    """What a quantiser's output misses its float64 target by, beyond one rounding, per element and relative to it:
+        (|got - t| - 0.5 ulp(t)) / max(|t|, tiny)
+    t64: the target, already multiplied by the scale and clamped to +-448 for e4m3.  ulp: ulp_e4m3 or ulp_bf16, or None
+    for an fp32 output (no half-ulp term: the slack alone is the bar).  A NaN in `got` where t is finite is an infinite
+    excess; where t is NaN `got` must be NaN (for e4m3: the byte 0x7f) and the excess is then 0.  Zeros compare by value,
+    so -0 meets a target of +0."""
+    assert t64.dtype == torch.float64 and t64.shape == got.shape, (t64.dtype, t64.shape, got.shape)
+    g = got.float().double()
+    half = 0.5 * ulp(t64) if ulp is not None else torch.zeros_like(t64)
+    ex = ((g - t64).abs() - half) / t64.abs().clamp_min(1e-300)
+    ex = torch.where(g.isnan(), torch.full_like(ex, float("inf")), ex)
+    nan_ok = g.isnan() & (got.view(torch.uint8) == 0x7F if got.dtype == torch.float8_e4m3fn else True)
+    return torch.where(t64.isnan(), torch.where(nan_ok, 0.0, float("inf")).to(ex.dtype), ex)
+
+
+def quant_close(t64, got, ulp, slack, label=""):
+    """The quantisers' bar: every element of `got` within half an ulp of its float64 target plus `slack` x |target|
+    (quant_excess).  Prints the worst excess in units of the slack; on failure the ten worst elements too."""
+    ex = quant_excess(t64, got, ulp)
+    worst = float(ex.max()) if ex.numel() else float("-inf")
+    ok = bool((ex <= slack).all())
+    print(f"quant_close {label}: worst excess {worst:.3g} = {worst / slack:.3g} x slack"
+          + ("" if ok else f"  FAILED: {int((ex > slack).sum())}/{ex.numel()} elements over"))
+    if not ok:
+        for i in torch.topk(ex.reshape(-1), min(10, ex.numel())).indices.tolist():
+            idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ex.shape))
+            print(f"  {idx}: got {float(got.reshape(-1)[i].float()):.9g} target {float(t64.reshape(-1)[i]):.9g} "
+                  f"excess {float(ex.reshape(-1)[i]):.3g}")
+    return ok
+
+
 def to_cpu(*ts):
     return [t.cpu() if t is not None else None for t in ts]
 

@@ -1,6 +1,8 @@
 """Float64 statements of the per-tensor FP8 path and the RMSNorm quantiser, their inputs, and the CPU models the slacks
 of tests/utils.py are measured on (tests/test_normalization_bar.py, tests/test_act_quant_bar.py,
-tests/test_group_gemm_pertensor_exact.py).  CPU tensors only."""
+tests/test_group_gemm_pertensor_exact.py), and the statements of the blockwise grouped GEMM's k-block chain and of the MoE
+reduce with their float64 emulation of fp32 FMAs (tests/test_group_gemm_blockwise_exact.py, tests/test_moe_reduce_bar.py).
+CPU tensors only."""
 import functools
 
 import torch
@@ -215,3 +217,127 @@ def bf16_tie_share(y64):
     """share of the float64 values that sit exactly half way between two bf16 values"""
     b = y64.contiguous().view(torch.int64)
     return float(((b & ((1 << 45) - 1)) == (1 << 44)).double().mean())
+
+
+# ------------------------------------------------------------------- blockwise grouped GEMM, exact inputs (128-block scales)
+LOUD = 2.0 ** 20  # what every scale holds that belongs to no valid (row, k-block) or (n-block, k-block): finite, and never right
+
+
+def pad4(v):
+    return (v + 3) // 4 * 4
+
+
+def fma32(a64, b64, c64):
+    """fp32 fmaf(a, b, c) on float64 tensors that hold fp32 values whose product a * b is exact in float64 (here: 11 x 24
+    bits) -> (the fp32 result as float64, mask of the elements where it is not certain).  The float64 sum p + c is rounded
+    once; TwoSum recovers its error.  Rounding that sum to fp32 is the one rounding of a true FMA unless the float64 sum was
+    inexact AND sits exactly half way between two fp32 values - then the lost bits decide the direction, and the mask says
+    so.  (An inexact sum that is no midpoint is at least one float64 ulp from the nearest one: same side as the true sum.)
+    Normal fp32 results only."""
+    p = a64 * b64
+    s = p + c64
+    bb = s - p
+    err = (p - (s - bb)) + (c64 - bb)
+    mid = (s.contiguous().view(torch.int64) & ((1 << 29) - 1)) == (1 << 28)
+    return s.float().double(), mid & (err != 0)
+
+
+def blockwise_scales(rows, num_group, n, k, seed, kind, loud_rows=None):
+    """-> (xs f32 [rows, k / 128], ws f32 [num_group, n / 128, pad4(k / 128)]).  kind "pow2": xs = 2^e, ws = +-2^e with e in
+    -3 ... 1; "general": xs = rand + 0.5, ws = +-(rand + 0.5).  The signs are drawn per (group, n-block, k-block) and are the
+    same for both kinds.  ws columns kb >= k / 128 and the xs rows named by loud_rows hold LOUD."""
+    g = torch.Generator().manual_seed(seed)
+    kb = k // 128
+    sign = (torch.randint(0, 2, (num_group, n // 128, kb), generator=g) * 2 - 1).float()
+    ex, ew = torch.randint(-3, 2, (rows, kb), generator=g), torch.randint(-3, 2, (num_group, n // 128, kb), generator=g)
+    rx, rw = torch.rand((rows, kb), generator=g), torch.rand((num_group, n // 128, kb), generator=g)
+    xs = torch.exp2(ex.float()) if kind == "pow2" else rx + 0.5
+    ws = torch.full((num_group, n // 128, pad4(kb)), LOUD)
+    ws[:, :, :kb] = sign * (torch.exp2(ew.float()) if kind == "pow2" else rw + 0.5)
+    if loud_rows is not None:
+        xs[loud_rows] = LOUD
+    return xs.contiguous(), ws
+
+
+def blockwise_block_sums(x, w, row_group):
+    """float64 [k / 128, M, N]: sum_{k in block} x[m, k] * w[row_group[m], n, k].  Integer inputs: computed in fp32, where
+    every partial sum is an integer below 2^24 - exact in any order."""
+    m, k = x.shape
+    n, kb = w.shape[1], k // 128
+    x32, parts = x.float().view(m, kb, 128), torch.zeros(kb, m, n, dtype=torch.float64)
+    for grp in row_group.unique().tolist():
+        rows = torch.nonzero(row_group == grp).flatten()
+        parts[:, rows] = torch.einsum("mbk,nbk->bmn", x32[rows], w[grp].float().view(n, kb, 128)).double()
+    return parts
+
+
+def blockwise_chain(parts, xs, ws_rows, form="fma", order=None):
+    """The grouped blockwise GEMM's k-block chain on the CPU.  parts float64 [KB, M, N] (blockwise_block_sums), xs
+    f32 [M, KB], ws_rows f32 [M, N / 128, KB]: the weight scales each ROW uses.  form "fma": f = fp32(xs * ws), tot =
+    fmaf(part, f, tot) over `order` (default ascending) - the statement; "eager": tot += (part * xs) * ws, every operation
+    rounded to fp32 (the eager model); "round_product": tot += fp32(part * f).
+    -> (tot, the fp32 values as float64 [M, N]; flagged, how many FMAs fma32 could not decide; exact, the float64 sum of
+    part * xs * ws; A, the sum of the |terms|; inexact, how many running sums were rounded)."""
+    kb, m, n = parts.shape
+    tot = torch.zeros(m, n, dtype=torch.float64)
+    exact, big_a = torch.zeros_like(tot), torch.zeros_like(tot)
+    flagged = inexact = 0
+    for b in (range(kb) if order is None else order):
+        wsn = ws_rows[:, :, b].repeat_interleave(128, dim=1)  # [M, N]
+        xsb = xs[:, b].unsqueeze(1)
+        f = (xsb * wsn).double()  # one fp32 multiply
+        term = parts[b] * xsb.double() * wsn.double()
+        exact, big_a = exact + term, big_a + term.abs()
+        if form == "fma":
+            true = parts[b] * f + tot
+            tot, flag = fma32(parts[b], f, tot)
+            flagged += int(flag.sum())
+            inexact += int((tot != true).sum())
+        elif form == "eager":
+            tot = (tot.float() + (parts[b].float() * xsb) * wsn).double()
+        else:
+            tot = (tot.float() + parts[b].float() * f.float()).double()
+    return tot, flagged, exact, big_a, inexact
+
+
+def xs_transposed(xs, seqlens, cu, tile_m, extra=64):
+    """the torch op's activation-scale layout: f32 [KB, sum(ceil(seqlens / tile_m)) * tile_m + extra], group g's rows at
+    columns cu_tiles[g] * tile_m ...; every other column holds LOUD"""
+    tiles = [(int(c) + tile_m - 1) // tile_m for c in seqlens]
+    out = torch.full((xs.shape[1], sum(tiles) * tile_m + extra), LOUD)
+    col = 0
+    for i, c in enumerate(int(c) for c in seqlens):
+        out[:, col : col + c] = xs[int(cu[i]) : int(cu[i]) + c].t()
+        col += tiles[i] * tile_m
+    return out
+
+
+def xs_from_transposed(xs_t, seqlens, tile_m):
+    """rows [sum(seqlens), KB] read back from xs_transposed's layout with `tile_m` (the wrong one: a planted error)"""
+    rows, col = [], 0
+    for c in (int(c) for c in seqlens):
+        rows.append(xs_t[:, col : col + c].t())
+        col += (c + tile_m - 1) // tile_m * tile_m
+    return torch.cat(rows).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------- MoE reduce
+def moe_reduce_chain(x, pos, scale, shared, skip=True, shared_times=1):
+    """csrc/fuse_moe.hip::reduce_kernel on the CPU: acc = fmaf(float(x[pos_j]), scale_j, acc) in j order, pos < 0 skipped
+    (skip=False: read as row 0, a planted error), then acc += shared (shared_times of them), every step rounded to fp32.
+    -> (acc fp32 values as float64 [T, H]; exact, the float64 sum; A, the sum of the |terms|)."""
+    num_tokens, topk = pos.shape
+    acc = torch.zeros(num_tokens, x.shape[1], dtype=torch.float64)
+    exact, big_a = torch.zeros_like(acc), torch.zeros_like(acc)
+    for j in range(topk):
+        p = pos[:, j].long()
+        on = (p >= 0) if skip else torch.ones_like(p, dtype=torch.bool)
+        xr = x[p.clamp_min(0)].double()
+        sc = scale[:, j].double().unsqueeze(1)
+        term = torch.where(on.unsqueeze(1), xr * sc, torch.zeros_like(xr))  # 8 x 24 bits: exact
+        acc = torch.where(on.unsqueeze(1), fma32(xr, sc.expand_as(xr), acc)[0], acc)
+        exact, big_a = exact + term, big_a + term.abs()
+    for _ in range(shared_times if shared is not None else 0):
+        acc = (acc + shared.double()).float().double()  # (through float64: exact on the power-of-two inputs, which alone are held to bits)
+        exact, big_a = exact + shared.double(), big_a + shared.double().abs()
+    return acc, exact, big_a

@@ -528,9 +528,9 @@ extern "C" int hpc_gemm_bf16xfp32_async(void* y_ptr, void* splitk_y_ptr, void* s
                                         int m, int n, int k, float scale, int use_fp32_output, int splits,
                                         int flag_ld, hipStream_t stream) {
   using namespace hpc::rgemm;
-  if (!y_ptr || !x_ptr || !w_high_ptr || !w_low_ptr) return HPC_ERR_INVALID;
   if (m < 0 || n <= 0 || k <= 0 || splits < 1) return HPC_ERR_INVALID;
-  if (m == 0) return HPC_OK;
+  if (m == 0) return HPC_OK;  // nothing to do, nothing read: an empty [0, k] x and [0, n] y have no storage (null pointers)
+  if (!y_ptr || !x_ptr || !w_high_ptr || !w_low_ptr) return HPC_ERR_INVALID;
   // kernel and grid from the route; the split count is the caller's (any count up to the route's bound: grid_z)
   const hpc::RgemmRoute r = hpc::rgemm_route(m, n, k, 0, 0);
   if (r.code != HPC_OK) return r.code;

@@ -121,6 +121,7 @@ def test_router_chain_gemm_topk_fused_moe(num_tokens):
     against the oracle chain fed with the device logits (the GEMM has its own parity test): indices bit-exact,
     MoE output at the reference tolerance."""
     import hpc
+    import router_gemm_ref as rr
     from oracle import fuse_moe as omoe
     from oracle import gemm as ogemm
     from oracle import router as orouter
@@ -131,7 +132,7 @@ def test_router_chain_gemm_topk_fused_moe(num_tokens):
     wr = torch.randn(E, H)
     wh, wl = ogemm.split_weight(wr)
     logits = hpc.gemm_bf16xfp32(xb.cuda(), wh.cuda(), wl.cuda(), 1 / 256, True)
-    assert allclose(ogemm.two_plane(xb, wh, wl, 1 / 256), logits.cpu(), rtol=1e-4, atol=2e-3)
+    assert rr.close(logits.cpu(), *rr.ref64(xb, wh, wl, 1 / 256), f"{num_tokens} tokens")
     ids, sc = hpc.topk_router(logits, k, True)
     rid, rsc = orouter.ref_topk_router(logits.cpu(), k, True)
     assert torch.equal(ids.cpu(), rid) and allclose(rsc, sc.cpu(), rtol=1e-5, atol=1e-7)

@@ -201,26 +201,27 @@ def test_decode_scratch_of_exactly_the_reported_size(lib, heads, shape):
 
 @functools.lru_cache(maxsize=None)
 def _router_problem(n, k):
+    import router_gemm_ref as rr
     from oracle import gemm as orc
 
     g = torch.Generator().manual_seed(10086)
     x = torch.randn(257, k, generator=g).bfloat16()
     w = torch.randn(n, k, generator=g)
     wh, wl = orc.split_weight(w, 1 / 256)
-    return x, wh, wl, orc.two_plane(x, wh, wl, 1 / 256), wh.cuda(), wl.cuda()
+    return x, wh, wl, rr.ref64(x, wh, wl, 1 / 256), wh.cuda(), wl.cuda()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m", [16, 17, 32, 33, 256, 257])
 def test_router_gemm_split_flag_of_exactly_the_planned_size(lib, m):
     """The op with a caller's split_flag of exactly the planned rows x row stride (flat up to 256 tokens, 2-D above) between two
-    guard bands, at the edges of the tile ladder: the fp32 bar against the two-plane oracle, flags zero after the call, guards
-    untouched."""
+    guard bands, at the edges of the tile ladder: the derived fp32 bar against the two-plane statement (tests/router_gemm_ref.py),
+    flags zero after the call, guards untouched."""
     import hpc
-    from utils import allclose
+    import router_gemm_ref as rr
 
     n, k = 192, 4096
-    x, _, _, exact, whd, wld = _router_problem(n, k)
+    x, _, _, (r, big_a), whd, wld = _router_problem(n, k)
     splits, rows, ld = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     assert lib.hpc_gemm_bf16xfp32_plan(m, n, k, 1, ctypes.byref(splits), ctypes.byref(rows), ctypes.byref(ld)) == 0
     print("m", m, "splits", splits.value, "counter rows", rows.value, "row stride", ld.value)
@@ -234,5 +235,5 @@ def test_router_gemm_split_flag_of_exactly_the_planned_size(lib, m):
     my = hpc.gemm_bf16xfp32(x[:m].cuda(), whd, wld, 1 / 256, True, True, flag)
     torch.cuda.synchronize()
     assert _guards_untouched(buf, nbytes)
-    assert allclose(exact[:m], my.cpu(), rtol=1e-4, atol=2e-3)
+    assert rr.close(my.cpu(), r[:m], big_a[:m], f"m {m}")
     assert int(flag.abs().sum()) == 0

@@ -37,7 +37,6 @@
 #include <type_traits>
 
 #include "attention_decode_mla_route.h"
-#include "attention_decode_mla_sparse_route.h"
 #include "mla_fp8_format.h"
 #include "hpc_amd.h"
 #include "hpc_common.h"
@@ -457,90 +456,121 @@ __global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const A
 }  // namespace mla
 }  // namespace hpc
 
+// ---- host side: dense and token-sparse share the route (mla_route() of attention_decode_mla_route.h), the plan sequence and
+// the launcher; the form is the template argument kSparse, and the list's checks and members stand beside the shared ones -------
 namespace {
 int mla_current_cu_count() {
   int dev = 0;
   return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
 }
-}  // namespace
 
-// What a call of hpc_attention_decode_mla_bf16_async with this `splits_wanted` runs with and needs: mla_route()
-// (attention_decode_mla_route.h).  num_cu <= 0: the current device's (256 without a device).
-extern "C" int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int num_head, int splits_wanted, int num_cu,
-                                             int* splits, int* max_splits, int64_t* workspace_bytes) {
-  if (!splits || !max_splits || !workspace_bytes) return HPC_ERR_INVALID;
-  // refusals first, on the host alone; only a call that leaves both the split count and the CU count open asks the device
-  hpc::MlaRoute r = hpc::mla_route(num_batch, num_seq_q, num_head, splits_wanted, num_cu > 0 ? num_cu : 256);
+// Both plan entries: refusals first, on the host alone; only a call that leaves both the split count and the CU count open asks
+// the device.  num_cu <= 0: the current device's (256 without a device).
+hpc::MlaRoute mla_plan_route(int num_batch, int num_seq_q, int num_head, bool sparse, int topk, int splits_wanted, int num_cu) {
+  hpc::MlaRoute r = hpc::mla_route(num_batch, num_seq_q, num_head, sparse, topk, splits_wanted, num_cu > 0 ? num_cu : 256);
   if (r.code == HPC_OK && num_cu <= 0 && splits_wanted == 0 && num_batch > 0)
-    r = hpc::mla_route(num_batch, num_seq_q, num_head, 0, mla_current_cu_count());
-  *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes;
-  return r.code;
+    r = hpc::mla_route(num_batch, num_seq_q, num_head, sparse, topk, 0, mla_current_cu_count());
+  return r;
 }
 
-namespace {
-// Both launchers: the checks, the route and the launches.  What a valid cache is - its page size, its strides in the kind's
-// units (bf16 elements or FP8 bytes) and its alignment - is mla_cache_check() of mla_cache.h.
-template <bool kFp8>
-int mla_decode_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr, const int* block_ids_ptr,
-                      const int* num_seq_kvcache_ptr, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
-                      int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale, int new_kv_included, int splits,
-                      void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
+// the arguments of the four launchers, in the sparse entries' order; dense: indices null, topk and num_blocks 0
+struct MlaDecodeCall {
+  void* out;
+  float* lse;
+  const void* q;
+  const void* ckv;
+  const int* block_ids;
+  const int* num_seq_kvcache;
+  const int* indices;
+  int num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks;
+  int64_t ckv_block_stride, ckv_token_stride;  // in the kind's units: bf16 elements or FP8 bytes
+  float softmax_scale;
+  int new_kv_included, splits;
+  void* workspace;
+  int64_t workspace_bytes;
+  hipStream_t stream;
+};
+
+// All four launchers: the checks, the route and the launches.  What a valid cache is - its page size, its strides in the kind's
+// units and its alignment - is mla_cache_check() of mla_cache.h.
+template <bool kFp8, bool kSparse>
+int mla_decode_launch(const MlaDecodeCall& c) {
   using namespace hpc::mla;
   constexpr hpc::MlaCacheKind kind = kFp8 ? hpc::kMlaCacheFp8 : hpc::kMlaCacheBf16;
-  if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr) return HPC_ERR_INVALID;
+  if (!c.out || !c.q || !c.ckv || !c.block_ids || !c.num_seq_kvcache || (kSparse && !c.indices)) return HPC_ERR_INVALID;
   // the cache's invalid argument (a negative block stride) is refused here with the others, what it does not support behind
   // the shapes: a call with two faults keeps the code of the earlier check
   const hpc::MlaCacheCheck cache =
-      hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_ptr), block_size, ckv_block_stride, ckv_token_stride);
-  if (splits < 0 || max_blocks < 0 || cache.code == HPC_ERR_INVALID) return HPC_ERR_INVALID;
+      hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(c.ckv), c.block_size, c.ckv_block_stride, c.ckv_token_stride);
+  if (c.splits < 0 || c.max_blocks < 0 || (kSparse && c.num_blocks < 0) || cache.code == HPC_ERR_INVALID)
+    return HPC_ERR_INVALID;
   // the split count is the caller's, or with 0 the route's for this device; shapes are refused before the device is asked
-  const hpc::MlaRoute shape = hpc::mla_route(num_batch, num_seq_q, num_head, splits > 0 ? splits : 1, 256);
+  const hpc::MlaRoute shape =
+      hpc::mla_route(c.num_batch, c.num_seq_q, c.num_head, kSparse, c.topk, c.splits > 0 ? c.splits : 1, 256);
   if (shape.code != HPC_OK) return shape.code;
   if (cache.code != HPC_OK) return cache.code;
-  if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(q_ptr) & 15) return HPC_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3)) return HPC_ERR_UNSUPPORTED;
-  if (num_batch == 0) return HPC_OK;
-  if (max_blocks == 0) return HPC_ERR_INVALID;
-  const hpc::MlaRoute r = splits > 0 ? shape : hpc::mla_route(num_batch, num_seq_q, num_head, 0, mla_current_cu_count());
+  if (static_cast<int64_t>(c.max_blocks) * c.block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(c.q) & 15) return HPC_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(c.out) & 7) || (reinterpret_cast<uintptr_t>(c.lse) & 3) ||
+      (kSparse && (reinterpret_cast<uintptr_t>(c.indices) & 3)))
+    return HPC_ERR_UNSUPPORTED;
+  if (c.num_batch == 0) return HPC_OK;
+  if (c.max_blocks == 0) return HPC_ERR_INVALID;
+  const hpc::MlaRoute r =
+      c.splits > 0 ? shape : hpc::mla_route(c.num_batch, c.num_seq_q, c.num_head, kSparse, c.topk, 0, mla_current_cu_count());
   if (r.code != HPC_OK) return r.code;
   if (r.splits > 1) {
-    if (!workspace_ptr || workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace_ptr) & 15) return HPC_ERR_UNSUPPORTED;
+    if (!c.workspace || c.workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(c.workspace) & 15) return HPC_ERR_UNSUPPORTED;
   }
-  Args a;
-  a.q = static_cast<const uint8_t*>(q_ptr);
-  a.ckv = static_cast<const uint8_t*>(ckv_ptr);
-  a.block_ids = block_ids_ptr;
-  a.num_seq = num_seq_kvcache_ptr;
-  a.out = static_cast<uint16_t*>(out_ptr);
-  a.lse = lse_ptr;
-  a.ws_o = static_cast<float*>(workspace_ptr);
-  a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
-  a.block_stride_bytes = ckv_block_stride * kind.unit;
-  a.token_stride_bytes = ckv_token_stride * kind.unit;
-  a.total_rows = static_cast<int64_t>(num_batch) * r.rows;
-  a.num_head = num_head;
-  a.num_seq_q = num_seq_q;
+  ArgsOf<kSparse> a;
+  a.q = static_cast<const uint8_t*>(c.q);
+  a.ckv = static_cast<const uint8_t*>(c.ckv);
+  a.block_ids = c.block_ids;
+  a.num_seq = c.num_seq_kvcache;
+  a.out = static_cast<uint16_t*>(c.out);
+  a.lse = c.lse;
+  a.ws_o = static_cast<float*>(c.workspace);
+  a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(c.workspace) + r.ml_offset);
+  a.block_stride_bytes = c.ckv_block_stride * kind.unit;
+  a.token_stride_bytes = c.ckv_token_stride * kind.unit;
+  a.total_rows = r.total_rows;
+  a.num_head = c.num_head;
+  a.num_seq_q = c.num_seq_q;
   a.rows = r.rows;
   a.row_tiles = r.row_tiles;
   a.splits = r.splits;
-  a.page_shift = hpc::mla_page_shift(block_size);
-  a.max_blocks = max_blocks;
-  a.new_kv_included = new_kv_included ? 1 : 0;
-  a.scale_log2 = softmax_scale * kLog2e;
+  a.page_shift = hpc::mla_page_shift(c.block_size);
+  a.max_blocks = c.max_blocks;
+  a.new_kv_included = c.new_kv_included ? 1 : 0;
+  a.scale_log2 = c.softmax_scale * kLog2e;
+  if constexpr (kSparse) {
+    a.indices = c.indices;
+    a.topk = c.topk;
+    a.plen = r.plen;
+    a.num_blocks = c.num_blocks;
+  }
   if (r.narrow)
-    attention_decode_mla_kernel<true, kFp8, false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<true, kFp8, kSparse><<<dim3(r.grid), kThreads, 0, c.stream>>>(a);
   else
-    attention_decode_mla_kernel<false, kFp8, false><<<dim3(r.grid), kThreads, 0, stream>>>(a);
+    attention_decode_mla_kernel<false, kFp8, kSparse><<<dim3(r.grid), kThreads, 0, c.stream>>>(a);
   HPC_CHECK_LAUNCH();
   if (r.splits > 1) {
-    attention_decode_mla_merge_kernel<false><<<dim3(r.merge_grid), 128, 0, stream>>>(a);
+    attention_decode_mla_merge_kernel<kSparse><<<dim3(r.merge_grid), 128, 0, c.stream>>>(a);
     HPC_CHECK_LAUNCH();
   }
   return HPC_OK;
 }
 }  // namespace
+
+// What a call of hpc_attention_decode_mla_{bf16,fp8}_async with this `splits_wanted` runs with and needs
+extern "C" int hpc_attention_decode_mla_plan(int num_batch, int num_seq_q, int num_head, int splits_wanted, int num_cu,
+                                             int* splits, int* max_splits, int64_t* workspace_bytes) {
+  if (!splits || !max_splits || !workspace_bytes) return HPC_ERR_INVALID;
+  const hpc::MlaRoute r = mla_plan_route(num_batch, num_seq_q, num_head, false, 0, splits_wanted, num_cu);
+  *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes;
+  return r.code;
+}
 
 extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
                                                    const int* block_ids_ptr, const int* num_seq_kvcache_ptr, int num_batch,
@@ -548,9 +578,9 @@ extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr
                                                    int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                    int new_kv_included, int splits, void* workspace_ptr,
                                                    int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<false>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, num_batch, num_seq_q,
-                                  num_head, block_size, max_blocks, ckv_block_stride, ckv_token_stride, softmax_scale,
-                                  new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+  return mla_decode_launch<false, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, num_batch,
+                                          num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride, ckv_token_stride,
+                                          softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes, stream});
 }
 
 // the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
@@ -560,96 +590,25 @@ extern "C" int hpc_attention_decode_mla_fp8_async(void* out_ptr, float* lse_ptr,
                                                   int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                   float softmax_scale, int new_kv_included, int splits, void* workspace_ptr,
                                                   int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<true>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, num_batch, num_seq_q,
-                                 num_head, block_size, max_blocks, ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale,
-                                 new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+  return mla_decode_launch<true, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, num_batch,
+                                         num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride_bytes,
+                                         ckv_token_stride_bytes, softmax_scale, new_kv_included, splits, workspace_ptr,
+                                         workspace_bytes, stream});
 }
 
 // ---- the token-sparse form: each q row attends to the tokens its list names --------------------------------------------------
-// What a call of hpc_attention_decode_mla_sparse_{bf16,fp8}_async with this `splits_wanted` runs with and needs:
-// mla_sparse_route() (attention_decode_mla_sparse_route.h).  *splits is the EFFECTIVE piece count; grid (workgroups of the
-// attention launch) and narrow (1: the 16-head form) may be null.  num_cu <= 0: the current device's (256 without a device).
+// What a call of hpc_attention_decode_mla_sparse_{bf16,fp8}_async with this `splits_wanted` runs with and needs.  *splits is
+// the EFFECTIVE piece count; grid (workgroups of the attention launch) and narrow (1: the 16-head form) may be null.
 extern "C" int hpc_attention_decode_mla_sparse_plan(int num_batch, int num_seq_q, int num_head, int topk, int splits_wanted,
                                                     int num_cu, int* splits, int* max_splits, int64_t* workspace_bytes,
                                                     int* grid, int* narrow) {
   if (!splits || !max_splits || !workspace_bytes) return HPC_ERR_INVALID;
-  hpc::MlaSparseRoute r = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, splits_wanted, num_cu > 0 ? num_cu : 256);
-  if (r.code == HPC_OK && num_cu <= 0 && splits_wanted == 0 && num_batch > 0)
-    r = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, 0, mla_current_cu_count());
+  const hpc::MlaRoute r = mla_plan_route(num_batch, num_seq_q, num_head, true, topk, splits_wanted, num_cu);
   *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes;
   if (grid) *grid = r.grid;
   if (narrow) *narrow = r.narrow;
   return r.code;
 }
-
-namespace {
-// Both sparse launchers: the dense launchers' checks in their order, with the list's beside them.
-template <bool kFp8>
-int mla_sparse_launch(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr, const int* block_ids_ptr,
-                      const int* num_seq_kvcache_ptr, const int* indices_ptr, int num_batch, int num_seq_q, int num_head, int topk,
-                      int block_size, int max_blocks, int num_blocks, int64_t ckv_block_stride, int64_t ckv_token_stride,
-                      float softmax_scale, int new_kv_included, int splits, void* workspace_ptr, int64_t workspace_bytes,
-                      hipStream_t stream) {
-  using namespace hpc::mla;
-  constexpr hpc::MlaCacheKind kind = kFp8 ? hpc::kMlaCacheFp8 : hpc::kMlaCacheBf16;
-  if (!out_ptr || !q_ptr || !ckv_ptr || !block_ids_ptr || !num_seq_kvcache_ptr || !indices_ptr) return HPC_ERR_INVALID;
-  const hpc::MlaCacheCheck cache =
-      hpc::mla_cache_check(kind, reinterpret_cast<uintptr_t>(ckv_ptr), block_size, ckv_block_stride, ckv_token_stride);
-  if (splits < 0 || max_blocks < 0 || num_blocks < 0 || cache.code == HPC_ERR_INVALID) return HPC_ERR_INVALID;
-  const hpc::MlaSparseRoute shape = hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, splits > 0 ? splits : 1, 256);
-  if (shape.code != HPC_OK) return shape.code;
-  if (cache.code != HPC_OK) return cache.code;
-  if (static_cast<int64_t>(max_blocks) * block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(q_ptr) & 15) return HPC_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(out_ptr) & 7) || (reinterpret_cast<uintptr_t>(lse_ptr) & 3) ||
-      (reinterpret_cast<uintptr_t>(indices_ptr) & 3))
-    return HPC_ERR_UNSUPPORTED;
-  if (num_batch == 0) return HPC_OK;
-  if (max_blocks == 0) return HPC_ERR_INVALID;
-  const hpc::MlaSparseRoute r =
-      splits > 0 ? shape : hpc::mla_sparse_route(num_batch, num_seq_q, num_head, topk, 0, mla_current_cu_count());
-  if (r.code != HPC_OK) return r.code;
-  if (r.splits > 1) {
-    if (!workspace_ptr || workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(workspace_ptr) & 15) return HPC_ERR_UNSUPPORTED;
-  }
-  SparseArgs a;
-  a.q = static_cast<const uint8_t*>(q_ptr);
-  a.ckv = static_cast<const uint8_t*>(ckv_ptr);
-  a.block_ids = block_ids_ptr;
-  a.num_seq = num_seq_kvcache_ptr;
-  a.out = static_cast<uint16_t*>(out_ptr);
-  a.lse = lse_ptr;
-  a.ws_o = static_cast<float*>(workspace_ptr);
-  a.ws_ml = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace_ptr) + r.ml_offset);
-  a.block_stride_bytes = ckv_block_stride * kind.unit;
-  a.token_stride_bytes = ckv_token_stride * kind.unit;
-  a.total_rows = static_cast<int64_t>(num_batch) * num_seq_q * r.rows;
-  a.num_head = num_head;
-  a.num_seq_q = num_seq_q;
-  a.rows = r.rows;
-  a.row_tiles = r.head_tiles;
-  a.splits = r.splits;
-  a.page_shift = hpc::mla_page_shift(block_size);
-  a.max_blocks = max_blocks;
-  a.new_kv_included = new_kv_included ? 1 : 0;
-  a.scale_log2 = softmax_scale * kLog2e;
-  a.indices = indices_ptr;
-  a.topk = topk;
-  a.plen = r.plen;
-  a.num_blocks = num_blocks;
-  if (r.narrow)
-    attention_decode_mla_kernel<true, kFp8, true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
-  else
-    attention_decode_mla_kernel<false, kFp8, true><<<dim3(r.grid), kThreads, 0, stream>>>(a);
-  HPC_CHECK_LAUNCH();
-  if (r.splits > 1) {
-    attention_decode_mla_merge_kernel<true><<<dim3(r.merge_grid), 128, 0, stream>>>(a);
-    HPC_CHECK_LAUNCH();
-  }
-  return HPC_OK;
-}
-}  // namespace
 
 extern "C" int hpc_attention_decode_mla_sparse_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
                                                           const int* block_ids_ptr, const int* num_seq_kvcache_ptr,
@@ -658,9 +617,10 @@ extern "C" int hpc_attention_decode_mla_sparse_bf16_async(void* out_ptr, float* 
                                                           int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                           int new_kv_included, int splits, void* workspace_ptr,
                                                           int64_t workspace_bytes, hipStream_t stream) {
-  return mla_sparse_launch<false>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, num_batch,
-                                  num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride,
-                                  softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes, stream);
+  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr,
+                                         num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride,
+                                         ckv_token_stride, softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes,
+                                         stream});
 }
 
 // the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
@@ -671,8 +631,8 @@ extern "C" int hpc_attention_decode_mla_sparse_fp8_async(void* out_ptr, float* l
                                                          int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                          float softmax_scale, int new_kv_included, int splits,
                                                          void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
-  return mla_sparse_launch<true>(out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, num_batch,
-                                 num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride_bytes,
-                                 ckv_token_stride_bytes, softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes,
-                                 stream);
+  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr,
+                                        num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks,
+                                        ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale, new_kv_included, splits,
+                                        workspace_ptr, workspace_bytes, stream});
 }

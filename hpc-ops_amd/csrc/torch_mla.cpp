@@ -9,7 +9,8 @@
 // difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
 // the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
 // kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  attention_decode_mla_sparse_{bf16,fp8} are the decode
-// attention over a list of token positions per q row (the same kernel source, its kSparse form).  Either side of the decode
+// attention over a list of token positions per q row (the same kernel source, its kSparse form, and here the same body as the
+// dense ops: decode_mla<kFp8>, the list null or given).  Either side of the decode
 // attention the two absorb matmuls, absorb_q and unabsorb_o (csrc/mla_absorb.hip).  No kernels here.
 #include "byte_span.h"
 #include "mla_cache.h"
@@ -85,12 +86,18 @@ void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, 
               t.sizes());
 }
 
+// ---- attention_decode_mla_{bf16,fp8} and attention_decode_mla_sparse_{bf16,fp8}: one body, `indices` null for the dense ops -----
+// sparse: each q row attends to the tokens its list names (tests/mla_sparse_ref.py); the list's checks stand beside the dense
+// ones.  Nothing here reads the values of num_seq_kvcache, block_ids or indices.  With `output` (and `output_lse` where an lse
+// is wanted) given nothing is allocated per call beyond the cached scratch.
 template <bool kFp8>
-std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
-                                                        const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
-                                                        bool new_kv_included, const c10::optional<at::Tensor>& output,
-                                                        const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
-  const char* op = kFp8 ? "attention_decode_mla_fp8" : "attention_decode_mla_bf16";
+std::tuple<at::Tensor, at::Tensor> decode_mla(const at::Tensor& q, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
+                                              const at::Tensor& num_seq_kvcache, const at::Tensor* indices, double softmax_scale,
+                                              int64_t mtp, bool new_kv_included, const c10::optional<at::Tensor>& output,
+                                              const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
+  const bool sparse = indices != nullptr;
+  const char* op = sparse ? (kFp8 ? "attention_decode_mla_sparse_fp8" : "attention_decode_mla_sparse_bf16")
+                          : (kFp8 ? "attention_decode_mla_fp8" : "attention_decode_mla_bf16");
   cuda_contig(q, "q");
   cuda_contig(block_ids, "block_ids");
   cuda_contig(num_seq_kvcache, "num_seq_kvcache");
@@ -109,9 +116,16 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, con
   TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
   TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
   TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
+  int64_t topk = 0;
+  if (sparse) {
+    check_table(*indices, "indices", q, at::kInt, {b * sq, -1});
+    topk = indices->size(1);
+    TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [num_batch * (mtp + 1), topk] with 1 <= topk <= 65536, got topk = ", topk);
+  }
   check_cache(ckv_cache, kCache<kFp8>);
   const int64_t page = ckv_cache.size(1);
   TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
+  TORCH_CHECK(!sparse || ckv_cache.size(0) <= INT32_MAX, "sizes beyond int32");
   TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
   at::Tensor out = out_or_new(output, q, {b * sq, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
   const bool want_lse = return_lse || output_lse.has_value();
@@ -120,26 +134,46 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, con
 
   int s = 0, max_splits = 0;
   int64_t ws_bytes = 0;
-  const int rc_plan = hpc_attention_decode_mla_plan(i32(b), i32(sq), i32(h), i32(std::min<int64_t>(splits, INT32_MAX)),
-                                                    b > 0 ? hpc_get_cu_count(q.device().index()) : 256, &s, &max_splits, &ws_bytes);
-  TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a request may be cut into");
+  const int wanted = i32(std::min<int64_t>(splits, INT32_MAX)), cus = b > 0 ? hpc_get_cu_count(q.device().index()) : 256;
+  const int rc_plan =
+      sparse ? hpc_attention_decode_mla_sparse_plan(i32(b), i32(sq), i32(h), i32(topk), wanted, cus, &s, &max_splits, &ws_bytes,
+                                                    nullptr, nullptr)
+             : hpc_attention_decode_mla_plan(i32(b), i32(sq), i32(h), wanted, cus, &s, &max_splits, &ws_bytes);
+  TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a ", sparse ? "list" : "request",
+              " may be cut into");
   HPC_LAUNCH_CHECK(rc_plan, op);
   if (b == 0) return {out, lse};
   TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
   at::Tensor ws;
   if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: an unwritten piece is never read
-  const int rc = (kFp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
-      ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache),
-      static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(num_seq_kvcache.data_ptr()), i32(b), i32(sq), i32(h),
-      i32(page), i32(block_ids.size(1)), ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale),
-      new_kv_included ? 1 : 0, s, s > 1 ? ws.data_ptr() : nullptr, ws_bytes, stream_of(q));
+  float* lse_ptr = want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr;
+  const int* bid_ptr = static_cast<const int*>(block_ids.data_ptr());
+  const int* len_ptr = static_cast<const int*>(num_seq_kvcache.data_ptr());
+  void* ws_ptr = s > 1 ? ws.data_ptr() : nullptr;
+  const float scale = static_cast<float>(softmax_scale);
+  // sparse: the launcher is given the effective count - cutting the list into that many pieces gives the same piece length again
+  const int rc =
+      sparse ? (kFp8 ? hpc_attention_decode_mla_sparse_fp8_async : hpc_attention_decode_mla_sparse_bf16_async)(
+                   ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), bid_ptr, len_ptr, static_cast<const int*>(indices->data_ptr()), i32(b),
+                   i32(sq), i32(h), i32(topk), i32(page), i32(block_ids.size(1)), i32(ckv_cache.size(0)), ckv_cache.stride(0),
+                   ckv_cache.stride(1), scale, new_kv_included ? 1 : 0, s, ws_ptr, ws_bytes, stream_of(q))
+             : (kFp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
+                   ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), bid_ptr, len_ptr, i32(b), i32(sq), i32(h), i32(page),
+                   i32(block_ids.size(1)), ckv_cache.stride(0), ckv_cache.stride(1), scale, new_kv_included ? 1 : 0, s, ws_ptr,
+                   ws_bytes, stream_of(q));
   HPC_LAUNCH_CHECK(rc, op);
   return {out, lse};
 }
 
-// ---- attention_decode_mla_sparse_{bf16,fp8}: each q row attends to the tokens its list names; tests/mla_sparse_ref.py ----------
-// The dense op's checks with the list's beside them; nothing here reads the values of num_seq_kvcache, block_ids or indices.  With
-// `output` (and `output_lse` where an lse is wanted) given nothing is allocated per call beyond the cached scratch.
+template <bool kFp8>
+std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
+                                                        const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
+                                                        bool new_kv_included, const c10::optional<at::Tensor>& output,
+                                                        const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
+  return decode_mla<kFp8>(q, ckv_cache, block_ids, num_seq_kvcache, nullptr, softmax_scale, mtp, new_kv_included, output, output_lse,
+                          return_lse, splits);
+}
+
 template <bool kFp8>
 std::tuple<at::Tensor, at::Tensor> attention_decode_mla_sparse(const at::Tensor& q, const at::Tensor& ckv_cache,
                                                                const at::Tensor& block_ids, const at::Tensor& num_seq_kvcache,
@@ -147,59 +181,8 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_sparse(const at::Tensor&
                                                                bool new_kv_included, const c10::optional<at::Tensor>& output,
                                                                const c10::optional<at::Tensor>& output_lse, bool return_lse,
                                                                int64_t splits) {
-  const char* op = kFp8 ? "attention_decode_mla_sparse_fp8" : "attention_decode_mla_sparse_bf16";
-  cuda_contig(q, "q");
-  cuda_contig(block_ids, "block_ids");
-  cuda_contig(num_seq_kvcache, "num_seq_kvcache");
-  TORCH_CHECK(ckv_cache.is_cuda(), "ckv_cache tensor must be cuda");
-  TORCH_CHECK(ckv_cache.device() == q.device() && block_ids.device() == q.device() && num_seq_kvcache.device() == q.device(),
-              "ckv_cache, block_ids and num_seq_kvcache must be on q's device");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
-  TORCH_CHECK(block_ids.scalar_type() == at::kInt, "block_ids dtype must be int32");
-  TORCH_CHECK(num_seq_kvcache.scalar_type() == at::kInt, "num_seq_kvcache dtype must be int32");
-  TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
-  const int64_t sq = mtp + 1;
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [num_batch * num_seq_q, num_head, 576]");
-  TORCH_CHECK(block_ids.dim() == 2, "block_ids must be [num_batch, max_blocks]");
-  TORCH_CHECK(num_seq_kvcache.dim() == 1, "num_seq_kvcache must be [num_batch]");
-  const int64_t b = num_seq_kvcache.size(0), h = q.size(1);
-  TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
-  TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
-  TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
-  check_table(indices, "indices", q, at::kInt, {b * sq, -1});
-  const int64_t topk = indices.size(1);
-  TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [num_batch * (mtp + 1), topk] with 1 <= topk <= 65536, got topk = ", topk);
-  check_cache(ckv_cache, kCache<kFp8>);
-  const int64_t page = ckv_cache.size(1);
-  TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
-  TORCH_CHECK(ckv_cache.size(0) <= INT32_MAX, "sizes beyond int32");
-  TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
-  at::Tensor out = out_or_new(output, q, {b * sq, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
-  const bool want_lse = return_lse || output_lse.has_value();
-  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {b * sq, h}, at::kFloat, "output_lse", kOnInputDevice)
-                            : at::empty({0}, q.options().dtype(at::kFloat));
-
-  int s = 0, max_splits = 0;
-  int64_t ws_bytes = 0;
-  const int rc_plan =
-      hpc_attention_decode_mla_sparse_plan(i32(b), i32(sq), i32(h), i32(topk), i32(std::min<int64_t>(splits, INT32_MAX)),
-                                           b > 0 ? hpc_get_cu_count(q.device().index()) : 256, &s, &max_splits, &ws_bytes,
-                                           nullptr, nullptr);
-  TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a list may be cut into");
-  HPC_LAUNCH_CHECK(rc_plan, op);
-  if (b == 0) return {out, lse};
-  TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
-  at::Tensor ws;
-  if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: every launched piece writes all of its rows
-  // the launcher is given the effective count: cutting the list into that many pieces gives the same piece length again
-  const int rc = (kFp8 ? hpc_attention_decode_mla_sparse_fp8_async : hpc_attention_decode_mla_sparse_bf16_async)(
-      ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache),
-      static_cast<const int*>(block_ids.data_ptr()), static_cast<const int*>(num_seq_kvcache.data_ptr()),
-      static_cast<const int*>(indices.data_ptr()), i32(b), i32(sq), i32(h), i32(topk), i32(page), i32(block_ids.size(1)),
-      i32(ckv_cache.size(0)), ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale), new_kv_included ? 1 : 0,
-      s, s > 1 ? ws.data_ptr() : nullptr, ws_bytes, stream_of(q));
-  HPC_LAUNCH_CHECK(rc, op);
-  return {out, lse};
+  return decode_mla<kFp8>(q, ckv_cache, block_ids, num_seq_kvcache, &indices, softmax_scale, mtp, new_kv_included, output,
+                          output_lse, return_lse, splits);
 }
 
 // ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------

@@ -323,6 +323,13 @@ def _attention_with_kvcache_prefill_bf16_fake(q, kcache, vcache, cu_seqlens_q, b
                                                          device=q.device)
 
 
+def _decode_mla_result(out, lse, output, output_lse, return_lse):
+    out = out if output is None else output
+    if not (return_lse or output_lse is not None):
+        return out
+    return out, (lse if output_lse is None else output_lse)
+
+
 def attention_decode_mla_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,
                               softmax_scale: float, mtp: int = 0, new_kv_included: bool = False, *, output: Tensor = None,
                               output_lse: Tensor = None, return_lse: bool = False, splits: int = 0):
@@ -371,10 +378,7 @@ def attention_decode_mla_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, n
     out, lse = torch.ops.hpc_mla.attention_decode_mla_bf16(q, ckv_cache, block_ids, num_seq_kvcache, float(softmax_scale),
                                                            int(mtp), bool(new_kv_included), output, output_lse,
                                                            bool(return_lse), int(splits))
-    out = out if output is None else output
-    if not (return_lse or output_lse is not None):
-        return out
-    return out, (lse if output_lse is None else output_lse)
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
 
 
 @torch.library.register_fake("hpc_mla::attention_decode_mla_bf16")
@@ -424,20 +428,10 @@ def attention_decode_mla_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, nu
     out, lse = torch.ops.hpc_mla.attention_decode_mla_fp8(q, ckv_cache, block_ids, num_seq_kvcache, float(softmax_scale),
                                                           int(mtp), bool(new_kv_included), output, output_lse,
                                                           bool(return_lse), int(splits))
-    out = out if output is None else output
-    if not (return_lse or output_lse is not None):
-        return out
-    return out, (lse if output_lse is None else output_lse)
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
 
 
 torch.library.register_fake("hpc_mla::attention_decode_mla_fp8")(_attention_decode_mla_bf16_fake)
-
-
-def _decode_mla_result(out, lse, output, output_lse, return_lse):
-    out = out if output is None else output
-    if not (return_lse or output_lse is not None):
-        return out
-    return out, (lse if output_lse is None else output_lse)
 
 
 def attention_decode_mla_sparse_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seq_kvcache: Tensor,

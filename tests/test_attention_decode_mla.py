@@ -215,11 +215,13 @@ def test_cabi_refuses_a_small_workspace_and_takes_an_empty_batch(lib):
 
 
 def _route(B, sq, H, splits_wanted, cus):
-    """the arithmetic of csrc/attention_decode_mla_route.h, restated"""
+    """the arithmetic of mla_route() (csrc/attention_decode_mla_route.h) in its dense form, restated"""
     rows = sq * H
     tiles = -(-rows // 64)
     W = B * tiles
-    if splits_wanted:
+    if B == 0:  # nothing to launch: one piece, no scratch, whatever was asked for
+        s = 1
+    elif splits_wanted:
         s = splits_wanted
     else:
         s = 1 if W >= cus else min(MAX_SPLITS, -(-2 * cus // W))
@@ -228,7 +230,16 @@ def _route(B, sq, H, splits_wanted, cus):
 
 
 @pytest.mark.parametrize("B,sq,H,cus", [(64, 1, 16, 256), (64, 1, 128, 256), (8, 2, 128, 256), (1, 1, 16, 256), (3, 4, 48, 304),
-                                        (256, 1, 16, 256), (255, 1, 64, 256), (7, 3, 32, 80), (130, 2, 128, 256)])
+                                        (256, 1, 16, 256), (255, 1, 64, 256), (7, 3, 32, 80), (130, 2, 128, 256),
+                                        # W one below, at and one above the CU count (one row tile per request; W = 256 on 256 CUs is in the line above)
+                                        (255, 1, 16, 256), (257, 1, 16, 256), (79, 1, 48, 80), (80, 1, 48, 80), (81, 1, 48, 80),
+                                        (303, 2, 32, 304), (304, 2, 32, 304), (305, 2, 32, 304),
+                                        # two row tiles per request: the nearest W either side of the CU count, and at it
+                                        (151, 2, 64, 304), (152, 2, 64, 304), (153, 2, 64, 304),
+                                        # 16 heads: one 16-row block at mtp 0 (the narrow form), two at mtp 1 (not narrow)
+                                        (5, 1, 16, 256), (5, 2, 16, 256),
+                                        # an empty batch
+                                        (0, 1, 16, 256), (0, 3, 128, 80)])
 def test_plan_is_the_route(lib, B, sq, H, cus):
     for wanted in (0, 1, 2, 3, 8, 64):
         rc, s, mx, ws = plan(lib, B, sq, H, wanted, cus)

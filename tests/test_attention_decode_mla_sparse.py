@@ -283,7 +283,8 @@ def plan(lib, B, sq, H, topk, splits, cus):
 
 
 def _route(B, sq, H, topk, wanted, cus):
-    """the arithmetic of csrc/attention_decode_mla_sparse_route.h, restated: (effective pieces, scratch bytes, grid, narrow)"""
+    """the arithmetic of mla_route() (csrc/attention_decode_mla_route.h) in its sparse form, restated: (effective pieces, scratch
+    bytes, grid, narrow)"""
     head_tiles = -(-H // 64)
     W = B * sq * head_tiles
     tiles = -(-topk // 64)
@@ -297,7 +298,14 @@ def _route(B, sq, H, topk, wanted, cus):
 
 @pytest.mark.parametrize("B,sq,H,topk,cus", [(1, 1, 16, 2048, 256), (64, 1, 128, 2048, 256), (64, 1, 16, 2048, 256),
                                              (8, 2, 128, 2048, 256), (3, 4, 48, 65, 256), (5, 1, 32, 1, 304), (2, 2, 64, 320, 80),
-                                             (1, 1, 16, 65536, 256), (7, 3, 80, 1000, 256), (300, 1, 16, 64, 256)])
+                                             (1, 1, 16, 65536, 256), (7, 3, 80, 1000, 256), (300, 1, 16, 64, 256),
+                                             # W one below, at and one above the CU count
+                                             (255, 1, 16, 2048, 256), (256, 1, 16, 2048, 256), (257, 1, 16, 2048, 256),
+                                             (79, 1, 64, 320, 80), (80, 1, 64, 320, 80), (81, 1, 64, 320, 80),
+                                             (101, 3, 48, 1000, 304), (76, 2, 128, 2048, 304), (51, 3, 128, 1000, 305),
+                                             # one tile, two tiles, and one slot either side: the effective count is clamped
+                                             (3, 1, 16, 63, 256), (3, 1, 16, 64, 256), (3, 1, 16, 65, 256),
+                                             (3, 2, 128, 127, 256), (3, 2, 128, 128, 256), (3, 2, 128, 129, 256)])
 def test_plan_is_the_route(lib, B, sq, H, topk, cus):
     for wanted in (0, 1, 2, 3, 5, 8, 33, 64):
         rc, s, mx, ws, grid, narrow = plan(lib, B, sq, H, topk, wanted, cus)
@@ -324,6 +332,17 @@ def test_plan_examples(lib):
     assert plan(lib, 2, 1, 16, MAX_TOPK + 1, 1, 256)[0] == UNSUPPORTED and plan(lib, 2, 1, 16, MAX_TOPK, 1, 256)[0] == 0
     assert plan(lib, 2, 1, 24, 64, 1, 256)[0] == UNSUPPORTED and plan(lib, 2, 5, 16, 64, 1, 256)[0] == UNSUPPORTED
     assert plan(lib, 2, 1, 16, 64, MAX_SPLITS + 1, 256)[0] == INVALID and plan(lib, -1, 1, 16, 64, 1, 256)[0] == INVALID
+
+
+@pytest.mark.parametrize("B,H", [(1, 16), (3, 64), (5, 128), (64, 16), (300, 128)])
+def test_a_list_cut_evenly_plans_as_the_dense_op(lib, B, H):
+    """mtp 0 and a list of 65536 slots = 1024 tiles, which every count asked for here divides: the piece length is a whole
+    number of tiles, no piece is dropped, and a q row is a request - so the sparse plan is the dense one (one route behind both)"""
+    for wanted in (1, 2, 4, 8, 16, 32, 64):
+        s, mx, ws = c_int(-7), c_int(-7), c_int64(-7)
+        rc = lib.hpc_attention_decode_mla_plan(B, 1, H, wanted, 256, ctypes.byref(s), ctypes.byref(mx), ctypes.byref(ws))
+        assert rc == 0 and s.value == wanted
+        assert plan(lib, B, 1, H, MAX_TOPK, wanted, 256)[:4] == (0, s.value, mx.value, ws.value), wanted
 
 
 def call(lib, kind="bf16", *, out=4096, lse=4096, q=4096, ckv=4096, bid=4096, lens=4096, idx=4096, B=2, sq=1, H=16, topk=128, P=64,

@@ -9,7 +9,7 @@
 //            16 lanes, the codes are the project's 128-column quantiser (act_quant.h: bit for bit hpc_blockwise_fp8_quant_async
 //            on the row) and leave as one 8-byte store per lane, the scale as one 4-byte store per row.  The request and position
 //            of a row are mla_store.hip's: binary search in q_index, one page-table entry, every index checked against a host
-//            value before it is used.
+//            value before it is used.  Lookup, quantiser and store are mla_indexer_dev.h's, shared with mla_indexer_prep.hip.
 //   logits   a 132 B/token stream with one v_mfma_f32_16x16x128_f8f6f4 per 16 heads x 16 tokens: A = q (heads on the rows), B =
 //            keys straight from global memory (tokens on the columns, 32 contiguous bytes per lane, no LDS).  Lane (n, g) of the
 //            result holds heads 4 g .. 4 g + 3 of token n, so ReLU, the weight and the sum over a lane's heads stay in the lane -
@@ -26,6 +26,7 @@
 //            the threshold and the first `need` ties - so the list ascends and ties go to the smaller position.
 #include "act_quant.h"
 #include "hpc_common.h"
+#include "mla_indexer_dev.h"
 #include "mla_indexer_route.h"
 #include "ordered_key.h"
 #include "../../include/hpc_amd.h"
@@ -53,45 +54,15 @@ __global__ __launch_bounds__(kStoreThreads) void store_kernel(const StoreArgs a)
   u32x4 raw = u32x4{0u, 0u, 0u, 0u};
   if (in) raw = ld16(a.k + row * a.k_rs + 8 * sub);  // in flight before the lookup
 
-  // request and position of this row, as mla_store.hip: last b with q_index[b] <= row.  Nothing is stored for a row of no
-  // request, a token whose page the table does not hold, or whose page id is not a page.
-  bool store = false;
-  long cell = 0, scale_at = 0;
-  if (in) {
-    bool live = row < a.q_index[a.num_req];
-    int lo = 0, hi = a.num_req;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (a.q_index[mid + 1] <= row) lo = mid + 1; else hi = mid;
-    }
-    const int req = lo < a.num_req ? lo : a.num_req - 1;  // a q_index that does not ascend must not index past seqlen
-    const long pos = static_cast<long>(a.seqlen[req]) - (static_cast<long>(a.q_index[req + 1]) - row);
-    live = live && pos >= 0;
-    const long blk = pos >> a.page_shift;
-    if (live && blk < a.max_blocks) {
-      const int phys = a.block_ids[static_cast<long>(req) * a.max_blocks + blk];
-      store = phys >= 0 && phys < a.num_blocks;  // frameworks pad tables with -1
-      const long t = pos & ((1L << a.page_shift) - 1);
-      cell = phys * a.cache_bs + t * kIdxDim;
-      scale_at = phys * a.cache_bs + (static_cast<long>(kIdxDim) << a.page_shift) + 4 * t;
-    }
-  }
+  // request and position of this row and its cache cell with their guards: mla_indexer_dev.h
+  Cell cell{false, 0, 0};
+  if (in) cell = locate_cell(locate_row(a.q_index, a.seqlen, a.num_req, row), a.block_ids, a.page_shift, a.max_blocks, a.num_blocks, a.cache_bs);
   float v[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = bf16lo_to_f32(raw[i]);
-    v[2 * i + 1] = bf16hi_to_f32(raw[i]);
-  }
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
-#pragma unroll
-  for (int d = 1; d < kStoreLanes; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));  // every lane takes part
+  unpack8(raw, v);
+  const float amax = amax16(v);  // every lane takes part
   const float scale = e4m3_block_scale(amax), inv = e4m3_block_inv(scale);
-  if (!store) return;
-  *reinterpret_cast<u32x2*>(a.cache + cell + 8 * sub) =
-      u32x2{quant_4xe4m3(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv), quant_4xe4m3(v[4] * inv, v[5] * inv, v[6] * inv, v[7] * inv)};
-  if (sub == 0) *reinterpret_cast<float*>(a.cache + scale_at) = scale;
+  if (!cell.store) return;
+  store_key(a.cache, cell, sub, codes8(v, inv), scale);
 }
 
 // ---- logits -----------------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,83 @@
+// Device pieces the writers of the index-key cache share (mla_indexer.hip: store_kernel; mla_indexer_prep.hip: prep_kernel), stated
+// once: the request and position of a row, the cache cell of a token with its guards, the 16-lane abs-max, the 128-column
+// quantiser on a vector held as 8 columns per lane, and the store of a token's 128 + 4 bytes.  Internal, device only.
+#pragma once
+#include "act_quant.h"
+#include "hpc_common.h"
+#include "mla_indexer_route.h"
+
+namespace hpc {
+namespace mla_indexer {
+
+// Request and position of row `row`, as mla_store.hip: the last b with q_index[b] <= row, pos = seqlen[b] - (q_index[b + 1] -
+// row); live is false for a row at or past q_index[num_req] and for pos < 0 (a row of no request).  num_req >= 1.
+struct RowAt {
+  bool live;
+  int req;
+  long pos;
+};
+__device__ __forceinline__ RowAt locate_row(const int* q_index, const int* seqlen, int num_req, int row) {
+  bool live = row < q_index[num_req];
+  int lo = 0, hi = num_req;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (q_index[mid + 1] <= row) lo = mid + 1; else hi = mid;
+  }
+  const int req = lo < num_req ? lo : num_req - 1;  // a q_index that does not ascend must not index past seqlen
+  const long pos = static_cast<long>(seqlen[req]) - (static_cast<long>(q_index[req + 1]) - row);
+  live = live && pos >= 0;
+  return {live, req, pos};
+}
+
+// Where the token of `at` lies in the cache: nothing is stored for a row of no request, a token whose page the table does not
+// hold, or whose page id is not a page.  Every device value is checked against a host value before it reaches an address.
+struct Cell {
+  bool store;
+  long codes_at, scale_at;  // bytes from the cache's base
+};
+__device__ __forceinline__ Cell locate_cell(const RowAt& at, const int* block_ids, int page_shift, int max_blocks, int num_blocks,
+                                            long cache_bs) {
+  Cell c{false, 0, 0};
+  const long blk = at.pos >> page_shift;
+  if (at.live && blk < max_blocks) {
+    const int phys = block_ids[static_cast<long>(at.req) * max_blocks + blk];
+    c.store = phys >= 0 && phys < num_blocks;  // frameworks pad tables with -1
+    const long t = at.pos & ((1L << page_shift) - 1);
+    c.codes_at = phys * cache_bs + t * kIdxDim;
+    c.scale_at = phys * cache_bs + (static_cast<long>(kIdxDim) << page_shift) + 4 * t;
+  }
+  return c;
+}
+
+// 16 bytes of bf16 -> the lane's 8 columns
+__device__ __forceinline__ void unpack8(const u32x4 raw, float (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = bf16lo_to_f32(raw[i]);
+    v[2 * i + 1] = bf16hi_to_f32(raw[i]);
+  }
+}
+
+// abs-max of a vector of 128 columns held 8 per lane by 16 consecutive lanes: every lane of the wave takes part
+__device__ __forceinline__ float amax16(const float (&v)[8]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
+  return amax;
+}
+
+// the lane's 8 codes: the project's quantiser (act_quant.h) with the multiplier `inv`
+__device__ __forceinline__ u32x2 codes8(const float (&v)[8], float inv) {
+  return u32x2{quant_4xe4m3(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv), quant_4xe4m3(v[4] * inv, v[5] * inv, v[6] * inv, v[7] * inv)};
+}
+
+// the 128 + 4 bytes of a token: 8 bytes per lane, the scale from the vector's first lane
+__device__ __forceinline__ void store_key(uint8_t* cache, const Cell& c, int sub, u32x2 codes, float scale) {
+  *reinterpret_cast<u32x2*>(cache + c.codes_at + 8 * sub) = codes;
+  if (sub == 0) *reinterpret_cast<float*>(cache + c.scale_at) = scale;
+}
+
+}  // namespace mla_indexer
+}  // namespace hpc

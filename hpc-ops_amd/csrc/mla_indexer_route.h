@@ -1,7 +1,8 @@
 // The DSA lightning indexer (mla_indexer.hip), stated once: the paged index-key cache, the host rule for a cache a launcher
-// accepts, and the one route of the logits / top-k ops - the grid, the chunking of the context, the scratch of the fused call and
-// every refusal with its reason in words.  Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip,
-// hpc_mla_indexer_plan and the torch shim (torch_mla_indexer.cpp) all read it.
+// accepts, the one route of the logits / top-k ops - the grid, the chunking of the context, the scratch of the fused call and
+// every refusal with its reason in words - and the one host rule of the front end (mla_indexer_prep.hip) at the end.
+// Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip and mla_indexer_prep.hip, hpc_mla_indexer_plan
+// and the torch shim (torch_mla_indexer.cpp) all read it.
 //
 // The index-key cache.  Every token of every request has ONE index key of 128 columns, shared by all index heads: 128
 // float8_e4m3fn codes and one float32 scale, column d = fp32(code[d]) * scale, for any finite non-negative scale.  The cache is
@@ -100,6 +101,95 @@ static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, in
   const int64_t grid = static_cast<int64_t>(num_batch) * r.chunks;
   if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
   r.grid = static_cast<int>(grid);
+  return r;
+}
+
+// ---- the front end (mla_indexer_prep.hip): LayerNorm + RoPE + rotation + quantisation of the index key and the index queries ----
+// One launch over T * (1 + Hi) vectors of 128 columns: the T keys first, then the T * Hi q heads.  A vector is 16 lanes wide, a
+// workgroup of 256 threads takes 16 of them.
+constexpr int kIdxPrepThreads = 256;
+constexpr int kIdxPrepLanes = 16;                                   // lanes of one vector: 8 columns each
+constexpr int kIdxPrepVectors = kIdxPrepThreads / kIdxPrepLanes;    // vectors of a workgroup
+constexpr int kIdxRope = 64;                                        // columns of a vector that RoPE turns (the FIRST 64), and of a cos_sin row
+
+// Every argument of hpc_mla_indexer_prep_fp8_async the host rule looks at; pointers as integers: none is dereferenced.
+struct MlaIndexerPrepCall {
+  uintptr_t k_cache, out_k, out_q, out_weights, out_q_rot, k, q, head_weights, k_norm_weight, k_norm_bias, cos_sin,
+      num_seqlen_per_req, q_index, block_ids;
+  int num_rows, num_req, num_head, block_size, max_blocks, num_blocks, max_pos, head_weights_bf16;
+  int64_t block_stride, k_row_stride, q_row_stride, q_head_stride;
+  float weight_scale, eps, rotate_scale;
+};
+
+// Hi ** -0.5 in double, as Python forms it: the weight_scale of a call is float32(softmax_scale * Hi ** -0.5), formed by the
+// caller in double (the torch shim does)
+constexpr double mla_indexer_prep_head_factor(int num_head) {
+  return num_head == 16 ? 0.25 : num_head == 32 ? 0.1767766952966369 : 0.125;
+}
+
+struct MlaIndexerPrepRoute {
+  int code;         // HPC_OK or the refusal
+  const char* why;  // the refusal in words (null when accepted)
+  int head_shift;   // log2(num_head) with q, 0 without: vector T + (r << head_shift) + h is head h of row r
+  int64_t vectors;  // T * (1 + Hi) with q, T without
+  int grid;         // workgroups of 16 vectors; 0: nothing to launch
+};
+
+// The one host rule of the front end: the grid and every refusal with its reason.  q == 0: the key alone, num_head, head_weights
+// and weight_scale are not looked at.  k_cache == 0: the key goes to out_k alone and block_size, the block stride and block_ids
+// are not looked at.
+static inline MlaIndexerPrepRoute mla_indexer_prep_route(const MlaIndexerPrepCall& c) {
+  MlaIndexerPrepRoute r{};
+  const auto refuse = [&](int code, const char* why) {
+    r.code = code;
+    r.why = why;
+    return r;
+  };
+  constexpr int64_t span = int64_t{1} << 60;  // bytes: page id x block stride and row x row stride stay below 2^61
+  if (c.num_rows < 0 || c.num_req < 0 || c.max_blocks < 0 || c.num_blocks < 0 || c.max_pos < 0)
+    return refuse(HPC_ERR_INVALID, "num_rows, num_req, max_blocks, num_blocks and max_pos must not be negative");
+  if (!c.k_cache && !c.out_k) return refuse(HPC_ERR_INVALID, "the key has no destination: one of k_cache and out_k must be given");
+  const bool with_q = c.q != 0, work = c.num_rows > 0 && c.num_req > 0;
+  if (!with_q && (c.out_q || c.out_weights || c.out_q_rot || c.head_weights))
+    return refuse(HPC_ERR_INVALID, "out_q, out_weights, out_q_rot and head_weights need q");
+  if (with_q) {
+    if (c.num_head != 16 && c.num_head != 32 && c.num_head != 64)
+      return refuse(HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64");
+    if (!c.head_weights || !(c.weight_scale - c.weight_scale == 0.f))
+      return refuse(HPC_ERR_INVALID, "q needs head_weights and a finite weight_scale (softmax_scale * num_head^-0.5)");
+    if (!c.out_q || !c.out_weights) return refuse(HPC_ERR_INVALID, "q needs out_q and out_weights");
+  }
+  if (c.k_cache) {
+    const MlaIndexerCheck cache = mla_indexer_cache_check(c.k_cache, c.block_size, c.block_stride);
+    if (cache.code != HPC_OK) return refuse(cache.code, cache.why);
+  }
+  if (work && (!c.k || !c.k_norm_weight || !c.k_norm_bias || !c.cos_sin || !c.num_seqlen_per_req || !c.q_index ||
+               (c.k_cache && !c.block_ids)))
+    return refuse(HPC_ERR_INVALID, "k, k_norm_weight, k_norm_bias, cos_sin, num_seqlen_per_req, q_index and block_ids must not be null");
+  if (work && c.max_pos == 0) return refuse(HPC_ERR_INVALID, "cos_sin has no rows");
+  if (!(c.eps >= 0.f) || !(c.rotate_scale - c.rotate_scale == 0.f))
+    return refuse(HPC_ERR_INVALID, "eps must not be negative and rotate_scale must be finite");
+  if (c.k % 16 || c.q % 16 || c.out_k % 16 || c.out_q_rot % 16 || c.k_norm_weight % 16 || c.k_norm_bias % 16 || c.cos_sin % 16)
+    return refuse(HPC_ERR_UNSUPPORTED, "k, q, out_k, out_q_rot, k_norm_weight, k_norm_bias and cos_sin must be 16-byte aligned");
+  if (c.out_q % 8 || c.out_weights % 4 || c.head_weights % (c.head_weights_bf16 ? 2 : 4))
+    return refuse(HPC_ERR_UNSUPPORTED, "out_q must be 8-byte aligned, out_weights 4-byte and head_weights to its element");
+  if (c.k_row_stride < 0 || c.k_row_stride % 8 != 0 || (c.num_rows > 1 && c.k_row_stride < kIdxDim))
+    return refuse(HPC_ERR_UNSUPPORTED, "k row stride must be a multiple of 8 elements and at least 128");
+  if (with_q) {
+    if (c.q_head_stride < 0 || c.q_head_stride % 8 != 0 || c.q_head_stride < kIdxDim)
+      return refuse(HPC_ERR_UNSUPPORTED, "q head stride must be a multiple of 8 elements and at least 128");
+    if (c.q_row_stride < 0 || c.q_row_stride % 8 != 0 ||
+        (c.num_rows > 1 && c.q_row_stride < (c.num_head - 1) * c.q_head_stride + kIdxDim))
+      return refuse(HPC_ERR_UNSUPPORTED, "q row stride must be a multiple of 8 elements and hold num_head heads");
+  }
+  r.head_shift = !with_q ? 0 : c.num_head == 16 ? 4 : c.num_head == 32 ? 5 : 6;
+  r.vectors = static_cast<int64_t>(c.num_rows) * (with_q ? 1 + c.num_head : 1);
+  if (r.vectors > 0x7fffffffll - kIdxPrepVectors || c.num_req == 0x7fffffff)
+    return refuse(HPC_ERR_UNSUPPORTED, "num_rows * (1 + num_head) vectors do not fit int32");
+  if (c.k_row_stride > span / 2 / 0x7fffffffll || (with_q && c.q_row_stride > span / 2 / 0x7fffffffll) ||
+      (c.k_cache && c.num_blocks > 0 && c.block_stride > span / c.num_blocks))
+    return refuse(HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes");
+  r.grid = work ? static_cast<int>((r.vectors + kIdxPrepVectors - 1) / kIdxPrepVectors) : 0;
   return r;
 }
 

@@ -1,6 +1,7 @@
 // C++ host side of the DSA lightning indexer (csrc/mla_indexer.hip): mla_indexer_store_k_fp8, mla_indexer_logits_fp8,
-// mla_indexer_topk and the fused mla_indexer_topk_fp8, under torch.ops.hpc_mla.* beside the MLA ops they serve.  Ours only;
-// pinned to the PyTorch statement tests/mla_indexer_ref.py.  dtype, device and shape are checked here; the cache's rule, the
+// mla_indexer_topk and the fused mla_indexer_topk_fp8, and of its front end mla_indexer_prep_fp8 (csrc/mla_indexer_prep.hip), under torch.ops.hpc_mla.* beside the MLA ops they serve.  Ours only;
+// pinned to the PyTorch statements tests/mla_indexer_ref.py and tests/mla_indexer_prep_ref.py.  dtype, device and shape are
+// checked here; the cache's rule, the
 // limits, strides and alignment are the launchers' (csrc/mla_indexer_route.h) and come back in their words through
 // hpc_mla_indexer_*_refusal.  Nothing here reads the values of a length, a page table or a logit; with `output` given nothing is
 // allocated per call beyond the cached scratch of the fused op and the calls capture into a hipGraph.  No kernels here.
@@ -160,6 +161,90 @@ at::Tensor topk_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Te
   return out;
 }
 
+// ---- mla_indexer_prep_fp8: the front end (csrc/mla_indexer_prep.hip), pinned to tests/mla_indexer_prep_ref.py -------------------------
+// Returns (q8, weights): the caller's out_q / out_weights or fresh contiguous ones; two empty tensors without q.  With the
+// outputs given (or no q) nothing is allocated.  The host rule and its words are mla_indexer_prep_route's.
+std::tuple<at::Tensor, at::Tensor> prep_fp8(const c10::optional<at::Tensor>& k_cache, const at::Tensor& k, const at::Tensor& k_norm_weight,
+                                            const at::Tensor& k_norm_bias, const at::Tensor& cos_sin,
+                                            const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, const at::Tensor& block_ids,
+                                            const c10::optional<at::Tensor>& q, const c10::optional<at::Tensor>& head_weights,
+                                            c10::optional<double> softmax_scale, double eps, bool interleaved, double rotate_scale,
+                                            bool pow2_scale, const c10::optional<at::Tensor>& out_k,
+                                            const c10::optional<at::Tensor>& out_q, const c10::optional<at::Tensor>& out_weights,
+                                            const c10::optional<at::Tensor>& out_q_rot) {
+  TORCH_CHECK(k.is_cuda(), "k tensor must be cuda");
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16, "k dtype must be bfloat16");
+  TORCH_CHECK(k.dim() == 2 && k.size(1) == hpc::kIdxDim && k.stride(1) == 1, "k must be [rows, 128] with a contiguous last dim");
+  const int64_t rows = k.size(0);
+  for (const auto& [t, name] : {std::pair<const at::Tensor&, const char*>{k_norm_weight, "k_norm_weight"}, {k_norm_bias, "k_norm_bias"}}) {
+    check_on(t, name, k, at::kFloat, "float32");
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == hpc::kIdxDim && t.is_contiguous(), name, " must be a contiguous [128]");
+  }
+  check_on(cos_sin, "cos_sin", k, at::kFloat, "float32");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == hpc::kIdxRope && cos_sin.is_contiguous() && cos_sin.size(0) > 0,
+              "cos_sin must be a contiguous [max_pos, 64] with max_pos > 0");
+  check_table(num_seqlen_per_req, "num_seqlen_per_req", k, 1);
+  const int64_t num_req = num_seqlen_per_req.size(0);
+  check_table(q_index, "q_index", k, 1);
+  TORCH_CHECK(q_index.size(0) == num_req + 1, "q_index must be [num_req + 1] = [", num_req + 1, "]");
+  check_table(block_ids, "block_ids", k, 2);
+  TORCH_CHECK(block_ids.size(0) == num_req, "block_ids must have num_req = ", num_req, " rows");
+  TORCH_CHECK(k_cache.has_value() || out_k.has_value(), "one of k_cache and out_k must be given");
+  int64_t page = 0, num_blocks = 0, bs = 0;
+  if (k_cache.has_value()) {
+    page = check_cache(*k_cache, k);
+    num_blocks = k_cache->size(0), bs = block_stride(*k_cache);
+  }
+  TORCH_CHECK(rows <= INT32_MAX && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX && cos_sin.size(0) <= INT32_MAX, "sizes beyond int32");
+  at::Tensor ok;
+  if (out_k.has_value()) ok = out_or_new(out_k, k, {rows, hpc::kIdxDim}, at::kBFloat16, "out_k", kOnInputDevice);
+
+  const bool with_q = q.has_value();
+  TORCH_CHECK(with_q || !(head_weights.has_value() || out_q.has_value() || out_weights.has_value() || out_q_rot.has_value()),
+              "head_weights, out_q, out_weights and out_q_rot need q");
+  int64_t h = 0, q_rs = 0, q_hs = 0;
+  at::Tensor q8 = at::empty({0}, k.options().dtype(kF8)), w = at::empty({0}, k.options().dtype(at::kFloat)), qrot;
+  bool hw_bf16 = false;
+  if (with_q) {
+    check_on(*q, "q", k, at::kBFloat16, "bfloat16");
+    TORCH_CHECK(q->dim() == 3 && q->size(0) == rows && q->size(2) == hpc::kIdxDim && q->stride(2) == 1,
+                "q must be [rows, num_head, 128] with a contiguous last dim");
+    h = q->size(1);
+    TORCH_CHECK(h == 16 || h == 32 || h == 64, "mla_indexer_prep_fp8: the index head count must be 16, 32 or 64, got ", h);
+    TORCH_CHECK(head_weights.has_value() && softmax_scale.has_value(), "q needs head_weights and softmax_scale");
+    const at::Tensor& hw = *head_weights;
+    TORCH_CHECK(hw.is_cuda() && hw.device() == k.device(), "head_weights must be a cuda tensor on the device of the op's first tensor");
+    TORCH_CHECK(hw.scalar_type() == at::kFloat || hw.scalar_type() == at::kBFloat16, "head_weights dtype must be float32 or bfloat16");
+    TORCH_CHECK(hw.dim() == 2 && hw.size(0) == rows && hw.size(1) == h && hw.is_contiguous(), "head_weights must be a contiguous [rows, num_head]");
+    hw_bf16 = hw.scalar_type() == at::kBFloat16;
+    q_rs = rows > 1 ? q->stride(0) : h * q->stride(1), q_hs = q->stride(1);
+    q8 = out_or_new(out_q, k, {rows, h, hpc::kIdxDim}, kF8, "out_q", kOnInputDevice);
+    w = out_or_new(out_weights, k, {rows, h}, at::kFloat, "out_weights", kOnInputDevice);
+    if (out_q_rot.has_value()) qrot = out_or_new(out_q_rot, k, {rows, h, hpc::kIdxDim}, at::kBFloat16, "out_q_rot", kOnInputDevice);
+  }
+  const int64_t k_rs = rows > 1 ? k.stride(0) : hpc::kIdxDim;
+  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
+  const auto fp = [](const at::Tensor& t) { return static_cast<const float*>(t.data_ptr()); };
+  const auto vp = [](const at::Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; };
+  // float32(softmax_scale * Hi ** -0.5), formed in double as the caller's Python would
+  const float ss = with_q ? static_cast<float>(*softmax_scale * hpc::mla_indexer_prep_head_factor(i32(h))) : 0.f;
+  const char* why = hpc_mla_indexer_prep_fp8_refusal(
+      ptr(k_cache), vp(ok), with_q ? q8.data_ptr() : nullptr, with_q ? static_cast<float*>(w.data_ptr()) : nullptr, vp(qrot), ptr(k),
+      ptr(q), ptr(head_weights), fp(k_norm_weight), fp(k_norm_bias), fp(cos_sin), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
+      i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)), i32(num_blocks), i32(cos_sin.size(0)), bs, k_rs, q_rs, q_hs,
+      hw_bf16 ? 1 : 0, ss, static_cast<float>(eps), static_cast<float>(rotate_scale));
+  TORCH_CHECK(why == nullptr, "mla_indexer_prep_fp8: ", why);
+  if (rows == 0 || num_req == 0) return {q8, w};  // nothing to launch
+  const int rc = hpc_mla_indexer_prep_fp8_async(
+      ptr(k_cache), vp(ok), with_q ? q8.data_ptr() : nullptr, with_q ? static_cast<float*>(w.data_ptr()) : nullptr, vp(qrot), ptr(k),
+      ptr(q), ptr(head_weights), fp(k_norm_weight), fp(k_norm_bias), fp(cos_sin), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
+      i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)), i32(num_blocks), i32(cos_sin.size(0)), bs, k_rs, q_rs, q_hs,
+      hw_bf16 ? 1 : 0, ss, static_cast<float>(eps), static_cast<float>(rotate_scale), interleaved ? 1 : 0, pow2_scale ? 1 : 0,
+      stream_of(k));
+  HPC_LAUNCH_CHECK(rc, "mla_indexer_prep_fp8");
+  return {q8, w};
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(hpc_mla, m) {
@@ -171,6 +256,11 @@ TORCH_LIBRARY_FRAGMENT(hpc_mla, m) {
   m.def(
       "mla_indexer_topk_fp8(Tensor q, Tensor weights, Tensor k_cache, Tensor block_ids, Tensor num_seq_kvcache, int topk, int mtp, "
       "bool new_kv_included, Tensor? output) -> Tensor");
+  m.def(
+      "mla_indexer_prep_fp8(Tensor? k_cache, Tensor k, Tensor k_norm_weight, Tensor k_norm_bias, Tensor cos_sin, "
+      "Tensor num_seqlen_per_req, Tensor q_index, Tensor block_ids, Tensor? q, Tensor? head_weights, float? softmax_scale, float eps, "
+      "bool interleaved, float rotate_scale, bool pow2_scale, Tensor? out_k, Tensor? out_q, Tensor? out_weights, Tensor? out_q_rot) "
+      "-> (Tensor, Tensor)");
   // the cached logits scratch of the fused op (tests fill it with NaN bytes: no column that was not written may be read)
   m.def("_mla_indexer_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMlaIndexer); });
 }
@@ -180,4 +270,5 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("mla_indexer_logits_fp8", &logits_fp8);
   m.impl("mla_indexer_topk", &select_topk);
   m.impl("mla_indexer_topk_fp8", &topk_fp8);
+  m.impl("mla_indexer_prep_fp8", &prep_fp8);
 }

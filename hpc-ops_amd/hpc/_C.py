@@ -116,6 +116,8 @@ _sig("hpc_mla_indexer_topk_refusal", c_char_p, P, P, IP, I, I, L, I, L)
 _sig("hpc_mla_indexer_topk_async", I, P, P, IP, I, I, L, I, L, I, P)
 _sig("hpc_mla_indexer_topk_fp8_refusal", c_char_p, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, P, L)
 _sig("hpc_mla_indexer_topk_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, I, P, L, P)
+_sig("hpc_mla_indexer_prep_fp8_refusal", c_char_p, P, P, P, P, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, I, F, F, F)
+_sig("hpc_mla_indexer_prep_fp8_async", I, P, P, P, P, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, I, F, F, F, I, I, P)
 _sig("hpc_mla_rope_norm_store_kv_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_mla_rope_norm_store_kv_fp8_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)
 _sig("hpc_attention_prefill_mla_bf16_async", I, P, P, P, P, P, P, IP, IP, I, I, I, I, L, L, L, L, L, L, L, F, I, P)

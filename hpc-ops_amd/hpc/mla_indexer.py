@@ -1,9 +1,14 @@
 """The DSA lightning indexer of a DeepSeek-V3.2 decode step: the paged FP8 index-key cache, its writer, the FP8 MQA logits over it
-and the top-k that yields the `indices` of hpc.attention_decode_mla_sparse_bf16 / _fp8 (csrc/mla_indexer.hip).
+and the top-k that yields the `indices` of hpc.attention_decode_mla_sparse_bf16 / _fp8 (csrc/mla_indexer.hip), and the front end
+in front of them (csrc/mla_indexer_prep.hip).
 
-No reference counterpart: the ops are registered under torch.ops.hpc_mla.* and pinned to the float64 PyTorch statement
-tests/mla_indexer_ref.py.  The index key's LayerNorm, RoPE and rotation in front of the store are the caller's.
+No reference counterpart: the ops are registered under torch.ops.hpc_mla.* and pinned to the float64 PyTorch statements
+tests/mla_indexer_ref.py and tests/mla_indexer_prep_ref.py.  The index key's LayerNorm, RoPE and rotation in front of the store,
+the queries' RoPE, rotation and quantisation and the fold of the head weights are mla_indexer_prep_fp8; mla_indexer_store_k_fp8
+remains for a caller that runs them itself.
 """
+from typing import Optional, Tuple
+
 import torch
 from torch import Tensor
 
@@ -124,3 +129,77 @@ def mla_indexer_topk_fp8(q: Tensor, weights: Tensor, k_cache: Tensor, block_ids:
 @torch.library.register_fake("hpc_mla::mla_indexer_topk_fp8")
 def _mla_indexer_topk_fp8_fake(q, weights, k_cache, block_ids, num_seq_kvcache, topk, mtp, new_kv_included, output=None):
     return output if output is not None else q.new_empty((q.shape[0], topk), dtype=torch.int32)
+
+
+def mla_indexer_prep_fp8(k_cache: Optional[Tensor], k: Tensor, k_norm_weight: Tensor, k_norm_bias: Tensor, cos_sin: Tensor,
+                         num_seqlen_per_req: Tensor, q_index: Tensor, block_ids: Tensor, *, q: Optional[Tensor] = None,
+                         head_weights: Optional[Tensor] = None, softmax_scale: Optional[float] = None, eps: float = 1e-6,
+                         interleaved: bool = False, rotate_scale: float = 128 ** -0.5, pow2_scale: bool = False,
+                         out_k: Optional[Tensor] = None, out_q: Optional[Tensor] = None, out_weights: Optional[Tensor] = None,
+                         out_q_rot: Optional[Tensor] = None) -> Optional[Tuple[Tensor, Tensor]]:
+    """The indexer's front end in one launch: everything between a layer's wq_b / wk / weights_proj GEMMs and
+    mla_indexer_topk_fp8.  Returns (q8, weights) when q is given, else None.
+
+    Semantics = the PyTorch statement tests/mla_indexer_prep_ref.py, in float64.  Row r is one new token.  Its request b is
+    the last one with q_index[b] <= r and its position pos = num_seqlen_per_req[b] - (q_index[b + 1] - r), the rule of
+    mla_rope_norm_store_kv / mla_indexer_store_k_fp8; rows past q_index[-1] or with pos < 0 belong to no request.
+    Everything is computed in fp32 with ONE rounding to bfloat16 per path, after the rotation.
+
+    key, x = k[r] (bfloat16 [T, 128], the wk output):
+        n      = (x - mean(x)) / sqrt(var(x) + eps) * k_norm_weight + k_norm_bias      (biased variance over the 128 columns)
+        n[:64] = rot(n[:64], cos_sin[pos])                                             (RoPE on the FIRST 64 columns)
+        kr     = bf16( H128(n) * rotate_scale )
+      kr goes into k_cache exactly as mla_indexer_store_k_fp8(kr) would write it (bit for bit), and into out_k (bfloat16
+      [T, 128], contiguous) when given.  k_cache may be None when out_k is given; at least one of the two is required.
+    queries, x = q[r, h] (bfloat16 [T, Hi, 128], Hi in {16, 32, 64}), when q is given:
+        x[:64]        = rot(x[:64], cos_sin[pos])
+        qr            = bf16( H128(x) * rotate_scale )                    -> out_q_rot (bfloat16 [T, Hi, 128]) when given
+        (code, scale) = the 128-block quantiser on qr                     -> q8 float8_e4m3fn [T, Hi, 128]
+        weights[r, h] = fp32( fp32( head_weights[r, h] * scale ) * c ),   c = float32(softmax_scale * Hi ** -0.5)
+      (q8, weights) are exactly the q / weights arguments of mla_indexer_logits_fp8 / mla_indexer_topk_fp8.  q needs
+      head_weights (float32 or bfloat16 [T, Hi], contiguous: the weights_proj output) and softmax_scale.
+
+    rot, cos_sin     those of mla_rope_norm_store_kv: cos_sin float32 [max_pos, 64] contiguous, cos[0..31] then sin[0..31];
+                     rot turns each pair (a, b) into (a cos_i - b sin_i, b cos_i + a sin_i).  interleaved=False pairs column
+                     i with i + 32 (neox: what the V3.2 indexer uses), True pairs (2i, 2i + 1).
+    H128             the Walsh-Hadamard transform in Sylvester order, y[i] = sum_j (-1)^popcount(i & j) x[j]; H128 . H128 =
+                     128 I, so with the default rotate_scale = 128 ** -0.5 the rotation is orthonormal and q . k is kept.
+    quantiser        the project's (hpc.blockwise_fp8_quant, tests/blockwise_quant_ref.py::quant): scale = amax / 448,
+                     code = e4m3fn(x * (1 / (scale + 1e-8))).  pow2_scale=True (DeepSeek's ue8m0 format), for key and
+                     queries alike: the scale is the smallest power of two at or above amax / 448 - of its float32 bits
+                     the exponent field goes up by one when the mantissa is non-zero and is clamped to [1, 254] - and
+                     code = e4m3fn(x / scale), which is exact and cannot saturate.  The readers take any finite
+                     non-negative scale.
+    k_norm_weight,   float32 [128] each.
+    k_norm_bias
+    layouts          k and q may be views with padded strides: last dim contiguous, row (and head) strides multiples of 8
+                     elements, base 16-byte aligned.  q8, weights (float32), out_k and out_q_rot are contiguous.
+    rows of no       store nothing in the cache and are written as zeros in out_k, out_q, out_weights and out_q_rot.
+    request
+    cache guards     as mla_indexer_store_k_fp8: a page id outside [0, num_blocks) stores nothing, a position beyond the table
+                     stores nothing, the cos_sin index is clamped to max_pos - 1 (the result of such a row is unspecified);
+                     only the 128 + 4 bytes of a new token are written, page tails are not cleared.
+    limits           T * (1 + Hi) vectors must fit int32.
+
+    Nothing on the host reads device values.  With out_q and out_weights given (or without q) nothing is allocated and the
+    call captures into a hipGraph.  T == 0 or num_req == 0 returns without a launch.  A fixed butterfly order and no
+    atomics: the result is bit-identical from call to call."""
+    q8, weights = torch.ops.hpc_mla.mla_indexer_prep_fp8(
+        k_cache, k, k_norm_weight, k_norm_bias, cos_sin, num_seqlen_per_req, q_index, block_ids, q, head_weights,
+        None if softmax_scale is None else float(softmax_scale), float(eps), bool(interleaved), float(rotate_scale), bool(pow2_scale),
+        out_k, out_q, out_weights, out_q_rot)
+    if q is None:
+        return None
+    return (q8 if out_q is None else out_q), (weights if out_weights is None else out_weights)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_prep_fp8")
+def _mla_indexer_prep_fp8_fake(k_cache, k, k_norm_weight, k_norm_bias, cos_sin, num_seqlen_per_req, q_index, block_ids, q,
+                               head_weights, softmax_scale, eps, interleaved, rotate_scale, pow2_scale, out_k, out_q, out_weights,
+                               out_q_rot):
+    """the entry's return (csrc/torch_mla_indexer.cpp::prep_fp8): out_q / out_weights, fresh ones, or two empty tensors"""
+    if q is None:
+        return (torch.empty((0,), dtype=torch.float8_e4m3fn, device=k.device), torch.empty((0,), dtype=torch.float32, device=k.device))
+    q8 = out_q if out_q is not None else torch.empty(q.shape, dtype=torch.float8_e4m3fn, device=k.device)
+    w = out_weights if out_weights is not None else torch.empty(q.shape[:2], dtype=torch.float32, device=k.device)
+    return q8, w

@@ -613,6 +613,48 @@ int hpc_mla_indexer_topk_fp8_async(int* indices, const void* q, const float* wei
                                    int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
                                    int new_kv_included, void* workspace, int64_t workspace_bytes, hpc_stream_t stream);
 
+/* ---- The indexer's front end: key LayerNorm + RoPE + Hadamard rotation + FP8 quant + store, q likewise (csrc/mla_indexer_prep.hip)
+ * What runs between a layer's wq_b / wk / weights_proj GEMMs and hpc_mla_indexer_topk_fp8_async, in one launch.  No reference
+ * kernel; the statement is tests/mla_indexer_prep_ref.py, the host rule csrc/mla_indexer_route.h (mla_indexer_prep_route).
+ * Row r of k (bf16 [num_rows, 128], row stride in elements) is one new token; its request and position are those of
+ * hpc_mla_indexer_store_k_fp8_async.  Everything in fp32 with ONE rounding to bf16, after the rotation:
+ *   n = (k[r] - mean) / sqrt(var + eps) * k_norm_weight + k_norm_bias (biased variance over the 128 columns),
+ *   n[:64] = rot(n[:64], cos_sin[pos]) (rot and the table [max_pos, 64] of hpc_mla_rope_norm_store_kv_async, on the FIRST 64
+ *   columns; interleaved 0 pairs i with i + 32), kr = bf16(H128(n) * rotate_scale), H128 the Walsh-Hadamard transform in
+ *   Sylvester order; kr goes into the cache exactly as hpc_mla_indexer_store_k_fp8_async(kr) writes it, and to out_k (bf16
+ *   [num_rows, 128] contiguous) when given.  k_cache NULL: out_k alone (block_size, the block stride, block_ids not looked at).
+ * With q (bf16 [num_rows, num_head, 128], row and head strides in elements; num_head 16 / 32 / 64): qr = bf16(H128(q[r, h] with
+ *   its first 64 columns turned) * rotate_scale) -> out_q_rot (bf16, contiguous, optional); its 128-block quantisation -> out_q
+ *   (e4m3 codes, contiguous) and out_weights[r, h] = fp32(fp32(head_weights[r, h] * scale) * weight_scale), weight_scale =
+ *   float(softmax_scale * num_head^-0.5) formed by the caller in double (head_weights fp32 or bf16 [num_rows, num_head]
+ *   contiguous): the q / weights of hpc_mla_indexer_logits_fp8_async.
+ *   q NULL: the key alone; num_head, head_weights, weight_scale are not looked at and the q outputs must be NULL.
+ * pow2_scale != 0: both quantisers take the smallest power of two >= amax / 448 as the scale (exponent field + 1 when the mantissa
+ *   is not zero, clamped to [1, 254]) and code = e4m3(x / scale), exactly.
+ * Rows of no request store nothing and are zeros in every output; a page id outside [0, num_blocks) and a position beyond the
+ * table store nothing; the cos_sin row is clamped to max_pos - 1; only the 128 + 4 bytes of a new token are written.
+ * HPC_ERR_INVALID: negative counts, no destination for the key, q outputs or head_weights without q, q without head_weights / a
+ * finite weight_scale / out_q / out_weights, null pointers with work, max_pos == 0 with work, a negative eps or block stride;
+ * HPC_ERR_UNSUPPORTED: num_head, block_size, strides that are no multiple of 8 elements or too short, misaligned bases,
+ * num_rows * (1 + num_head) beyond int32.  num_rows == 0 or num_req == 0 launches nothing.  hpc_mla_indexer_prep_fp8_refusal
+ * returns the refusal of the same call in words, or NULL: a pure host function.  Nothing on the host reads a device value; no
+ * atomics, a fixed butterfly order: the same bits on every call. */
+const char* hpc_mla_indexer_prep_fp8_refusal(const void* k_cache, const void* out_k, const void* out_q, const float* out_weights,
+                                             const void* out_q_rot, const void* k, const void* q, const void* head_weights,
+                                             const float* k_norm_weight, const float* k_norm_bias, const float* cos_sin,
+                                             const int* num_seqlen_per_req, const int* q_index, const int* block_ids,
+                                             int num_rows, int num_req, int num_head, int block_size, int max_blocks,
+                                             int num_blocks, int max_pos, int64_t k_cache_block_stride_bytes,
+                                             int64_t k_row_stride, int64_t q_row_stride, int64_t q_head_stride,
+                                             int head_weights_bf16, float weight_scale, float eps, float rotate_scale);
+int hpc_mla_indexer_prep_fp8_async(void* k_cache, void* out_k, void* out_q, float* out_weights, void* out_q_rot, const void* k,
+                                   const void* q, const void* head_weights, const float* k_norm_weight, const float* k_norm_bias,
+                                   const float* cos_sin, const int* num_seqlen_per_req, const int* q_index, const int* block_ids,
+                                   int num_rows, int num_req, int num_head, int block_size, int max_blocks, int num_blocks,
+                                   int max_pos, int64_t k_cache_block_stride_bytes, int64_t k_row_stride, int64_t q_row_stride,
+                                   int64_t q_head_stride, int head_weights_bf16, float weight_scale, float eps,
+                                   float rotate_scale, int interleaved, int pow2_scale, hpc_stream_t stream);
+
 /* ---- MLA latent-cache write: kv_a RMSNorm + RoPE + paged store, bf16 (csrc/mla_store.hip) ------------------------------------
  * No reference kernel exists; the semantics are the PyTorch statement tests/mla_store_ref.py.  The producer of the cache and of
  * the RoPE columns of q that hpc_attention_decode_mla_bf16_async reads.  Row r of kv_a is one new token; its request b is the

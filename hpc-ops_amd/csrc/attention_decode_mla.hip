@@ -40,6 +40,7 @@
 #include "mla_fp8_format.h"
 #include "hpc_amd.h"
 #include "hpc_common.h"
+#include "mla_indexer_dev.h"
 
 namespace hpc {
 namespace mla {
@@ -69,9 +70,12 @@ struct Args {
 };
 
 // The token-sparse form adds the lists: row b * num_seq_q + s of `indices` names the token positions q row (b, s) attends to
+// Ragged (a prefill chunk, q_index given): unit r is row r of the chunk, its request and vis are the writers' row rule
+// (mla_indexer_dev.h::row_sees over num_seq = num_seqlen_per_req), num_seq_q is 1 and block_ids has num_req rows.
 struct SparseArgs : Args {
   const int* indices;  // [num_batch * num_seq_q, topk]
-  int topk, plen, num_blocks;  // plen: list slots per piece, a multiple of kMlaKvTile (a host value, as topk is)
+  const int* q_index;  // null: a decode step.  Given: [num_req + 1] of a ragged chunk
+  int topk, plen, num_blocks, num_req;  // plen: list slots per piece, a multiple of kMlaKvTile (a host value, as topk is)
 };
 template <bool kSparse>
 using ArgsOf = std::conditional_t<kSparse, SparseArgs, Args>;
@@ -136,14 +140,21 @@ __global__ __launch_bounds__(kThreads) void attention_decode_mla_kernel(const Ar
   id /= a.splits;
   // unit: the request (dense) or the q row b * num_seq_q + s (sparse) whose a.rows rows this workgroup's tile is cut from
   const int tile = id % a.row_tiles, unit = id / a.row_tiles;
-  const int b = kSparse ? unit / a.num_seq_q : unit;
+  int b = kSparse ? unit / a.num_seq_q : unit;
 
   int p0, p1, vis = 0;  // dense: the piece's tokens; sparse: the piece's list slots and the positions they may name
   [[maybe_unused]] int len = 0;
   if constexpr (kSparse) {
     p0 = piece * a.plen;  // < topk: the host launches no piece past the list
     p1 = p0 + a.plen < a.topk ? p0 + a.plen : a.topk;
-    vis = sparse_vis(a, b, unit - b * a.num_seq_q);
+    if (a.q_index) {  // a ragged chunk: the row rule gives the request (one of the call's) and what the row sees
+      const hpc::mla_indexer::RowSees at =
+          hpc::mla_indexer::row_sees(a.q_index, a.num_seq, a.num_req, unit, a.max_blocks << a.page_shift);
+      b = at.req;
+      vis = at.vis;
+    } else {
+      vis = sparse_vis(a, b, unit - b * a.num_seq_q);
+    }
   } else {
     len = request_len(a, b);
     const int plen = piece_len(len, a.splits);
@@ -482,6 +493,8 @@ struct MlaDecodeCall {
   const int* block_ids;
   const int* num_seq_kvcache;
   const int* indices;
+  const int* q_index;  // the ragged entries: num_batch is the chunk's rows, num_seq_q 1, num_seq_kvcache num_seqlen_per_req
+  int num_req;
   int num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks;
   int64_t ckv_block_stride, ckv_token_stride;  // in the kind's units: bf16 elements or FP8 bytes
   float softmax_scale;
@@ -516,6 +529,7 @@ int mla_decode_launch(const MlaDecodeCall& c) {
     return HPC_ERR_UNSUPPORTED;
   if (c.num_batch == 0) return HPC_OK;
   if (c.max_blocks == 0) return HPC_ERR_INVALID;
+  if (c.q_index && (c.num_req <= 0 || c.num_req == INT32_MAX)) return HPC_ERR_INVALID;  // the ragged entries leave before this without requests
   const hpc::MlaRoute r =
       c.splits > 0 ? shape : hpc::mla_route(c.num_batch, c.num_seq_q, c.num_head, kSparse, c.topk, 0, mla_current_cu_count());
   if (r.code != HPC_OK) return r.code;
@@ -546,6 +560,8 @@ int mla_decode_launch(const MlaDecodeCall& c) {
   a.scale_log2 = c.softmax_scale * kLog2e;
   if constexpr (kSparse) {
     a.indices = c.indices;
+    a.q_index = c.q_index;
+    a.num_req = c.num_req;
     a.topk = c.topk;
     a.plen = r.plen;
     a.num_blocks = c.num_blocks;
@@ -578,7 +594,7 @@ extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr
                                                    int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                    int new_kv_included, int splits, void* workspace_ptr,
                                                    int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<false, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, num_batch,
+  return mla_decode_launch<false, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, nullptr, 0, num_batch,
                                           num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride, ckv_token_stride,
                                           softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes, stream});
 }
@@ -590,7 +606,7 @@ extern "C" int hpc_attention_decode_mla_fp8_async(void* out_ptr, float* lse_ptr,
                                                   int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                   float softmax_scale, int new_kv_included, int splits, void* workspace_ptr,
                                                   int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<true, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, num_batch,
+  return mla_decode_launch<true, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, nullptr, 0, num_batch,
                                          num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride_bytes,
                                          ckv_token_stride_bytes, softmax_scale, new_kv_included, splits, workspace_ptr,
                                          workspace_bytes, stream});
@@ -617,7 +633,7 @@ extern "C" int hpc_attention_decode_mla_sparse_bf16_async(void* out_ptr, float* 
                                                           int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                           int new_kv_included, int splits, void* workspace_ptr,
                                                           int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr,
+  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, nullptr, 0,
                                          num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride,
                                          ckv_token_stride, softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes,
                                          stream});
@@ -631,8 +647,40 @@ extern "C" int hpc_attention_decode_mla_sparse_fp8_async(void* out_ptr, float* l
                                                          int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                          float softmax_scale, int new_kv_included, int splits,
                                                          void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr,
+  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, nullptr, 0,
                                         num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks,
                                         ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale, new_kv_included, splits,
                                         workspace_ptr, workspace_bytes, stream});
+}
+
+// ---- the token-sparse form over a ragged prefill chunk: row r of the chunk is a unit, its request and what it sees come from the
+// row rule on the device (num_seqlen_per_req: total lengths including the chunk's tokens; q_index [num_req + 1]); everything
+// else - route (mla_route with num_batch = num_rows, num_seq_q = 1; hpc_attention_decode_mla_sparse_plan sizes the scratch),
+// launcher, kernel, merge - is the decode form's.  num_rows == 0 or num_req == 0 launches nothing.
+extern "C" int hpc_attention_prefill_mla_sparse_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                           const int* block_ids_ptr, const int* num_seqlen_per_req_ptr,
+                                                           const int* q_index_ptr, const int* indices_ptr, int num_rows, int num_req,
+                                                           int num_head, int topk, int block_size, int max_blocks, int num_blocks,
+                                                           int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
+                                                           int splits, void* workspace_ptr, int64_t workspace_bytes,
+                                                           hipStream_t stream) {
+  if (!q_index_ptr || num_req < 0) return HPC_ERR_INVALID;
+  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seqlen_per_req_ptr, indices_ptr,
+                                         q_index_ptr, num_req, num_req == 0 && num_rows > 0 ? 0 : num_rows, 1, num_head, topk,
+                                         block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride, softmax_scale, 1,
+                                         splits, workspace_ptr, workspace_bytes, stream});
+}
+
+extern "C" int hpc_attention_prefill_mla_sparse_fp8_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
+                                                          const int* block_ids_ptr, const int* num_seqlen_per_req_ptr,
+                                                          const int* q_index_ptr, const int* indices_ptr, int num_rows, int num_req,
+                                                          int num_head, int topk, int block_size, int max_blocks, int num_blocks,
+                                                          int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
+                                                          float softmax_scale, int splits, void* workspace_ptr,
+                                                          int64_t workspace_bytes, hipStream_t stream) {
+  if (!q_index_ptr || num_req < 0) return HPC_ERR_INVALID;
+  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seqlen_per_req_ptr, indices_ptr,
+                                        q_index_ptr, num_req, num_req == 0 && num_rows > 0 ? 0 : num_rows, 1, num_head, topk,
+                                        block_size, max_blocks, num_blocks, ckv_block_stride_bytes, ckv_token_stride_bytes,
+                                        softmax_scale, 1, splits, workspace_ptr, workspace_bytes, stream});
 }

@@ -78,10 +78,6 @@ struct LogitsArgs {
 };
 
 constexpr int kLogitsThreads = 64 * kIdxWaves;
-constexpr int kSub = kIdxTile / 16;  // 16-token blocks of a wave's step
-static_assert(kSub == 4, "lane group g stores block g");
-
-__device__ __forceinline__ int clamp_len(long v, int cols) { return static_cast<int>(v < 0 ? 0 : (v > cols ? cols : v)); }
 
 template <int kHB, int kSq>
 __global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs a) {
@@ -110,9 +106,7 @@ __global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs
 #pragma unroll
     for (int hb = 0; hb < kHB; ++hb) {
       const uint8_t* p = a.q + (r * kHi + 16 * hb + n) * kIdxDim + 32 * g;
-      const u32x4 x = ld16(p), y = ld16(p + 16);
-      qf[s][hb] = i32x8{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3]),
-                        static_cast<int>(y[0]), static_cast<int>(y[1]), static_cast<int>(y[2]), static_cast<int>(y[3])};
+      qf[s][hb] = operand32(ld16(p), ld16(p + 16));
       wt[s][hb] = *reinterpret_cast<const f32x4*>(a.w + r * kHi + 16 * hb + 4 * g);
     }
   }
@@ -137,41 +131,17 @@ __global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs
     const int t1 = t0 + kIdxTile * kIdxWaves;
     if (t1 < c1) lookup(t1, next);  // a step ahead of its keys
 
-    i32x8 kv[kSub];
-    float sc[kSub];
-    bool ok[kSub];
+    // the step's four key blocks, their operand layout and guards: mla_indexer_dev.h
+    KeyBlock key[kSub];
 #pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-      ok[u] = phys[u] >= 0 && phys[u] < a.num_blocks;  // a block at or past c1, -1 padding, a poisoned id: its page is never loaded
-      kv[u] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-      sc[u] = 0.f;
-      if (ok[u]) {
-        const uint8_t* page = a.cache + phys[u] * a.cache_bs;
-        const int t = (t0 + 16 * u + n) & mask;
-        const u32x4 x = ld16(page + t * kIdxDim + 32 * g), y = ld16(page + t * kIdxDim + 32 * g + 16);
-        kv[u] = i32x8{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3]),
-                      static_cast<int>(y[0]), static_cast<int>(y[1]), static_cast<int>(y[2]), static_cast<int>(y[3])};
-        sc[u] = *reinterpret_cast<const float*>(page + scales_at + 4 * t);
-      }
-    }
+    for (int u = 0; u < kSub; ++u)
+      key[u] = load_key_block(a.cache, a.cache_bs, scales_at, phys[u], a.num_blocks, (t0 + 16 * u + n) & mask, g);
     const int j = t0 + 16 * g + n;  // the column this lane stores
 #pragma unroll
     for (int s = 0; s < kSq; ++s) {
       float val[kSub];
 #pragma unroll
-      for (int u = 0; u < kSub; ++u) {
-        float acc = 0.f;
-#pragma unroll
-        for (int hb = 0; hb < kHB; ++hb) {
-          const f32x4 d =
-              __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(qf[s][hb], kv[u], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc = fmaf(wt[s][hb][i], fmaxf(d[i], 0.f), acc);
-        }
-        acc += __shfl_xor(acc, 16, 64);
-        acc += __shfl_xor(acc, 32, 64);
-        val[u] = ok[u] ? sc[u] * acc : -__builtin_inff();
-      }
+      for (int u = 0; u < kSub; ++u) val[u] = key_logit(key[u], head_sum<kHB>(qf[s], wt[s], key[u].kv));
       const float mine = g == 0 ? val[0] : g == 1 ? val[1] : g == 2 ? val[2] : val[3];
       if (j < vis[s]) a.out[(static_cast<long>(b) * kSq + s) * a.out_rs + j] = mine;
     }
@@ -183,10 +153,11 @@ __global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs
 // ---- top-k ------------------------------------------------------------------------------------------------------------------------
 struct TopkArgs {
   const float* logits;  // row r at logits + r * rs floats
-  const int* lens;      // [B]
-  int* out;             // [B * Sq, topk]
+  const int* lens;      // [B]; ragged: num_seqlen_per_req [num_req]
+  const int* q_index;   // null: a decode step, row r is (b, s) = (r / sq, r % sq).  Given: a ragged chunk, [num_req + 1]
+  int* out;             // [rows, topk]
   long rs;
-  int sq, cols, topk, nki;
+  int sq, cols, topk, nki, num_req, row_begin;  // ragged: row r of the call is row row_begin + r of the chunk
 };
 
 constexpr int kTopkThreads = 1024, kTopkWaves = kTopkThreads / 64, kTopkBatch = 4;
@@ -196,9 +167,15 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const TopkArgs a) {
   __shared__ uint32_t found[2];  // the prefix with the pass's digit behind it, and what is still needed inside it
   __shared__ uint32_t wave_gt[kTopkWaves], wave_tie[kTopkWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = blockIdx.x, b = r / a.sq, s = r % a.sq;
-  const long len = static_cast<long>(a.lens[b]) + (a.nki ? 0 : a.sq);
-  const int n = clamp_len(len - a.sq + s + 1, a.cols);
+  const int r = blockIdx.x;
+  int n;  // the columns row r sees: the one thing a ragged chunk takes from elsewhere (the row rule, mla_indexer_dev.h)
+  if (a.q_index) {
+    n = row_sees(a.q_index, a.lens, a.num_req, a.row_begin + r, a.cols).vis;
+  } else {
+    const int b = r / a.sq, s = r % a.sq;
+    const long len = static_cast<long>(a.lens[b]) + (a.nki ? 0 : a.sq);
+    n = clamp_len(len - a.sq + s + 1, a.cols);
+  }
   int* o = a.out + static_cast<long>(r) * a.topk;
   if (n <= a.topk) {  // the identity list: no logit is read
     for (int i = tid; i < a.topk; i += kTopkThreads) o[i] = i < n ? i : -1;
@@ -427,12 +404,17 @@ int launch_logits(float* logits, const void* q, const float* weights, const void
   return HPC_OK;
 }
 
+// q_index null: a decode step of num_batch requests.  Given: a ragged chunk, num_batch its rows, num_seq_q 1
 int launch_topk(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q, int64_t num_cols,
-                int topk, int64_t logits_row_stride, int new_kv_included, hipStream_t stream) {
+                int topk, int64_t logits_row_stride, int new_kv_included, hipStream_t stream, const int* q_index = nullptr,
+                int num_req = 0, int row_begin = 0) {
   using namespace hpc::mla_indexer;
   TopkArgs a{};
   a.logits = logits;
   a.lens = num_seq_kvcache;
+  a.q_index = q_index;
+  a.num_req = num_req;
+  a.row_begin = row_begin;
   a.out = indices;
   a.rs = logits_row_stride;
   a.sq = num_seq_q;
@@ -533,6 +515,47 @@ extern "C" int hpc_mla_indexer_topk_async(int* indices, const float* logits, con
   if (num_batch == 0) return HPC_OK;  // nothing to launch
   return launch_topk(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride, new_kv_included,
                      stream);
+}
+
+// ---- the top-k of a ragged chunk: the same kernel with the row rule as the source of n_r --------------------------------------
+namespace {
+MlaIndexerCheck topk_prefill_check(const int* indices, const float* logits, const int* num_seqlen_per_req, const int* q_index,
+                                   int num_rows, int num_req, int row_begin, int64_t num_cols, int topk, int64_t logits_row_stride) {
+  using namespace hpc;
+  if (num_rows < 0 || num_req < 0 || row_begin < 0) return {HPC_ERR_INVALID, "num_rows, num_req and row_begin must not be negative"};
+  if (num_cols < 0) return {HPC_ERR_INVALID, "the logits' column count must not be negative"};
+  if (topk < 1 || topk > kIdxMaxTopk) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
+  if (num_cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "logits reach beyond 2^30 columns"};
+  if (static_cast<int64_t>(row_begin) + num_rows > INT32_MAX || num_req == INT32_MAX)
+    return {HPC_ERR_UNSUPPORTED, "row_begin + num_rows and num_req + 1 must fit int32"};
+  // a row that sees no more than topk tokens reads no logit, so a call over zero columns needs no logits at all
+  const bool work = num_rows > 0 && num_req > 0;
+  if (work && (!indices || !num_seqlen_per_req || !q_index || (!logits && num_cols > 0)))
+    return {HPC_ERR_INVALID, "indices, logits, num_seqlen_per_req and q_index must not be null"};
+  if (misaligned(indices, 4) || misaligned(logits, 4)) return {HPC_ERR_UNSUPPORTED, "indices and logits must be 4-byte aligned"};
+  if (logits_row_stride < num_cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least the column count"};
+  if (logits_row_stride > kSpan / 4 / INT32_MAX) return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+}  // namespace
+
+extern "C" const char* hpc_mla_indexer_topk_prefill_refusal(const int* indices, const float* logits, const int* num_seqlen_per_req,
+                                                            const int* q_index, int num_rows, int num_req, int row_begin,
+                                                            int64_t num_cols, int topk, int64_t logits_row_stride) {
+  return topk_prefill_check(indices, logits, num_seqlen_per_req, q_index, num_rows, num_req, row_begin, num_cols, topk,
+                            logits_row_stride)
+      .why;
+}
+
+extern "C" int hpc_mla_indexer_topk_prefill_async(int* indices, const float* logits, const int* num_seqlen_per_req,
+                                                  const int* q_index, int num_rows, int num_req, int row_begin, int64_t num_cols,
+                                                  int topk, int64_t logits_row_stride, hipStream_t stream) {
+  const MlaIndexerCheck c = topk_prefill_check(indices, logits, num_seqlen_per_req, q_index, num_rows, num_req, row_begin, num_cols,
+                                               topk, logits_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (num_rows == 0 || num_req == 0) return HPC_OK;  // nothing to launch, as the writers of the cache
+  return launch_topk(indices, logits, num_seqlen_per_req, num_rows, 1, num_cols, topk, logits_row_stride, 1, stream, q_index,
+                     num_req, row_begin);
 }
 
 extern "C" const char* hpc_mla_indexer_topk_fp8_refusal(const int* indices, const void* q, const float* weights,

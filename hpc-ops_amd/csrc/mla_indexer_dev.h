@@ -1,6 +1,9 @@
 // Device pieces the writers of the index-key cache share (mla_indexer.hip: store_kernel; mla_indexer_prep.hip: prep_kernel), stated
 // once: the request and position of a row, the cache cell of a token with its guards, the 16-lane abs-max, the 128-column
 // quantiser on a vector held as 8 columns per lane, and the store of a token's 128 + 4 bytes.  Internal, device only.
+// Behind them what the READERS share (mla_indexer.hip: logits_kernel, topk_kernel; mla_indexer_prefill.hip: logits_prefill_kernel;
+// attention_decode_mla.hip: the sparse form over a ragged chunk): the operand roles, the key block and the head sum of a logit,
+// and the ragged row rule as what a row sees.
 #pragma once
 #include "act_quant.h"
 #include "hpc_common.h"
@@ -77,6 +80,65 @@ __device__ __forceinline__ u32x2 codes8(const float (&v)[8], float inv) {
 __device__ __forceinline__ void store_key(uint8_t* cache, const Cell& c, int sub, u32x2 codes, float scale) {
   *reinterpret_cast<u32x2*>(cache + c.codes_at + 8 * sub) = codes;
   if (sub == 0) *reinterpret_cast<float*>(cache + c.scale_at) = scale;
+}
+
+// ---- the readers: logits_kernel (mla_indexer.hip, a decode step) and logits_prefill_kernel (mla_indexer_prefill.hip, a ragged
+// chunk).  The operand roles, the key block and the head sum are stated here once, so that logit (row, j) has the same bits from
+// either kernel: A = 16 q heads (lane (n, g) holds bytes 32 g .. 32 g + 31 of head 16 hb + n), B = 16 keys (lane (n, g) holds
+// bytes 32 g .. 32 g + 31 of token n of the block), and lane (n, g) of the result holds heads 16 hb + 4 g .. + 3 of token n.
+constexpr int kSub = kIdxTile / 16;  // 16-token blocks of a wave's step
+static_assert(kSub == 4, "lane group g stores block g");
+
+__device__ __forceinline__ int clamp_len(long v, int cols) { return static_cast<int>(v < 0 ? 0 : (v > cols ? cols : v)); }
+
+__device__ __forceinline__ i32x8 operand32(const u32x4 x, const u32x4 y) {
+  return i32x8{static_cast<int>(x[0]), static_cast<int>(x[1]), static_cast<int>(x[2]), static_cast<int>(x[3]),
+               static_cast<int>(y[0]), static_cast<int>(y[1]), static_cast<int>(y[2]), static_cast<int>(y[3])};
+}
+
+// One 16-token block of a page as the B operand, with the scale of the lane's token n.  `phys` is a device value: a block at
+// or past the end of the piece (-1), -1 padding and a poisoned id are not ok, and such a page is never loaded.
+struct KeyBlock {
+  i32x8 kv;
+  float sc;
+  bool ok;
+};
+__device__ __forceinline__ KeyBlock load_key_block(const uint8_t* cache, long cache_bs, long scales_at, int phys, int num_blocks,
+                                                   int t, int g) {
+  KeyBlock k{i32x8{0, 0, 0, 0, 0, 0, 0, 0}, 0.f, phys >= 0 && phys < num_blocks};
+  if (k.ok) {
+    const uint8_t* page = cache + phys * cache_bs;
+    k.kv = operand32(ld16(page + t * kIdxDim + 32 * g), ld16(page + t * kIdxDim + 32 * g + 16));
+    k.sc = *reinterpret_cast<const float*>(page + scales_at + 4 * t);
+  }
+  return k;
+}
+
+// sum_h w[h] * relu(q[h] . key) of the lane's token, before the key's scale: per lane the fmaf chain over the head blocks and
+// the lane's four heads, then the xor-16 and xor-32 steps - a fixed order, no atomics
+template <int kHB>
+__device__ __forceinline__ float head_sum(const i32x8 (&qf)[kHB], const f32x4 (&wt)[kHB], const i32x8 kv) {
+  float acc = 0.f;
+#pragma unroll
+  for (int hb = 0; hb < kHB; ++hb) {
+    const f32x4 d = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(qf[hb], kv, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc = fmaf(wt[hb][i], fmaxf(d[i], 0.f), acc);
+  }
+  acc += __shfl_xor(acc, 16, 64);
+  acc += __shfl_xor(acc, 32, 64);
+  return acc;
+}
+__device__ __forceinline__ float key_logit(const KeyBlock& k, float acc) { return k.ok ? k.sc * acc : -__builtin_inff(); }
+
+// The ragged row rule of the readers: what row `row` of a chunk sees, vis = min(pos + 1, cols) for a live row and 0 for a row
+// of no request; req is a request of the call either way (locate_row)
+struct RowSees {
+  int req, vis;
+};
+__device__ __forceinline__ RowSees row_sees(const int* q_index, const int* seqlen, int num_req, int row, int cols) {
+  const RowAt at = locate_row(q_index, seqlen, num_req, row);
+  return {at.req, at.live ? clamp_len(at.pos + 1, cols) : 0};
 }
 
 }  // namespace mla_indexer

@@ -1,7 +1,8 @@
 // The DSA lightning indexer (mla_indexer.hip), stated once: the paged index-key cache, the host rule for a cache a launcher
 // accepts, the one route of the logits / top-k ops - the grid, the chunking of the context, the scratch of the fused call and
-// every refusal with its reason in words - and the one host rule of the front end (mla_indexer_prep.hip) at the end.
-// Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip and mla_indexer_prep.hip, hpc_mla_indexer_plan
+// every refusal with its reason in words -, the one route of the same ops over a ragged prefill chunk (mla_indexer_prefill.hip:
+// row tile, chunk, grid, slab, scratch, refusals) and the one host rule of the front end (mla_indexer_prep.hip) at the end.
+// Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip, mla_indexer_prefill.hip and mla_indexer_prep.hip, hpc_mla_indexer_plan
 // and the torch shim (torch_mla_indexer.cpp) all read it.
 //
 // The index-key cache.  Every token of every request has ONE index key of 128 columns, shared by all index heads: 128
@@ -101,6 +102,91 @@ static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, in
   const int64_t grid = static_cast<int64_t>(num_batch) * r.chunks;
   if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
   r.grid = static_cast<int>(grid);
+  return r;
+}
+
+// ---- a ragged prefill chunk (mla_indexer_prefill.hip: logits; mla_indexer.hip: top-k) -------------------------------------------
+// The rows of a chunk follow the writers' row rule (mla_indexer_dev.h::locate_row), read on the device.  The logits kernel is
+// key-stationary: a workgroup stages a tile of kIdxPrefillTile q rows (codes and weights) in LDS once and runs all of them
+// against every 64-key step of its chunk of columns, so a key tile is loaded once per row tile.  Tiles are cut from the row
+// index of the call, not per request, which makes the grid a host value: ceil(rows / tile) * chunks; the chunking of the columns
+// is the decode route's - 512, doubled up to 8192 while the grid is beyond 16 workgroups per CU - with the tile count in the
+// place of the request count.
+// The fused call runs logits then top-k over slabs of rows through one float32 scratch [slab_rows, cols]; the slab is the
+// caller's (scratch_rows > 0) or, with 0, what fits kIdxPrefillScratchBytes.  That budget is a resource cap, not a tuned number:
+// 256 MiB holds the logits of a 2048-row slab over a 32k-token table, so that the scratch does not grow with the chunk while a
+// slab still fills the device many times over; nothing was measured to pick it.
+constexpr int kIdxPrefillTile = 16;  // q rows of a workgroup: 16 x Hi x 132 B of LDS, 132 KiB at Hi = 64 of the 160 KiB
+constexpr int kIdxPrefillWaves = 8;  // waves of a workgroup, two per SIMD: each takes 64 of every 512 columns of the chunk
+constexpr int64_t kIdxPrefillScratchBytes = int64_t{256} << 20;
+constexpr int64_t kIdxPrefillMaxScratchBytes = int64_t{1} << 40;  // a caller's slab beyond 1 TiB of logits is refused (and the
+                                                                  // product slab_rows * cols * 4 stays far inside int64)
+constexpr int64_t mla_indexer_prefill_lds_bytes(int num_head) { return int64_t{kIdxPrefillTile} * num_head * kIdxTokenBytes; }
+
+struct MlaIndexerPrefillRoute {
+  int code;          // HPC_OK or the refusal; the rest is set either way (zeros where it has no meaning)
+  const char* why;   // the refusal in words (null when accepted)
+  int head_blocks;   // num_head / 16
+  int64_t cols;      // max_blocks * block_size: the logits' columns
+  int tile;          // q rows of a logits workgroup
+  int tiles;         // ceil(num_rows / tile) of a logits call over all num_rows rows
+  int chunk;         // columns one logits workgroup owns (a multiple of 512), chosen for a launch over a whole slab (logits op:
+                     // over all rows).  The fused call launches the logits once per slab and each launch routes itself from
+                     // its own rows and the device's CU count: a partial last slab may take a shorter chunk.  No logit
+                     // depends on the chunk.
+  int chunks;        // ceil(cols / chunk)
+  int grid;          // workgroups of ONE logits launch over num_rows rows at that chunk: id = tile * chunks + piece; 0: nothing
+                     // to launch.  The fused call's launches together have as many tiles, each slab's rounded up
+  int topk_grid;     // top-k workgroups: one per row
+  int slab_rows;     // rows of a slab of the fused call
+  int slabs;         // ceil(num_rows / slab_rows): a host value
+  MlaIndexerScratch scratch;  // of the fused call: [slab_rows, cols] float32, never zeroed
+};
+
+// logits_only: topk and scratch_rows are not looked at.  The chunk is chosen from rows_per_call, the rows one logits launch
+// takes: num_rows for the logits op, a slab for the fused one.  cu_count <= 0: 256.
+static inline MlaIndexerPrefillRoute mla_indexer_prefill_route(int num_rows, int num_req, int num_head, int block_size, int max_blocks,
+                                                               int topk, bool logits_only, int scratch_rows, int cu_count) {
+  MlaIndexerPrefillRoute r{};
+  const auto refuse = [&](int code, const char* why) {
+    r.code = code;
+    r.why = why;
+    return r;
+  };
+  if (num_rows < 0 || num_req < 0) return refuse(HPC_ERR_INVALID, "num_rows and num_req must not be negative");
+  if (max_blocks < 0) return refuse(HPC_ERR_INVALID, "max_blocks must not be negative");
+  if (!logits_only && scratch_rows < 0) return refuse(HPC_ERR_INVALID, "scratch_rows must be 0 (the library chooses) or a row count");
+  if (num_head != 16 && num_head != 32 && num_head != 64) return refuse(HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64");
+  if (mla_page_shift(block_size) < 0) return refuse(HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128");
+  if (!logits_only && (topk < 1 || topk > kIdxMaxTopk)) return refuse(HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536");
+  if (num_req == 0x7fffffff) return refuse(HPC_ERR_UNSUPPORTED, "num_req + 1 beyond int32");
+  r.head_blocks = num_head / 16;
+  r.cols = static_cast<int64_t>(max_blocks) * block_size;
+  if (r.cols > kIdxMaxCols) return refuse(HPC_ERR_UNSUPPORTED, "block_ids reaches beyond 2^30 tokens");
+  r.tile = kIdxPrefillTile;
+  r.tiles = static_cast<int>((static_cast<int64_t>(num_rows) + r.tile - 1) / r.tile);
+  r.topk_grid = num_rows;
+  // the slab: the caller's, or the rows the budget holds, in whole tiles and at least one; never more than the chunk has
+  int64_t slab = num_rows;
+  if (!logits_only) {
+    slab = scratch_rows > 0 ? scratch_rows : kIdxPrefillScratchBytes / 4 / (r.cols > 0 ? r.cols : 1) / r.tile * r.tile;
+    slab = slab < r.tile && scratch_rows == 0 ? r.tile : slab;
+    slab = slab > num_rows ? num_rows : slab;
+  }
+  if (slab > kIdxPrefillMaxScratchBytes / 4 / (r.cols > 0 ? r.cols : 1))
+    return refuse(HPC_ERR_UNSUPPORTED, "scratch_rows * max_blocks * block_size * 4 beyond 2^40 bytes of scratch");
+  r.slab_rows = static_cast<int>(slab);
+  r.slabs = slab > 0 ? static_cast<int>((num_rows + slab - 1) / slab) : 0;
+  r.scratch = mla_indexer_scratch(logits_only ? 0 : slab, r.cols);
+  const int cus = cu_count > 0 ? cu_count : 256;
+  const int64_t call_tiles = (slab + r.tile - 1) / r.tile;
+  int64_t chunk = kIdxMinChunk;
+  while (chunk < kIdxMaxChunk && call_tiles * ((r.cols + chunk - 1) / chunk) > 16ll * cus) chunk *= 2;
+  r.chunk = static_cast<int>(chunk);
+  r.chunks = static_cast<int>((r.cols + chunk - 1) / chunk);
+  const int64_t grid = static_cast<int64_t>(r.tiles) * r.chunks;
+  if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
+  r.grid = num_req > 0 ? static_cast<int>(grid) : 0;
   return r;
 }
 

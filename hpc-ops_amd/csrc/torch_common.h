@@ -112,7 +112,8 @@ inline void check_noise(const c10::optional<at::Tensor>& g, int64_t b, int64_t v
 // serves the calls of that capture and nothing else, the entries of earlier (ended) captures on the stream are dropped on
 // the next call (their memory stays with their graph's pool), and a buffer cached by eager calls is not used inside a capture - every graph
 // owns its buffer and its zero node.
-enum ScratchPurpose { kScratchDecode = 0, kScratchGemmFlags = 1, kScratchLinear = 2, kScratchMla = 3, kScratchMlaIndexer = 4 };
+enum ScratchPurpose { kScratchDecode = 0, kScratchGemmFlags = 1, kScratchLinear = 2, kScratchMla = 3, kScratchMlaIndexer = 4,
+                      kScratchMlaIndexerPrefill = 5 };
 using ScratchKey = std::tuple<int, int, void*, long long>;
 inline std::mutex& scratch_mutex() {
   static std::mutex mu;
@@ -150,7 +151,8 @@ inline at::Tensor cached_scratch(int purpose, const at::Tensor& like, int64_t nb
   return it->second;
 }
 // Drops EVERY cached scratch buffer of every purpose: the decode workspaces, the router GEMM's split-K ticket buffers AND
-// the dense FP8 linear's tickets + planes, the MLA decode's split-KV partials and the MLA indexer's logits
+// the dense FP8 linear's tickets + planes, the MLA decode's split-KV partials and the MLA indexer's logits (a decode step's and
+// a prefill slab's)
 // (hpc.release_decode_workspaces documents them).
 inline void release_cached_scratch() {
   std::lock_guard<std::mutex> lock(scratch_mutex());

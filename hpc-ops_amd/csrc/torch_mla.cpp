@@ -10,8 +10,11 @@
 // the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
 // kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  attention_decode_mla_sparse_{bf16,fp8} are the decode
 // attention over a list of token positions per q row (the same kernel source, its kSparse form, and here the same body as the
-// dense ops: decode_mla<kFp8>, the list null or given).  Either side of the decode
+// dense ops: decode_mla<kFp8>, the list null or given), and attention_prefill_mla_sparse_{bf16,fp8} that kernel over a ragged
+// prefill chunk (the writers' row rule instead of mtp).  Either side of the decode
 // attention the two absorb matmuls, absorb_q and unabsorb_o (csrc/mla_absorb.hip).  No kernels here.
+#include <limits>
+
 #include "byte_span.h"
 #include "mla_cache.h"
 #include "torch_common.h"
@@ -183,6 +186,66 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_sparse(const at::Tensor&
                                                                int64_t splits) {
   return decode_mla<kFp8>(q, ckv_cache, block_ids, num_seq_kvcache, &indices, softmax_scale, mtp, new_kv_included, output,
                           output_lse, return_lse, splits);
+}
+
+// ---- attention_prefill_mla_sparse_{bf16,fp8}: the token-sparse attention over a ragged prefill chunk ---------------------------
+// The decode op's kernel, route and scratch with the writers' row rule (num_seqlen_per_req, q_index) as the source of a row's
+// request and of what it sees (tests/mla_indexer_prefill_ref.py: the sparse statement on the expanded form).  Nothing here reads
+// the values of num_seqlen_per_req, q_index, block_ids or indices.
+template <bool kFp8>
+std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_sparse(const at::Tensor& q, const at::Tensor& ckv_cache,
+                                                                const at::Tensor& block_ids, const at::Tensor& num_seqlen_per_req,
+                                                                const at::Tensor& q_index, const at::Tensor& indices,
+                                                                double softmax_scale, const c10::optional<at::Tensor>& output,
+                                                                const c10::optional<at::Tensor>& output_lse, bool return_lse,
+                                                                int64_t splits) {
+  const char* op = kFp8 ? "attention_prefill_mla_sparse_fp8" : "attention_prefill_mla_sparse_bf16";
+  cuda_contig(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [rows, num_head, 576]");
+  const int64_t t = q.size(0), h = q.size(1);
+  TORCH_CHECK(ckv_cache.is_cuda() && ckv_cache.device() == q.device(), "ckv_cache must be a cuda tensor on q's device");
+  check_table(num_seqlen_per_req, "num_seqlen_per_req", q, at::kInt, {-1});
+  const int64_t req = num_seqlen_per_req.size(0);
+  check_table(q_index, "q_index", q, at::kInt, {req + 1});
+  check_table(block_ids, "block_ids", q, at::kInt, {req, -1});
+  TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
+  check_table(indices, "indices", q, at::kInt, {t, -1});
+  const int64_t topk = indices.size(1);
+  TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [rows, topk] with 1 <= topk <= 65536, got topk = ", topk);
+  check_cache(ckv_cache, kCache<kFp8>);
+  const int64_t page = ckv_cache.size(1);
+  TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
+  TORCH_CHECK(ckv_cache.size(0) <= INT32_MAX && t <= INT32_MAX && req < INT32_MAX, "sizes beyond int32");
+  TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
+  at::Tensor out = out_or_new(output, q, {t, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
+  const bool want_lse = return_lse || output_lse.has_value();
+  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {t, h}, at::kFloat, "output_lse", kOnInputDevice)
+                            : at::empty({0}, q.options().dtype(at::kFloat));
+  int s = 0, max_splits = 0;
+  int64_t ws_bytes = 0;
+  const int wanted = i32(std::min<int64_t>(splits, INT32_MAX)), cus = t > 0 ? hpc_get_cu_count(q.device().index()) : 256;
+  const int rc_plan =
+      hpc_attention_decode_mla_sparse_plan(i32(t), 1, i32(h), i32(topk), wanted, cus, &s, &max_splits, &ws_bytes, nullptr, nullptr);
+  TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a list may be cut into");
+  HPC_LAUNCH_CHECK(rc_plan, op);
+  if (t == 0) return {out, lse};
+  if (req == 0) {  // every row is a row of no request: the empty row
+    out.zero_();
+    if (want_lse) lse.fill_(-std::numeric_limits<float>::infinity());
+    return {out, lse};
+  }
+  TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
+  at::Tensor ws;
+  if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: every launched piece writes all of its rows
+  const auto ip = [](const at::Tensor& x) { return static_cast<const int*>(x.data_ptr()); };
+  const int rc = (kFp8 ? hpc_attention_prefill_mla_sparse_fp8_async : hpc_attention_prefill_mla_sparse_bf16_async)(
+      ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache), ip(block_ids), ip(num_seqlen_per_req),
+      ip(q_index), ip(indices), i32(t), i32(req), i32(h), i32(topk), i32(page), i32(block_ids.size(1)), i32(ckv_cache.size(0)),
+      ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale), s, s > 1 ? ws.data_ptr() : nullptr, ws_bytes,
+      stream_of(q));
+  HPC_LAUNCH_CHECK(rc, op);
+  return {out, lse};
 }
 
 // ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------
@@ -466,6 +529,12 @@ TORCH_LIBRARY(hpc_mla, m) {
       "float softmax_scale, int mtp, bool new_kv_included, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> "
       "(Tensor, Tensor)");
   m.def(
+      "attention_prefill_mla_sparse_bf16(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seqlen_per_req, Tensor q_index, "
+      "Tensor indices, float softmax_scale, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
+  m.def(
+      "attention_prefill_mla_sparse_fp8(Tensor q, Tensor ckv_cache, Tensor block_ids, Tensor num_seqlen_per_req, Tensor q_index, "
+      "Tensor indices, float softmax_scale, Tensor? output, Tensor? output_lse, bool return_lse, int splits) -> (Tensor, Tensor)");
+  m.def(
       "attention_prefill_mla_bf16(Tensor q, Tensor k_nope, Tensor k_pe, Tensor v, Tensor cu_seqlens_q, int max_seqlens_q, "
       "float softmax_scale, Tensor? cu_seqlens_k, int? max_seqlens_k, bool causal, Tensor? output, Tensor? output_lse, "
       "bool return_lse) -> (Tensor, Tensor)");
@@ -487,6 +556,8 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("rope_norm_store_kv_fp8", &rope_norm_store_kv<true>);
   m.impl("attention_decode_mla_sparse_bf16", &attention_decode_mla_sparse<false>);
   m.impl("attention_decode_mla_sparse_fp8", &attention_decode_mla_sparse<true>);
+  m.impl("attention_prefill_mla_sparse_bf16", &attention_prefill_mla_sparse<false>);
+  m.impl("attention_prefill_mla_sparse_fp8", &attention_prefill_mla_sparse<true>);
   m.impl("attention_prefill_mla_bf16", &attention_prefill_mla_bf16);
   m.impl("merge_attn_states", &merge_attn_states);
   m.impl("gather_ckv", &gather_ckv<false>);

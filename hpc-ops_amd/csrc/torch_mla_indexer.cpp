@@ -4,7 +4,9 @@
 // checked here; the cache's rule, the
 // limits, strides and alignment are the launchers' (csrc/mla_indexer_route.h) and come back in their words through
 // hpc_mla_indexer_*_refusal.  Nothing here reads the values of a length, a page table or a logit; with `output` given nothing is
-// allocated per call beyond the cached scratch of the fused op and the calls capture into a hipGraph.  No kernels here.
+// allocated per call beyond the cached scratch of the fused op and the calls capture into a hipGraph.  Behind them the same three
+// over a ragged prefill chunk (csrc/mla_indexer_prefill.hip): mla_indexer_logits_prefill_fp8, mla_indexer_topk_prefill and the
+// fused mla_indexer_topk_prefill_fp8 over row slabs.  No kernels here.
 #include "mla_indexer_route.h"
 #include "torch_common.h"
 
@@ -161,6 +163,108 @@ at::Tensor topk_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Te
   return out;
 }
 
+// ---- the same three over a ragged prefill chunk (csrc/mla_indexer_prefill.hip), pinned to tests/mla_indexer_prefill_ref.py --------
+struct ChunkDims {
+  int64_t rows, req, h, page, max_blocks;
+};
+void check_row_rule(const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, const at::Tensor& like, int64_t row_begin) {
+  check_table(num_seqlen_per_req, "num_seqlen_per_req", like, 1);
+  check_table(q_index, "q_index", like, 1);
+  TORCH_CHECK(q_index.size(0) == num_seqlen_per_req.size(0) + 1, "q_index must be [num_req + 1] = [", num_seqlen_per_req.size(0) + 1, "]");
+  TORCH_CHECK(row_begin >= 0 && row_begin <= INT32_MAX, "row_begin must be a row of the chunk, got ", row_begin);
+}
+ChunkDims check_chunk_reader(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                             const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t row_begin) {
+  TORCH_CHECK(q.is_cuda(), "q tensor must be cuda");
+  TORCH_CHECK(q.scalar_type() == kF8, "q dtype must be float8_e4m3fn");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kIdxDim && q.is_contiguous(), "q must be a contiguous [rows, num_head, 128]");
+  const int64_t rows = q.size(0), h = q.size(1);
+  check_on(weights, "weights", q, at::kFloat, "float32");
+  TORCH_CHECK(weights.dim() == 2 && weights.size(0) == rows && weights.size(1) == h && weights.is_contiguous(),
+              "weights must be a contiguous [rows, num_head] = [", rows, ", ", h, "]");
+  check_row_rule(num_seqlen_per_req, q_index, q, row_begin);
+  const int64_t req = num_seqlen_per_req.size(0);
+  check_table(block_ids, "block_ids", q, 2);
+  TORCH_CHECK(block_ids.size(0) == req, "block_ids must have num_req = ", req, " rows");
+  const int64_t page = check_cache(k_cache, q);
+  TORCH_CHECK(rows <= INT32_MAX && req < INT32_MAX && h <= INT32_MAX && block_ids.size(1) <= INT32_MAX, "sizes beyond int32");
+  return {rows, req, h, page, block_ids.size(1)};
+}
+
+at::Tensor logits_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                              const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t row_begin,
+                              const c10::optional<at::Tensor>& output) {
+  const ChunkDims d = check_chunk_reader(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, row_begin);
+  const int64_t cols = d.max_blocks * d.page;
+  at::Tensor out = out_or_new(output, q, {d.rows, cols}, at::kFloat, "output", kOnInputDevice);
+  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
+  const char* why = hpc_mla_indexer_logits_prefill_fp8_refusal(
+      static_cast<const float*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
+      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(row_begin), i32(d.h), i32(d.page), i32(d.max_blocks),
+      i32(k_cache.size(0)), block_stride(k_cache), cols);
+  TORCH_CHECK(why == nullptr, "mla_indexer_logits_prefill_fp8: ", why);
+  if (d.rows == 0 || d.req == 0) return out;  // nothing to launch
+  const int rc = hpc_mla_indexer_logits_prefill_fp8_async(
+      static_cast<float*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
+      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(row_begin), i32(d.h), i32(d.page), i32(d.max_blocks),
+      i32(k_cache.size(0)), block_stride(k_cache), cols, stream_of(q));
+  HPC_LAUNCH_CHECK(rc, "mla_indexer_logits_prefill_fp8");
+  return out;
+}
+
+at::Tensor topk_prefill(const at::Tensor& logits, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk,
+                        int64_t row_begin, const c10::optional<at::Tensor>& output) {
+  TORCH_CHECK(logits.is_cuda(), "logits tensor must be cuda");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32");
+  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1), "logits must be [rows, columns] with a contiguous last dim");
+  check_row_rule(num_seqlen_per_req, q_index, logits, row_begin);
+  const int64_t rows = logits.size(0), cols = logits.size(1), req = num_seqlen_per_req.size(0);
+  TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
+  TORCH_CHECK(rows <= INT32_MAX && req < INT32_MAX, "sizes beyond int32");
+  at::Tensor out = out_or_new(output, logits, {rows, topk}, at::kInt, "output", kOnInputDevice);
+  const int64_t rs = rows > 1 ? logits.stride(0) : cols;
+  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
+  const char* why = hpc_mla_indexer_topk_prefill_refusal(ip(out), static_cast<const float*>(logits.data_ptr()), ip(num_seqlen_per_req),
+                                                         ip(q_index), i32(rows), i32(req), i32(row_begin), cols, i32(topk), rs);
+  TORCH_CHECK(why == nullptr, "mla_indexer_topk_prefill: ", why);
+  if (rows == 0) return out;  // nothing to launch
+  if (req == 0) return out.fill_(-1);  // every row is a row of no request
+  const int rc = hpc_mla_indexer_topk_prefill_async(static_cast<int*>(out.data_ptr()), static_cast<const float*>(logits.data_ptr()),
+                                                    ip(num_seqlen_per_req), ip(q_index), i32(rows), i32(req), i32(row_begin), cols,
+                                                    i32(topk), rs, stream_of(logits));
+  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk_prefill");
+  return out;
+}
+
+// the two over row slabs through the cached scratch, whose layout and slab are mla_indexer_prefill_route()'s
+at::Tensor topk_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                            const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk, int64_t scratch_rows,
+                            const c10::optional<at::Tensor>& output) {
+  const ChunkDims d = check_chunk_reader(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, 0);
+  TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
+  TORCH_CHECK(scratch_rows >= 0 && scratch_rows <= INT32_MAX, "scratch_rows must be 0 (the library chooses) or a row count, got ", scratch_rows);
+  at::Tensor out = out_or_new(output, q, {d.rows, topk}, at::kInt, "output", kOnInputDevice);
+  const bool work = d.rows > 0 && d.req > 0;
+  const hpc::MlaIndexerPrefillRoute r = hpc::mla_indexer_prefill_route(i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks),
+                                                                       i32(topk), false, i32(scratch_rows), 256);
+  at::Tensor ws;
+  if (work && r.code == HPC_OK) ws = cached_scratch(kScratchMlaIndexerPrefill, q, std::max<int64_t>(r.scratch.bytes, 16), 0);  // never zeroed
+  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
+  const char* why = hpc_mla_indexer_topk_prefill_fp8_refusal(
+      ip(out), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids), ip(num_seqlen_per_req), ip(q_index),
+      i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), i32(topk),
+      i32(scratch_rows), ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? ws.numel() : 0);
+  TORCH_CHECK(why == nullptr, "mla_indexer_topk_prefill_fp8: ", why);
+  if (d.rows == 0) return out;  // nothing to launch
+  if (d.req == 0) return out.fill_(-1);  // every row is a row of no request
+  const int rc = hpc_mla_indexer_topk_prefill_fp8_async(
+      static_cast<int*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
+      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)),
+      block_stride(k_cache), i32(topk), i32(scratch_rows), ws.data_ptr(), ws.numel(), stream_of(q));
+  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk_prefill_fp8");
+  return out;
+}
+
 // ---- mla_indexer_prep_fp8: the front end (csrc/mla_indexer_prep.hip), pinned to tests/mla_indexer_prep_ref.py -------------------------
 // Returns (q8, weights): the caller's out_q / out_weights or fresh contiguous ones; two empty tensors without q.  With the
 // outputs given (or no q) nothing is allocated.  The host rule and its words are mla_indexer_prep_route's.
@@ -261,6 +365,16 @@ TORCH_LIBRARY_FRAGMENT(hpc_mla, m) {
       "Tensor num_seqlen_per_req, Tensor q_index, Tensor block_ids, Tensor? q, Tensor? head_weights, float? softmax_scale, float eps, "
       "bool interleaved, float rotate_scale, bool pow2_scale, Tensor? out_k, Tensor? out_q, Tensor? out_weights, Tensor? out_q_rot) "
       "-> (Tensor, Tensor)");
+  m.def(
+      "mla_indexer_logits_prefill_fp8(Tensor q, Tensor weights, Tensor k_cache, Tensor block_ids, Tensor num_seqlen_per_req, "
+      "Tensor q_index, int row_begin, Tensor? output) -> Tensor");
+  m.def(
+      "mla_indexer_topk_prefill(Tensor logits, Tensor num_seqlen_per_req, Tensor q_index, int topk, int row_begin, Tensor? output) "
+      "-> Tensor");
+  m.def(
+      "mla_indexer_topk_prefill_fp8(Tensor q, Tensor weights, Tensor k_cache, Tensor block_ids, Tensor num_seqlen_per_req, "
+      "Tensor q_index, int topk, int scratch_rows, Tensor? output) -> Tensor");
+  m.def("_mla_indexer_prefill_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMlaIndexerPrefill); });
   // the cached logits scratch of the fused op (tests fill it with NaN bytes: no column that was not written may be read)
   m.def("_mla_indexer_workspaces() -> Tensor[]", []() { return list_cached_scratch(kScratchMlaIndexer); });
 }
@@ -271,4 +385,7 @@ TORCH_LIBRARY_IMPL(hpc_mla, CUDA, m) {
   m.impl("mla_indexer_topk", &select_topk);
   m.impl("mla_indexer_topk_fp8", &topk_fp8);
   m.impl("mla_indexer_prep_fp8", &prep_fp8);
+  m.impl("mla_indexer_logits_prefill_fp8", &logits_prefill_fp8);
+  m.impl("mla_indexer_topk_prefill", &topk_prefill);
+  m.impl("mla_indexer_topk_prefill_fp8", &topk_prefill_fp8);
 }

@@ -116,6 +116,15 @@ _sig("hpc_mla_indexer_topk_refusal", c_char_p, P, P, IP, I, I, L, I, L)
 _sig("hpc_mla_indexer_topk_async", I, P, P, IP, I, I, L, I, L, I, P)
 _sig("hpc_mla_indexer_topk_fp8_refusal", c_char_p, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, P, L)
 _sig("hpc_mla_indexer_topk_fp8_async", I, P, P, P, P, IP, IP, I, I, I, I, I, I, L, I, I, P, L, P)
+_sig("hpc_mla_indexer_prefill_plan", I, I, I, I, I, I, I, I, I, IP, IP, IP, IP, IP, LP, LP)
+_sig("hpc_mla_indexer_logits_prefill_fp8_refusal", c_char_p, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L)
+_sig("hpc_mla_indexer_logits_prefill_fp8_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, P)
+_sig("hpc_mla_indexer_topk_prefill_refusal", c_char_p, P, P, IP, IP, I, I, I, L, I, L)
+_sig("hpc_mla_indexer_topk_prefill_async", I, P, P, IP, IP, I, I, I, L, I, L, P)
+_sig("hpc_mla_indexer_topk_prefill_fp8_refusal", c_char_p, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, L, I, I, P, L)
+_sig("hpc_mla_indexer_topk_prefill_fp8_async", I, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, L, I, I, P, L, P)
+_sig("hpc_attention_prefill_mla_sparse_bf16_async", I, P, P, P, P, IP, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, P, L, P)
+_sig("hpc_attention_prefill_mla_sparse_fp8_async", I, P, P, P, P, IP, IP, IP, IP, I, I, I, I, I, I, I, L, L, F, I, P, L, P)
 _sig("hpc_mla_indexer_prep_fp8_refusal", c_char_p, P, P, P, P, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, I, F, F, F)
 _sig("hpc_mla_indexer_prep_fp8_async", I, P, P, P, P, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, I, F, F, F, I, I, P)
 _sig("hpc_mla_rope_norm_store_kv_async", I, P, P, P, P, P, P, P, IP, IP, IP, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P)

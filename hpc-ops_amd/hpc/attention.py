@@ -128,7 +128,7 @@ def task_workspace_bytes(num_cu, max_num_batch, max_seqlen, num_head_kv, min_pro
 def release_decode_workspaces():
     """Drop EVERY zero-once scratch buffer the host library caches per (purpose, device, stream, hipGraph capture) - the
     decode workspaces, the router GEMM's split-K ticket buffers, the MLA decode's split-KV partials and the MLA indexer's
-    logits alike (csrc/torch_common.h::release_cached_scratch) -
+    logits (a decode step's and a prefill slab's) alike (csrc/torch_common.h::release_cached_scratch) -
     e.g. after the streams / graphs that used them are gone.  Buffers of captures that have ended are dropped on the
     next call on their stream anyway."""
     torch.ops.hpc._release_decode_workspaces()
@@ -520,6 +520,67 @@ def attention_decode_mla_sparse_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Ten
 
 
 torch.library.register_fake("hpc_mla::attention_decode_mla_sparse_fp8")(_attention_decode_mla_sparse_fake)
+
+
+def attention_prefill_mla_sparse_bf16(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seqlen_per_req: Tensor,
+                                      q_index: Tensor, indices: Tensor, softmax_scale: float, *, output: Tensor = None,
+                                      output_lse: Tensor = None, return_lse: bool = False, splits: int = 0):
+    """Token-sparse MLA attention of a ragged PREFILL chunk over the paged latent KV cache, bfloat16: every prompt token
+    attends to the cache tokens its list names (DeepSeek-V3.2 / DSA: the top-2048 of hpc.mla_indexer_topk_prefill_fp8).
+    Returns out bf16 [T, H, 512], or (out, lse) with return_lse or output_lse - what hpc.mla_unabsorb_o and
+    hpc.merge_attn_states take.
+
+    attention_decode_mla_sparse_bf16 with the writers' row rule in the place of mtp; semantics = tests/mla_sparse_ref.py on
+    the expanded form (tests/mla_indexer_prefill_ref.py: every row its own one-row request).
+
+    row rule         that of mla_rope_norm_store_kv / mla_indexer_prep_fp8: row r of the chunk belongs to the last request
+                     b with q_index[b] <= r, at pos = num_seqlen_per_req[b] - (q_index[b + 1] - r).  num_seqlen_per_req
+                     int32 [num_req] (total lengths INCLUDING the chunk's tokens, whose rows are in the cache), q_index
+                     int32 [num_req + 1], block_ids int32 [num_req, max_blocks]; all on the device, never read on the
+                     host.  A live row sees vis(r) = min(pos + 1, max_blocks * P) tokens: causal inside the chunk, all
+                     of the cached context before it - chunked prefill and prefix caching need nothing extra.
+    row of no        a row at or past q_index[-1] or with pos < 0: an empty row.
+    request
+    q, indices       bf16 [T, H, 576] and int32 [T, topk]: row r's list names LOGICAL positions of its request.
+
+    The valid-entry rule (0 <= idx_k < vis(r), inside the page table, page id in [0, num_blocks)), the duplicate rule, the
+    empty row (out = 0, lse = -inf), the splits rule over the list (0 .. 64), the limits (H % 16 == 0, 16 <= H <= 128;
+    P in {16, 32, 64, 128}; 1 <= topk <= 65536), the cached scratch that hpc.release_decode_workspaces() drops and
+    hipGraph capture with caller-provided outputs are attention_decode_mla_sparse_bf16's: the same kernel, one workgroup
+    per row, 64 heads and piece.  With q_index = [0, Sq, 2 Sq, ...] the result is bit-identical to that op at mtp = Sq - 1
+    and the same splits, and on any chunk to that op on the expanded form.  T == 0 returns empty tensors without a
+    launch; num_req == 0 makes every row an empty row."""
+    out, lse = torch.ops.hpc_mla.attention_prefill_mla_sparse_bf16(q, ckv_cache, block_ids, num_seqlen_per_req, q_index, indices,
+                                                                   float(softmax_scale), output, output_lse, bool(return_lse),
+                                                                   int(splits))
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
+
+
+@torch.library.register_fake("hpc_mla::attention_prefill_mla_sparse_bf16")
+def _attention_prefill_mla_sparse_fake(q, ckv_cache, block_ids, num_seqlen_per_req, q_index, indices, softmax_scale, output=None,
+                                       output_lse=None, return_lse=False, splits=0):
+    return _attention_decode_mla_bf16_fake(q, ckv_cache, block_ids, num_seqlen_per_req, softmax_scale, 0, True, output, output_lse,
+                                           return_lse, splits)
+
+
+def attention_prefill_mla_sparse_fp8(q: Tensor, ckv_cache: Tensor, block_ids: Tensor, num_seqlen_per_req: Tensor,
+                                     q_index: Tensor, indices: Tensor, softmax_scale: float, *, output: Tensor = None,
+                                     output_lse: Tensor = None, return_lse: bool = False, splits: int = 0):
+    """attention_prefill_mla_sparse_bf16 over the FP8 latent KV cache of attention_decode_mla_fp8 (torch.uint8, logical
+    [num_blocks, P, 656]).  Returns out bf16 [T, H, 512], or (out, lse) with return_lse or output_lse.
+
+    The row rule (num_seqlen_per_req, q_index, rows of no request), the lists and every other rule are those of
+    attention_prefill_mla_sparse_bf16; the cache, its dequantisation c[d] = bf16_rne( fp32(code[d]) * scale[d // 128] ) and
+    its stride rule are attention_decode_mla_sparse_fp8's.  For given shapes, splits and CU count the result is
+    bit-identical to attention_decode_mla_sparse_fp8 on the expanded form, and bit-identical from call to call; the call
+    captures into a hipGraph with caller-provided outputs."""
+    out, lse = torch.ops.hpc_mla.attention_prefill_mla_sparse_fp8(q, ckv_cache, block_ids, num_seqlen_per_req, q_index, indices,
+                                                                  float(softmax_scale), output, output_lse, bool(return_lse),
+                                                                  int(splits))
+    return _decode_mla_result(out, lse, output, output_lse, return_lse)
+
+
+torch.library.register_fake("hpc_mla::attention_prefill_mla_sparse_fp8")(_attention_prefill_mla_sparse_fake)
 
 
 def attention_prefill_mla_bf16(q: Tensor, k_nope: Tensor, k_pe: Tensor, v: Tensor, cu_seqlens_q: Tensor, max_seqlens_q: int,

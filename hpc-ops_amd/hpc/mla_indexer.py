@@ -131,6 +131,83 @@ def _mla_indexer_topk_fp8_fake(q, weights, k_cache, block_ids, num_seq_kvcache, 
     return output if output is not None else q.new_empty((q.shape[0], topk), dtype=torch.int32)
 
 
+def mla_indexer_logits_prefill_fp8(q: Tensor, weights: Tensor, k_cache: Tensor, block_ids: Tensor, num_seqlen_per_req: Tensor,
+                                   q_index: Tensor, *, row_begin: int = 0, output: Tensor = None) -> Tensor:
+    """The indexer's FP8 MQA logits of a ragged PREFILL chunk over the paged index-key cache.  Returns float32
+    [R, max_blocks * P].
+
+    mla_indexer_logits_fp8 with the writers' row rule in the place of mtp; semantics = tests/mla_indexer_ref.py applied to
+    the expanded form of tests/mla_indexer_prefill_ref.py (every row its own one-row request of length pos + 1).
+
+    row rule         that of mla_indexer_prep_fp8 / mla_indexer_store_k_fp8: row r of the chunk belongs to the last request b
+                     with q_index[b] <= r, at pos = num_seqlen_per_req[b] - (q_index[b + 1] - r).  num_seqlen_per_req int32
+                     [num_req] (total lengths INCLUDING the chunk's tokens), q_index int32 [num_req + 1], block_ids int32
+                     [num_req, max_blocks]: on the device, never read on the host.  A row at or past q_index[-1] or with
+                     pos < 0 is a row of no request.  A live row sees vis(r) = min(pos + 1, max_blocks * P) tokens: causal
+                     inside the chunk, all of the cached context before it (chunked prefill, prefix caching).
+    q, weights       float8_e4m3fn [R, Hi, 128] and float32 [R, Hi], Hi in {16, 32, 64}, exactly what mla_indexer_prep_fp8
+                     returns: the chunk's rows row_begin .. row_begin + R - 1, so a caller can bound the logits' memory by
+                     row slabs (mla_indexer_topk_prefill_fp8 does).
+    result           for j < vis(r): logit[r - row_begin, j] by the formula of mla_indexer_logits_fp8, with the same bits as
+                     that op gives on the expanded form (one head sum, csrc/mla_indexer_dev.h).  Columns at or past vis(r)
+                     and rows of no request are NOT written.  A position whose page id lies outside [0, num_blocks) gets
+                     -inf, and its page is never loaded.
+    k_cache          the cache of mla_indexer_store_k_fp8: torch.uint8 [num_blocks, P * 132], P in {16, 32, 64, 128}.
+
+    Key-stationary: a workgroup stages 16 rows of q in LDS and runs them against each 64-key step of its chunk of columns,
+    so a key is loaded once per 16 rows, not once per mtp + 1 <= 4 rows as through the decode op.  R == 0 or num_req == 0
+    returns without a launch.  With output given nothing is allocated and the call captures into a hipGraph.  No float
+    atomics: the result is bit-identical from call to call."""
+    return torch.ops.hpc_mla.mla_indexer_logits_prefill_fp8(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index,
+                                                            int(row_begin), output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_logits_prefill_fp8")
+def _mla_indexer_logits_prefill_fp8_fake(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, row_begin, output=None):
+    if output is not None:
+        return output
+    return q.new_empty((q.shape[0], block_ids.shape[1] * (k_cache.shape[1] // 132)), dtype=torch.float32)
+
+
+def mla_indexer_topk_prefill(logits: Tensor, num_seqlen_per_req: Tensor, q_index: Tensor, topk: int, *, row_begin: int = 0,
+                             output: Tensor = None) -> Tensor:
+    """The indexer's top-k of a ragged PREFILL chunk.  Returns int32 [R, topk] - the `indices` of
+    attention_prefill_mla_sparse_bf16 / _fp8.
+
+    mla_indexer_topk (the same kernel): its selection, its tie rule (ties go to the smaller position), its ASCENDING
+    position output with -1 padding and the identity list 0 .. n_r - 1 without reading a logit when n_r <= topk.  Only
+    n_r differs: n_r = min(vis(row_begin + r), logits.shape[1]) from the row rule of mla_indexer_logits_prefill_fp8
+    (num_seqlen_per_req, q_index on the device).  A row of no request gets all -1.  logits float32 [R, columns] holds the
+    chunk's rows row_begin ..; columns at or past n_r are never read.  topk 1..65536.  With output given nothing is
+    allocated and the call captures into a hipGraph."""
+    return torch.ops.hpc_mla.mla_indexer_topk_prefill(logits, num_seqlen_per_req, q_index, int(topk), int(row_begin), output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_topk_prefill")
+def _mla_indexer_topk_prefill_fake(logits, num_seqlen_per_req, q_index, topk, row_begin, output=None):
+    return output if output is not None else logits.new_empty((logits.shape[0], topk), dtype=torch.int32)
+
+
+def mla_indexer_topk_prefill_fp8(q: Tensor, weights: Tensor, k_cache: Tensor, block_ids: Tensor, num_seqlen_per_req: Tensor,
+                                 q_index: Tensor, topk: int, *, scratch_rows: int = 0, output: Tensor = None) -> Tensor:
+    """mla_indexer_logits_prefill_fp8 then mla_indexer_topk_prefill over the whole chunk, in slabs of rows.  Returns int32
+    [T, topk]: what goes into attention_prefill_mla_sparse_bf16 / _fp8 as `indices`.
+
+    The logits of a slab go through a cached scratch buffer of float32 [slab_rows, max_blocks * P] per (device, stream,
+    hipGraph capture) that hpc.release_decode_workspaces() drops; it is never zeroed, the top-k reads only the columns the
+    logits wrote, and it does not grow with T.  scratch_rows > 0 fixes the slab; 0 lets the library take what fits a
+    256 MiB budget (a resource cap, csrc/mla_indexer_route.h).  The number of slabs is a host value: with output given
+    nothing is allocated beyond the scratch and the call captures into a hipGraph.  The result is bit-identical to the two
+    ops run over the whole chunk, whatever the slab, and from call to call.  Two launches per slab."""
+    return torch.ops.hpc_mla.mla_indexer_topk_prefill_fp8(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, int(topk),
+                                                          int(scratch_rows), output)
+
+
+@torch.library.register_fake("hpc_mla::mla_indexer_topk_prefill_fp8")
+def _mla_indexer_topk_prefill_fp8_fake(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, topk, scratch_rows, output=None):
+    return output if output is not None else q.new_empty((q.shape[0], topk), dtype=torch.int32)
+
+
 def mla_indexer_prep_fp8(k_cache: Optional[Tensor], k: Tensor, k_norm_weight: Tensor, k_norm_bias: Tensor, cos_sin: Tensor,
                          num_seqlen_per_req: Tensor, q_index: Tensor, block_ids: Tensor, *, q: Optional[Tensor] = None,
                          head_weights: Optional[Tensor] = None, softmax_scale: Optional[float] = None, eps: float = 1e-6,

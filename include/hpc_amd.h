@@ -613,6 +613,82 @@ int hpc_mla_indexer_topk_fp8_async(int* indices, const void* q, const float* wei
                                    int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
                                    int new_kv_included, void* workspace, int64_t workspace_bytes, hpc_stream_t stream);
 
+/* ---- DSA prefill: the indexer and the token-sparse attention over a ragged chunk (csrc/mla_indexer_prefill.hip) ---------------
+ * What the calls above are for a decode step, for a prompt chunk whose requests have any number of rows.  The row rule is the
+ * writers' (hpc_mla_rope_norm_store_kv_async, hpc_mla_indexer_store_k_fp8_async): row r of the chunk belongs to the last request
+ * b with q_index[b] <= r, at pos = num_seqlen_per_req[b] - (q_index[b + 1] - r); num_seqlen_per_req int32 [num_req] are total
+ * lengths INCLUDING the chunk's tokens, q_index int32 [num_req + 1], block_ids int32 [num_req, max_blocks], all ON THE DEVICE and
+ * never read by the host.  A row at or past q_index[num_req] or with pos < 0 is a row of no request; a live row sees
+ * vis(r) = min(pos + 1, max_blocks * block_size) tokens: causal inside the chunk, all of the cached context before it.  The
+ * statement is the decode statement on the expanded form (every row a one-row request of length pos + 1):
+ * tests/mla_indexer_prefill_ref.py.
+ *
+ * hpc_mla_indexer_logits_prefill_fp8_async: q e4m3 [num_rows, num_head, 128] and weights fp32 [num_rows, num_head] hold the
+ * chunk's rows row_begin .. row_begin + num_rows - 1; logits row r of the CALL (row row_begin + r of the chunk) gets the formula
+ * of hpc_mla_indexer_logits_fp8_async for 0 <= j < vis and, bit for bit, the values of that call on the expanded form; columns
+ * at or past vis and rows of no request are NOT written; -inf where the page id lies outside [0, num_blocks).  A key tile is
+ * loaded once per tile of 16 rows.
+ * hpc_mla_indexer_topk_prefill_async: hpc_mla_indexer_topk_async with n_r = min(vis(row_begin + r), num_cols); a row of no
+ * request gets all -1.
+ * hpc_mla_indexer_topk_prefill_fp8_async: the two over slabs of scratch_rows rows (0: what fits 256 MiB of scratch) through
+ * `workspace` (fp32 [slab_rows, max_blocks * block_size], never zeroed); bit-identical to the two calls over the whole chunk
+ * whatever the slab.  The slab count is a host value.
+ * hpc_mla_indexer_prefill_plan(..., topk (0: a logits call), scratch_rows, num_cu (<= 0: the current device's), ...) gives the
+ * row tile, the logits grid of a call over num_rows rows (ceil(num_rows / tile) * chunks; 0 without requests), the chunk, the
+ * slab, the slab count and the scratch's row stride and bytes; it returns what the calls would.
+ * Codes as the decode calls', plus HPC_ERR_INVALID for a negative row_begin or scratch_rows.  num_rows == 0 or num_req == 0
+ * launches nothing (nothing is written); a caller's slab of more than 2^40 bytes is HPC_ERR_UNSUPPORTED.  The *_refusal
+ * functions are pure host functions.
+ *
+ * hpc_attention_prefill_mla_sparse_{bf16,fp8}_async: hpc_attention_decode_mla_sparse_{bf16,fp8}_async with q bf16
+ * [num_rows, num_head, 576], indices int32 [num_rows, topk] and vis(r) from the row rule; a row of no request is an empty row
+ * (out = 0, lse = -inf).  The same kernel, route (num_batch = num_rows, num_seq_q = 1: hpc_attention_decode_mla_sparse_plan
+ * sizes the scratch), splits rule, limits and refusals, plus HPC_ERR_INVALID for a null q_index or a negative num_req.
+ * As in the other calls of this section num_rows == 0 or num_req == 0 launches nothing and WRITES nothing: a caller of the
+ * C-ABI that passes no request fills its own outputs (the torch ops do: lists of -1, out = 0, lse = -inf).  The plan's grid and
+ * chunk are those of one logits launch over num_rows rows; the fused call launches the logits once per slab and each launch
+ * takes its chunk from its own rows (a partial last slab may take a shorter one; no logit depends on it). */
+int hpc_mla_indexer_prefill_plan(int num_rows, int num_req, int num_head, int block_size, int max_blocks, int topk,
+                                 int scratch_rows, int num_cu, int* tile, int* grid, int* chunk, int* slab_rows, int* slabs,
+                                 int64_t* logits_row_stride, int64_t* workspace_bytes);
+const char* hpc_mla_indexer_logits_prefill_fp8_refusal(const float* logits, const void* q, const float* weights,
+                                                       const void* k_cache, const int* block_ids, const int* num_seqlen_per_req,
+                                                       const int* q_index, int num_rows, int num_req, int row_begin, int num_head,
+                                                       int block_size, int max_blocks, int num_blocks,
+                                                       int64_t k_cache_block_stride_bytes, int64_t logits_row_stride);
+int hpc_mla_indexer_logits_prefill_fp8_async(float* logits, const void* q, const float* weights, const void* k_cache,
+                                             const int* block_ids, const int* num_seqlen_per_req, const int* q_index, int num_rows,
+                                             int num_req, int row_begin, int num_head, int block_size, int max_blocks,
+                                             int num_blocks, int64_t k_cache_block_stride_bytes, int64_t logits_row_stride,
+                                             hpc_stream_t stream);
+const char* hpc_mla_indexer_topk_prefill_refusal(const int* indices, const float* logits, const int* num_seqlen_per_req,
+                                                 const int* q_index, int num_rows, int num_req, int row_begin, int64_t num_cols,
+                                                 int topk, int64_t logits_row_stride);
+int hpc_mla_indexer_topk_prefill_async(int* indices, const float* logits, const int* num_seqlen_per_req, const int* q_index,
+                                       int num_rows, int num_req, int row_begin, int64_t num_cols, int topk,
+                                       int64_t logits_row_stride, hpc_stream_t stream);
+const char* hpc_mla_indexer_topk_prefill_fp8_refusal(const int* indices, const void* q, const float* weights, const void* k_cache,
+                                                     const int* block_ids, const int* num_seqlen_per_req, const int* q_index,
+                                                     int num_rows, int num_req, int num_head, int block_size, int max_blocks,
+                                                     int num_blocks, int64_t k_cache_block_stride_bytes, int topk, int scratch_rows,
+                                                     const void* workspace, int64_t workspace_bytes);
+int hpc_mla_indexer_topk_prefill_fp8_async(int* indices, const void* q, const float* weights, const void* k_cache,
+                                           const int* block_ids, const int* num_seqlen_per_req, const int* q_index, int num_rows,
+                                           int num_req, int num_head, int block_size, int max_blocks, int num_blocks,
+                                           int64_t k_cache_block_stride_bytes, int topk, int scratch_rows, void* workspace,
+                                           int64_t workspace_bytes, hpc_stream_t stream);
+int hpc_attention_prefill_mla_sparse_bf16_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                                const int* num_seqlen_per_req, const int* q_index, const int* indices,
+                                                int num_rows, int num_req, int num_head, int topk, int block_size, int max_blocks,
+                                                int num_blocks, int64_t ckv_block_stride, int64_t ckv_token_stride,
+                                                float softmax_scale, int splits, void* workspace, int64_t workspace_bytes,
+                                                hpc_stream_t stream);
+int hpc_attention_prefill_mla_sparse_fp8_async(void* out, float* lse, const void* q, const void* ckv, const int* block_ids,
+                                               const int* num_seqlen_per_req, const int* q_index, const int* indices, int num_rows,
+                                               int num_req, int num_head, int topk, int block_size, int max_blocks, int num_blocks,
+                                               int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes, float softmax_scale,
+                                               int splits, void* workspace, int64_t workspace_bytes, hpc_stream_t stream);
+
 /* ---- The indexer's front end: key LayerNorm + RoPE + Hadamard rotation + FP8 quant + store, q likewise (csrc/mla_indexer_prep.hip)
  * What runs between a layer's wq_b / wk / weights_proj GEMMs and hpc_mla_indexer_topk_fp8_async, in one launch.  No reference
  * kernel; the statement is tests/mla_indexer_prep_ref.py, the host rule csrc/mla_indexer_route.h (mla_indexer_prep_route).

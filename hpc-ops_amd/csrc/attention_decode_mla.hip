@@ -91,7 +91,9 @@ __device__ __forceinline__ int piece_len(int len, int splits) {
   return ((len + splits - 1) / splits + kMlaKvTile - 1) & ~(kMlaKvTile - 1);
 }
 // positions a list entry of q row (b, s) may name: [0, vis), vis = L_b - num_seq_q + s + 1 from the UNCLAMPED length, never
-// beyond the page table's reach (so idx < vis implies idx >> page_shift < max_blocks)
+// beyond the page table's reach (so idx < vis implies idx >> page_shift < max_blocks).  The decode-step row rule of
+// mla_indexer_dev.h (step_len, step_sees) with the reach in 64 bits: calling those moves this kernel's assembly, so the rule
+// stands here a second time
 __device__ __forceinline__ int sparse_vis(const SparseArgs& a, int b, int s) {
   const int64_t cap = static_cast<int64_t>(a.max_blocks) << a.page_shift;
   int64_t vis = static_cast<int64_t>(a.num_seq[b]) + (a.new_kv_included ? 0 : a.num_seq_q) - a.num_seq_q + s + 1;
@@ -470,47 +472,47 @@ __global__ __launch_bounds__(128) void attention_decode_mla_merge_kernel(const A
 // ---- host side: dense and token-sparse share the route (mla_route() of attention_decode_mla_route.h), the plan sequence and
 // the launcher; the form is the template argument kSparse, and the list's checks and members stand beside the shared ones -------
 namespace {
-int mla_current_cu_count() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-}
+using hpc::MlaRows;
 
 // Both plan entries: refusals first, on the host alone; only a call that leaves both the split count and the CU count open asks
 // the device.  num_cu <= 0: the current device's (256 without a device).
 hpc::MlaRoute mla_plan_route(int num_batch, int num_seq_q, int num_head, bool sparse, int topk, int splits_wanted, int num_cu) {
   hpc::MlaRoute r = hpc::mla_route(num_batch, num_seq_q, num_head, sparse, topk, splits_wanted, num_cu > 0 ? num_cu : 256);
   if (r.code == HPC_OK && num_cu <= 0 && splits_wanted == 0 && num_batch > 0)
-    r = hpc::mla_route(num_batch, num_seq_q, num_head, sparse, topk, 0, mla_current_cu_count());
+    r = hpc::mla_route(num_batch, num_seq_q, num_head, sparse, topk, 0, hpc::current_cu_count());
   return r;
 }
 
-// the arguments of the four launchers, in the sparse entries' order; dense: indices null, topk and num_blocks 0
+// the arguments of the six launchers, in the sparse entries' order; dense: indices null, topk and num_blocks 0
 struct MlaDecodeCall {
   void* out;
   float* lse;
   const void* q;
   const void* ckv;
   const int* block_ids;
-  const int* num_seq_kvcache;
+  MlaRows rows;  // a decode step or, the ragged entries, a prefill chunk (mla_indexer_route.h)
   const int* indices;
-  const int* q_index;  // the ragged entries: num_batch is the chunk's rows, num_seq_q 1, num_seq_kvcache num_seqlen_per_req
-  int num_req;
-  int num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks;
+  int num_head, topk, block_size, max_blocks, num_blocks;
   int64_t ckv_block_stride, ckv_token_stride;  // in the kind's units: bf16 elements or FP8 bytes
   float softmax_scale;
-  int new_kv_included, splits;
+  int splits;
   void* workspace;
   int64_t workspace_bytes;
   hipStream_t stream;
 };
 
-// All four launchers: the checks, the route and the launches.  What a valid cache is - its page size, its strides in the kind's
+// All six launchers: the checks, the route and the launches.  What a valid cache is - its page size, its strides in the kind's
 // units and its alignment - is mla_cache_check() of mla_cache.h.
 template <bool kFp8, bool kSparse>
 int mla_decode_launch(const MlaDecodeCall& c) {
   using namespace hpc::mla;
   constexpr hpc::MlaCacheKind kind = kFp8 ? hpc::kMlaCacheFp8 : hpc::kMlaCacheBf16;
-  if (!c.out || !c.q || !c.ckv || !c.block_ids || !c.num_seq_kvcache || (kSparse && !c.indices)) return HPC_ERR_INVALID;
+  // A ragged chunk is routed as num_rows requests of one q row each (hpc_attention_decode_mla_sparse_plan sizes its scratch so);
+  // without requests every row is a row of no request and the call is an empty one
+  const MlaRows& rows = c.rows;
+  if (rows.ragged && (!rows.q_index || rows.num_req < 0)) return HPC_ERR_INVALID;
+  const int num_batch = !rows.ragged ? rows.num_batch : rows.num_req == 0 && rows.num_rows > 0 ? 0 : rows.num_rows;
+  if (!c.out || !c.q || !c.ckv || !c.block_ids || !rows.lens || (kSparse && !c.indices)) return HPC_ERR_INVALID;
   // the cache's invalid argument (a negative block stride) is refused here with the others, what it does not support behind
   // the shapes: a call with two faults keeps the code of the earlier check
   const hpc::MlaCacheCheck cache =
@@ -519,7 +521,7 @@ int mla_decode_launch(const MlaDecodeCall& c) {
     return HPC_ERR_INVALID;
   // the split count is the caller's, or with 0 the route's for this device; shapes are refused before the device is asked
   const hpc::MlaRoute shape =
-      hpc::mla_route(c.num_batch, c.num_seq_q, c.num_head, kSparse, c.topk, c.splits > 0 ? c.splits : 1, 256);
+      hpc::mla_route(num_batch, rows.num_seq_q, c.num_head, kSparse, c.topk, c.splits > 0 ? c.splits : 1, 256);
   if (shape.code != HPC_OK) return shape.code;
   if (cache.code != HPC_OK) return cache.code;
   if (static_cast<int64_t>(c.max_blocks) * c.block_size > (1ll << 30)) return HPC_ERR_UNSUPPORTED;
@@ -527,11 +529,11 @@ int mla_decode_launch(const MlaDecodeCall& c) {
   if ((reinterpret_cast<uintptr_t>(c.out) & 7) || (reinterpret_cast<uintptr_t>(c.lse) & 3) ||
       (kSparse && (reinterpret_cast<uintptr_t>(c.indices) & 3)))
     return HPC_ERR_UNSUPPORTED;
-  if (c.num_batch == 0) return HPC_OK;
+  if (num_batch == 0) return HPC_OK;
   if (c.max_blocks == 0) return HPC_ERR_INVALID;
-  if (c.q_index && (c.num_req <= 0 || c.num_req == INT32_MAX)) return HPC_ERR_INVALID;  // the ragged entries leave before this without requests
+  if (rows.ragged && rows.num_req == INT32_MAX) return HPC_ERR_INVALID;  // num_req + 1 entries of q_index
   const hpc::MlaRoute r =
-      c.splits > 0 ? shape : hpc::mla_route(c.num_batch, c.num_seq_q, c.num_head, kSparse, c.topk, 0, mla_current_cu_count());
+      c.splits > 0 ? shape : hpc::mla_route(num_batch, rows.num_seq_q, c.num_head, kSparse, c.topk, 0, hpc::current_cu_count());
   if (r.code != HPC_OK) return r.code;
   if (r.splits > 1) {
     if (!c.workspace || c.workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;
@@ -541,7 +543,7 @@ int mla_decode_launch(const MlaDecodeCall& c) {
   a.q = static_cast<const uint8_t*>(c.q);
   a.ckv = static_cast<const uint8_t*>(c.ckv);
   a.block_ids = c.block_ids;
-  a.num_seq = c.num_seq_kvcache;
+  a.num_seq = rows.lens;
   a.out = static_cast<uint16_t*>(c.out);
   a.lse = c.lse;
   a.ws_o = static_cast<float*>(c.workspace);
@@ -550,18 +552,18 @@ int mla_decode_launch(const MlaDecodeCall& c) {
   a.token_stride_bytes = c.ckv_token_stride * kind.unit;
   a.total_rows = r.total_rows;
   a.num_head = c.num_head;
-  a.num_seq_q = c.num_seq_q;
+  a.num_seq_q = rows.num_seq_q;
   a.rows = r.rows;
   a.row_tiles = r.row_tiles;
   a.splits = r.splits;
   a.page_shift = hpc::mla_page_shift(c.block_size);
   a.max_blocks = c.max_blocks;
-  a.new_kv_included = c.new_kv_included ? 1 : 0;
+  a.new_kv_included = rows.new_kv_included ? 1 : 0;
   a.scale_log2 = c.softmax_scale * kLog2e;
   if constexpr (kSparse) {
     a.indices = c.indices;
-    a.q_index = c.q_index;
-    a.num_req = c.num_req;
+    a.q_index = rows.q_index;
+    a.num_req = rows.num_req;
     a.topk = c.topk;
     a.plen = r.plen;
     a.num_blocks = c.num_blocks;
@@ -594,9 +596,10 @@ extern "C" int hpc_attention_decode_mla_bf16_async(void* out_ptr, float* lse_ptr
                                                    int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                    int new_kv_included, int splits, void* workspace_ptr,
                                                    int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<false, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, nullptr, 0, num_batch,
-                                          num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride, ckv_token_stride,
-                                          softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes, stream});
+  return mla_decode_launch<false, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                          MlaRows::step(num_seq_kvcache_ptr, num_batch, num_seq_q, new_kv_included), nullptr, num_head,
+                                          0, block_size, max_blocks, 0, ckv_block_stride, ckv_token_stride, softmax_scale, splits,
+                                          workspace_ptr, workspace_bytes, stream});
 }
 
 // the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
@@ -606,10 +609,10 @@ extern "C" int hpc_attention_decode_mla_fp8_async(void* out_ptr, float* lse_ptr,
                                                   int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                   float softmax_scale, int new_kv_included, int splits, void* workspace_ptr,
                                                   int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<true, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, nullptr, nullptr, 0, num_batch,
-                                         num_seq_q, num_head, 0, block_size, max_blocks, 0, ckv_block_stride_bytes,
-                                         ckv_token_stride_bytes, softmax_scale, new_kv_included, splits, workspace_ptr,
-                                         workspace_bytes, stream});
+  return mla_decode_launch<true, false>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                         MlaRows::step(num_seq_kvcache_ptr, num_batch, num_seq_q, new_kv_included), nullptr, num_head,
+                                         0, block_size, max_blocks, 0, ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale,
+                                         splits, workspace_ptr, workspace_bytes, stream});
 }
 
 // ---- the token-sparse form: each q row attends to the tokens its list names --------------------------------------------------
@@ -633,10 +636,10 @@ extern "C" int hpc_attention_decode_mla_sparse_bf16_async(void* out_ptr, float* 
                                                           int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                           int new_kv_included, int splits, void* workspace_ptr,
                                                           int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, nullptr, 0,
-                                         num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride,
-                                         ckv_token_stride, softmax_scale, new_kv_included, splits, workspace_ptr, workspace_bytes,
-                                         stream});
+  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                         MlaRows::step(num_seq_kvcache_ptr, num_batch, num_seq_q, new_kv_included), indices_ptr,
+                                         num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride,
+                                         softmax_scale, splits, workspace_ptr, workspace_bytes, stream});
 }
 
 // the same over the FP8 latent cache (mla_fp8_format.h); the cache's strides in bytes
@@ -647,16 +650,16 @@ extern "C" int hpc_attention_decode_mla_sparse_fp8_async(void* out_ptr, float* l
                                                          int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                          float softmax_scale, int new_kv_included, int splits,
                                                          void* workspace_ptr, int64_t workspace_bytes, hipStream_t stream) {
-  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seq_kvcache_ptr, indices_ptr, nullptr, 0,
-                                        num_batch, num_seq_q, num_head, topk, block_size, max_blocks, num_blocks,
-                                        ckv_block_stride_bytes, ckv_token_stride_bytes, softmax_scale, new_kv_included, splits,
-                                        workspace_ptr, workspace_bytes, stream});
+  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                        MlaRows::step(num_seq_kvcache_ptr, num_batch, num_seq_q, new_kv_included), indices_ptr,
+                                        num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride_bytes,
+                                        ckv_token_stride_bytes, softmax_scale, splits, workspace_ptr, workspace_bytes, stream});
 }
 
 // ---- the token-sparse form over a ragged prefill chunk: row r of the chunk is a unit, its request and what it sees come from the
 // row rule on the device (num_seqlen_per_req: total lengths including the chunk's tokens; q_index [num_req + 1]); everything
-// else - route (mla_route with num_batch = num_rows, num_seq_q = 1; hpc_attention_decode_mla_sparse_plan sizes the scratch),
-// launcher, kernel, merge - is the decode form's.  num_rows == 0 or num_req == 0 launches nothing.
+// else - route, launcher, kernel, merge - is the decode form's, and what a chunk's rows ask beyond a step's is the launcher's.
+// num_rows == 0 or num_req == 0 launches nothing.
 extern "C" int hpc_attention_prefill_mla_sparse_bf16_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
                                                            const int* block_ids_ptr, const int* num_seqlen_per_req_ptr,
                                                            const int* q_index_ptr, const int* indices_ptr, int num_rows, int num_req,
@@ -664,11 +667,10 @@ extern "C" int hpc_attention_prefill_mla_sparse_bf16_async(void* out_ptr, float*
                                                            int64_t ckv_block_stride, int64_t ckv_token_stride, float softmax_scale,
                                                            int splits, void* workspace_ptr, int64_t workspace_bytes,
                                                            hipStream_t stream) {
-  if (!q_index_ptr || num_req < 0) return HPC_ERR_INVALID;
-  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seqlen_per_req_ptr, indices_ptr,
-                                         q_index_ptr, num_req, num_req == 0 && num_rows > 0 ? 0 : num_rows, 1, num_head, topk,
-                                         block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride, softmax_scale, 1,
-                                         splits, workspace_ptr, workspace_bytes, stream});
+  return mla_decode_launch<false, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                         MlaRows::chunk(num_seqlen_per_req_ptr, q_index_ptr, num_rows, num_req, 0), indices_ptr,
+                                         num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride, ckv_token_stride,
+                                         softmax_scale, splits, workspace_ptr, workspace_bytes, stream});
 }
 
 extern "C" int hpc_attention_prefill_mla_sparse_fp8_async(void* out_ptr, float* lse_ptr, const void* q_ptr, const void* ckv_ptr,
@@ -678,9 +680,8 @@ extern "C" int hpc_attention_prefill_mla_sparse_fp8_async(void* out_ptr, float* 
                                                           int64_t ckv_block_stride_bytes, int64_t ckv_token_stride_bytes,
                                                           float softmax_scale, int splits, void* workspace_ptr,
                                                           int64_t workspace_bytes, hipStream_t stream) {
-  if (!q_index_ptr || num_req < 0) return HPC_ERR_INVALID;
-  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr, num_seqlen_per_req_ptr, indices_ptr,
-                                        q_index_ptr, num_req, num_req == 0 && num_rows > 0 ? 0 : num_rows, 1, num_head, topk,
-                                        block_size, max_blocks, num_blocks, ckv_block_stride_bytes, ckv_token_stride_bytes,
-                                        softmax_scale, 1, splits, workspace_ptr, workspace_bytes, stream});
+  return mla_decode_launch<true, true>({out_ptr, lse_ptr, q_ptr, ckv_ptr, block_ids_ptr,
+                                        MlaRows::chunk(num_seqlen_per_req_ptr, q_index_ptr, num_rows, num_req, 0), indices_ptr,
+                                        num_head, topk, block_size, max_blocks, num_blocks, ckv_block_stride_bytes,
+                                        ckv_token_stride_bytes, softmax_scale, splits, workspace_ptr, workspace_bytes, stream});
 }

@@ -503,21 +503,14 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16xfp32_skinny_kernel(const A
 }  // namespace rgemm
 }  // namespace hpc
 
-namespace {
-int current_cu_count() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-}
-}  // namespace
-
 // Split count the library picks for (m, n, k), and what the caller of hpc_gemm_bf16xfp32_async provides with it: rgemm_route()
 // (gemm_bf16xfp32_route.h).  split_y = splits * m * n floats; flag_rows x flag_ld zeroed int32 counters.
 extern "C" int hpc_gemm_bf16xfp32_splits(int m, int n, int k, int use_splitk) {
-  return hpc::rgemm_route(m, n, k, use_splitk, current_cu_count()).splits;
+  return hpc::rgemm_route(m, n, k, use_splitk, hpc::current_cu_count()).splits;
 }
 extern "C" int hpc_gemm_bf16xfp32_plan(int m, int n, int k, int use_splitk, int* splits, int* flag_rows, int* flag_ld) {
   if (!splits || !flag_rows || !flag_ld) return HPC_ERR_INVALID;
-  const hpc::RgemmRoute r = hpc::rgemm_route(m, n, k, use_splitk, current_cu_count());
+  const hpc::RgemmRoute r = hpc::rgemm_route(m, n, k, use_splitk, hpc::current_cu_count());
   *splits = r.splits, *flag_rows = r.flag_rows, *flag_ld = r.flag_ld;
   return r.code;
 }

@@ -239,19 +239,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_blockwise_fp8_kernel(const A
 }  // namespace lgemm
 }  // namespace hpc
 
-namespace {
-int current_cu_count() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-}
-}  // namespace
-
 // What a call of hpc_gemm_blockwise_fp8_async with this `splits_wanted` runs with and needs: lgemm_route()
 // (gemm_blockwise_fp8_route.h).  cu_count <= 0: the current device's (256 without a device).
 extern "C" int hpc_gemm_blockwise_fp8_plan(int m, int n, int k, int splits_wanted, int cu_count, int* splits, int* max_splits,
                                            int64_t* workspace_bytes, int* counters) {
   if (!splits || !max_splits || !workspace_bytes || !counters) return HPC_ERR_INVALID;
-  const hpc::LgemmRoute r = hpc::lgemm_route(m, n, k, splits_wanted, cu_count > 0 ? cu_count : current_cu_count());
+  const hpc::LgemmRoute r = hpc::lgemm_route(m, n, k, splits_wanted, cu_count > 0 ? cu_count : hpc::current_cu_count());
   *splits = r.splits, *max_splits = r.max_splits, *workspace_bytes = r.workspace_bytes, *counters = r.counters;
   return r.code;
 }
@@ -270,7 +263,7 @@ extern "C" int hpc_gemm_blockwise_fp8_async(void* y_ptr, const void* x_ptr, cons
   if ((reinterpret_cast<uintptr_t>(x_ptr) | reinterpret_cast<uintptr_t>(weight_ptr)) & 15) return HPC_ERR_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(y_ptr) & 7) return HPC_ERR_UNSUPPORTED;
   if (m == 0) return HPC_OK;
-  const hpc::LgemmRoute r = splits > 0 ? shape : hpc::lgemm_route(m, n, k, 0, current_cu_count());
+  const hpc::LgemmRoute r = splits > 0 ? shape : hpc::lgemm_route(m, n, k, 0, hpc::current_cu_count());
   if (r.code != HPC_OK) return r.code;
   if (r.splits > 1) {
     if (!workspace_ptr || !counters_ptr || workspace_bytes < r.workspace_bytes) return HPC_ERR_INVALID;

@@ -204,8 +204,18 @@ __device__ __forceinline__ u32x2 buf_ld8(rsrc_t rs, int voff, int soff) {
 
 }  // namespace hpc
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+// the CU count of the current device, what a route sizes its grid from; 0 without a device (the routes then take 256)
+extern "C" int hpc_get_cu_count(int device_id);
+namespace hpc {
+static inline int current_cu_count() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
+}
+}  // namespace hpc
+
 // the status codes: hpc_status.h
-#define HPC_CHECK_LAUNCH()                               \
+#define HPC_CHECK_LAUNCH()                              \
   do {                                                   \
     if (hipGetLastError() != hipSuccess) return HPC_ERR_LAUNCH; \
   } while (0)

@@ -28,7 +28,7 @@ constexpr int kMlaAbsorbFill = 512;     // absorb_q workgroups resident at once 
 constexpr int kMlaAbsorbSlice = 128;    // absorb_q: latent columns per workgroup, one LDS image of [128 d][128 c]
 constexpr int kMlaAbsorbSlices = kMlaAbsorbLatent / kMlaAbsorbSlice;
 constexpr int kMlaAbsorbXcds = 8;
-constexpr int64_t kMlaAbsorbMaxSpan = int64_t{1} << 60;  // bytes a tensor may span: offsets are 64-bit and stay below 2^61
+constexpr int64_t kMlaAbsorbMaxSpan = kMaxSpan;  // bytes a tensor may span (byte_span.h): offsets are 64-bit and stay below 2^61
 
 struct MlaAbsorbCall {  // strides in ELEMENTS of the tensor's dtype
   uintptr_t out, x, w;  // x: q_nope / o_lat

@@ -20,6 +20,7 @@
 // wave's rows is issued before the first store (9 KiB per wave in flight with the bf16 cache, 5.1 KiB with
 // FP8, up to 32 waves per CU); the stores are plain vector stores.  Device values are never trusted with an address: the
 // output row comes from the grid and the host's num_rows alone, see `resolve`.
+#include "byte_span.h"
 #include "hpc_common.h"
 #include "mla_cache.h"
 #include "mla_fp8_format.h"
@@ -156,9 +157,8 @@ int mla_gather_launch(void* out, const void* ckv_cache, const int* block_ids, co
   if (num_rows > 1 && out_row_stride < kMlaRow) return HPC_ERR_UNSUPPORTED;  // rows would overlap
   // sizes beyond int32 (the grid's row arithmetic) and cache offsets beyond 64 bits
   if (num_rows > INT32_MAX - kRowsPerBlock || num_req == INT32_MAX) return HPC_ERR_UNSUPPORTED;
-  constexpr int64_t kSpan = int64_t{1} << 60;  // bytes: page id x block stride + token x token stride stays below 2^61
-  if (ckv_token_stride > kSpan / kind.unit / 128 || out_row_stride > kSpan / 2 / INT32_MAX ||
-      (num_blocks > 0 && ckv_block_stride > kSpan / kind.unit / num_blocks))
+  if (ckv_token_stride > kMaxSpan / kind.unit / 128 || out_row_stride > kMaxSpan / 2 / INT32_MAX ||
+      (num_blocks > 0 && ckv_block_stride > kMaxSpan / kind.unit / num_blocks))
     return HPC_ERR_UNSUPPORTED;
   if (!work) return HPC_OK;  // nothing to launch
 

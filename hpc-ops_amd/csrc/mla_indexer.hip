@@ -86,11 +86,12 @@ __global__ __launch_bounds__(kLogitsThreads) void logits_kernel(const LogitsArgs
   const int n = lane & 15, g = lane >> 4;
   const int b = blockIdx.x / a.chunks, piece = blockIdx.x % a.chunks;  // b < num_batch: the grid is num_batch * chunks
 
-  // L_b and the rows' visible lengths, clamped to the table: device values never reach an address unchecked
-  const long len = static_cast<long>(as_const(a.lens)[b]) + (a.nki ? 0 : kSq);
+  // the rows' visible lengths (the step's row rule, mla_indexer_dev.h), clamped to the table: device values never reach an
+  // address unchecked
+  const long len = step_len(as_const(a.lens)[b], kSq, a.nki);
   int vis[kSq];
 #pragma unroll
-  for (int s = 0; s < kSq; ++s) vis[s] = clamp_len(len - kSq + s + 1, a.cols);
+  for (int s = 0; s < kSq; ++s) vis[s] = step_sees(len, kSq, s, a.cols);
   const int lim = vis[kSq - 1];  // the longest of them
   const int c0 = piece * a.chunk;
   if (c0 >= lim) return;
@@ -168,13 +169,12 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const TopkArgs a) {
   __shared__ uint32_t wave_gt[kTopkWaves], wave_tie[kTopkWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = blockIdx.x;
-  int n;  // the columns row r sees: the one thing a ragged chunk takes from elsewhere (the row rule, mla_indexer_dev.h)
+  int n;  // the columns row r sees: the one thing the two forms take from different rules (mla_indexer_dev.h)
   if (a.q_index) {
     n = row_sees(a.q_index, a.lens, a.num_req, a.row_begin + r, a.cols).vis;
   } else {
     const int b = r / a.sq, s = r % a.sq;
-    const long len = static_cast<long>(a.lens[b]) + (a.nki ? 0 : a.sq);
-    n = clamp_len(len - a.sq + s + 1, a.cols);
+    n = step_sees(step_len(a.lens[b], a.sq, a.nki), a.sq, s, a.cols);
   }
   int* o = a.out + static_cast<long>(r) * a.topk;
   if (n <= a.topk) {  // the identity list: no logit is read
@@ -276,15 +276,10 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const TopkArgs a) {
 
 namespace {
 using hpc::MlaIndexerCheck;
+using hpc::MlaRows;
 
-int current_cu_count() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-}
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-constexpr int64_t kSpan = int64_t{1} << 60;  // bytes: page id x block stride stays below 2^61
-
-// ---- the host rules, one function per call: the refusal code and its reason in words, no device call ------------------------------
+// ---- the host rule of the store: the refusal code and its reason in words, no device call.  The readers' rules - logits, top-k
+// and the fused call, for a decode step and a ragged chunk alike - are mla_indexer_route.h's ---------------------------------------
 MlaIndexerCheck store_check(const void* k_cache, const void* k, const int* num_seqlen_per_req, const int* q_index,
                             const int* block_ids, int num_rows, int num_req, int block_size, int max_blocks, int num_blocks,
                             int64_t block_stride, int64_t k_row_stride) {
@@ -300,67 +295,12 @@ MlaIndexerCheck store_check(const void* k_cache, const void* k, const int* num_s
   if (k_row_stride < 0 || k_row_stride % 8 != 0 || (num_rows > 1 && k_row_stride < kIdxDim))
     return {HPC_ERR_UNSUPPORTED, "k row stride must be a multiple of 8 elements and at least 128"};
   if (num_rows > INT32_MAX - mla_indexer::kStoreRows || num_req == INT32_MAX) return {HPC_ERR_UNSUPPORTED, "sizes beyond int32"};
-  if (k_row_stride > kSpan / 2 / INT32_MAX || (num_blocks > 0 && block_stride > kSpan / num_blocks))
+  if (k_row_stride > kMaxSpan / 2 / INT32_MAX || (num_blocks > 0 && block_stride > kMaxSpan / num_blocks))
     return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
   return {HPC_OK, nullptr};
 }
 
-MlaIndexerCheck logits_check(const float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
-                             const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size,
-                             int max_blocks, int num_blocks, int64_t block_stride, int64_t logits_row_stride) {
-  using namespace hpc;
-  const MlaIndexerRoute r = mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, 0, true, 256);
-  if (r.code != HPC_OK) return {r.code, r.why};
-  if (num_blocks < 0) return {HPC_ERR_INVALID, "num_blocks must not be negative"};
-  const MlaIndexerCheck cache = mla_indexer_cache_check(reinterpret_cast<uintptr_t>(k_cache), block_size, block_stride);
-  if (cache.code != HPC_OK) return cache;
-  if (num_batch > 0 && (!logits || !q || !weights || !k_cache || !block_ids || !num_seq_kvcache))
-    return {HPC_ERR_INVALID, "logits, q, weights, k_cache, block_ids and num_seq_kvcache must not be null"};
-  if (num_batch > 0 && max_blocks == 0) return {HPC_ERR_INVALID, "block_ids has no columns"};
-  if (misaligned(q, 16) || misaligned(weights, 16) || misaligned(logits, 4))
-    return {HPC_ERR_UNSUPPORTED, "q and weights must be 16-byte aligned, logits 4-byte"};
-  if (logits_row_stride < r.cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least max_blocks * block_size"};
-  if (logits_row_stride > kSpan / 4 / INT32_MAX || (num_blocks > 0 && block_stride > kSpan / num_blocks))
-    return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
-  return {HPC_OK, nullptr};
-}
-
-MlaIndexerCheck topk_check(const int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q,
-                           int64_t num_cols, int topk, int64_t logits_row_stride) {
-  using namespace hpc;
-  if (num_batch < 0) return {HPC_ERR_INVALID, "num_batch must not be negative"};
-  if (num_seq_q <= 0) return {HPC_ERR_INVALID, "num_seq_q must be positive"};
-  if (num_cols < 0) return {HPC_ERR_INVALID, "the logits' column count must not be negative"};
-  if (num_seq_q > kIdxMaxSeqQ) return {HPC_ERR_UNSUPPORTED, "mtp must be 0 .. 3"};
-  if (topk < 1 || topk > kIdxMaxTopk) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
-  if (num_cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "logits reach beyond 2^30 columns"};
-  if (static_cast<int64_t>(num_batch) * num_seq_q > INT32_MAX) return {HPC_ERR_UNSUPPORTED, "num_batch * num_seq_q beyond int32"};
-  // a row that sees no more than topk tokens reads no logit, so a call over zero columns needs no logits at all
-  if (num_batch > 0 && (!indices || !num_seq_kvcache || (!logits && num_cols > 0)))
-    return {HPC_ERR_INVALID, "indices, logits and num_seq_kvcache must not be null"};
-  if (misaligned(indices, 4) || misaligned(logits, 4)) return {HPC_ERR_UNSUPPORTED, "indices and logits must be 4-byte aligned"};
-  if (logits_row_stride < num_cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least the column count"};
-  if (logits_row_stride > kSpan / 4 / INT32_MAX) return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
-  return {HPC_OK, nullptr};
-}
-
-MlaIndexerCheck fused_check(const int* indices, const void* q, const float* weights, const void* k_cache, const int* block_ids,
-                            const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
-                            int num_blocks, int64_t block_stride, int topk, const void* workspace, int64_t workspace_bytes) {
-  using namespace hpc;
-  const MlaIndexerRoute r = mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, false, 256);
-  if (r.code != HPC_OK) return {r.code, r.why};
-  // the scratch stands in for the logits; without work neither is looked at
-  const float* ws = num_batch > 0 ? static_cast<const float*>(workspace) : nullptr;
-  if (num_batch > 0 && (!workspace || workspace_bytes < r.scratch.bytes))
-    return {HPC_ERR_INVALID, "the workspace is missing or smaller than hpc_mla_indexer_plan's workspace_bytes"};
-  const MlaIndexerCheck a = logits_check(ws, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
-                                         block_size, max_blocks, num_blocks, block_stride, r.scratch.row_stride);
-  if (a.code != HPC_OK) return a;
-  return topk_check(indices, ws, num_seq_kvcache, num_batch, num_seq_q, r.cols, topk, r.scratch.row_stride);
-}
-
-// ---- the launches behind the checks -----------------------------------------------------------------------------------------------
+// ---- the readers' launchers: the check, nothing without work, the launch ------------------------------------------------------------
 template <int kHB>
 void launch_logits_sq(const hpc::mla_indexer::LogitsArgs& a, int num_seq_q, int grid, hipStream_t stream) {
   using namespace hpc::mla_indexer;
@@ -372,19 +312,24 @@ void launch_logits_sq(const hpc::mla_indexer::LogitsArgs& a, int num_seq_q, int 
   }
 }
 
-int launch_logits(float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
-                  const int* num_seq_kvcache, int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
-                  int num_blocks, int64_t block_stride, int64_t logits_row_stride, int new_kv_included, hipStream_t stream) {
+// the logits of a decode step (a chunk's: mla_indexer_prefill.hip)
+int launch_logits(const MlaRows& rows, float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
+                  int num_head, int block_size, int max_blocks, int num_blocks, int64_t block_stride, int64_t logits_row_stride,
+                  hipStream_t stream) {
   using namespace hpc;
+  const MlaIndexerCheck c = mla_indexer_logits_check(rows, logits, q, weights, k_cache, block_ids, num_head, block_size, max_blocks,
+                                                     num_blocks, block_stride, logits_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (!rows.work()) return HPC_OK;
   const MlaIndexerRoute r =
-      mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, 0, true, current_cu_count());
+      mla_indexer_route(rows.num_batch, rows.num_seq_q, num_head, block_size, max_blocks, 0, true, current_cu_count());
   if (r.code != HPC_OK) return r.code;
   mla_indexer::LogitsArgs a{};
   a.q = static_cast<const uint8_t*>(q);
   a.w = weights;
   a.cache = static_cast<const uint8_t*>(k_cache);
   a.block_ids = block_ids;
-  a.lens = num_seq_kvcache;
+  a.lens = rows.lens;
   a.out = logits;
   a.cache_bs = block_stride;
   a.out_rs = logits_row_stride;
@@ -394,34 +339,36 @@ int launch_logits(float* logits, const void* q, const float* weights, const void
   a.cols = static_cast<int>(r.cols);
   a.chunk = r.chunk;
   a.chunks = r.chunks;
-  a.nki = new_kv_included ? 1 : 0;
+  a.nki = rows.new_kv_included ? 1 : 0;
   switch (r.head_blocks) {
-    case 1: launch_logits_sq<1>(a, num_seq_q, r.grid, stream); break;
-    case 2: launch_logits_sq<2>(a, num_seq_q, r.grid, stream); break;
-    default: launch_logits_sq<4>(a, num_seq_q, r.grid, stream); break;
+    case 1: launch_logits_sq<1>(a, rows.num_seq_q, r.grid, stream); break;
+    case 2: launch_logits_sq<2>(a, rows.num_seq_q, r.grid, stream); break;
+    default: launch_logits_sq<4>(a, rows.num_seq_q, r.grid, stream); break;
   }
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
 
-// q_index null: a decode step of num_batch requests.  Given: a ragged chunk, num_batch its rows, num_seq_q 1
-int launch_topk(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch, int num_seq_q, int64_t num_cols,
-                int topk, int64_t logits_row_stride, int new_kv_included, hipStream_t stream, const int* q_index = nullptr,
-                int num_req = 0, int row_begin = 0) {
+// the top-k of either form: one workgroup per row, the kernel takes the form from q_index
+int launch_topk(const MlaRows& rows, int* indices, const float* logits, int64_t num_cols, int topk, int64_t logits_row_stride,
+                hipStream_t stream) {
   using namespace hpc::mla_indexer;
+  const MlaIndexerCheck c = hpc::mla_indexer_topk_check(rows, indices, logits, num_cols, topk, logits_row_stride);
+  if (c.code != HPC_OK) return c.code;
+  if (!rows.work()) return HPC_OK;
   TopkArgs a{};
   a.logits = logits;
-  a.lens = num_seq_kvcache;
-  a.q_index = q_index;
-  a.num_req = num_req;
-  a.row_begin = row_begin;
+  a.lens = rows.lens;
+  a.q_index = rows.q_index;
+  a.num_req = rows.num_req;
+  a.row_begin = rows.row_begin;
   a.out = indices;
   a.rs = logits_row_stride;
-  a.sq = num_seq_q;
+  a.sq = rows.num_seq_q;
   a.cols = static_cast<int>(num_cols);
   a.topk = topk;
-  a.nki = new_kv_included ? 1 : 0;
-  topk_kernel<<<num_batch * num_seq_q, kTopkThreads, 0, stream>>>(a);
+  a.nki = rows.new_kv_included ? 1 : 0;
+  topk_kernel<<<static_cast<int>(rows.rows()), kTopkThreads, 0, stream>>>(a);
   HPC_CHECK_LAUNCH();
   return HPC_OK;
 }
@@ -435,7 +382,7 @@ extern "C" int hpc_mla_indexer_plan(int num_batch, int num_seq_q, int num_head, 
   hpc::MlaIndexerRoute r = hpc::mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, logits_only,
                                                   num_cu > 0 ? num_cu : 256);
   if (r.code == HPC_OK && num_cu <= 0 && num_batch > 0)
-    r = hpc::mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, logits_only, current_cu_count());
+    r = hpc::mla_indexer_route(num_batch, num_seq_q, num_head, block_size, max_blocks, topk, logits_only, hpc::current_cu_count());
   *grid = r.grid, *chunk = r.chunk, *topk_grid = r.topk_grid;
   *logits_row_stride = r.scratch.row_stride, *workspace_bytes = r.scratch.bytes;
   return r.code;
@@ -483,8 +430,8 @@ extern "C" const char* hpc_mla_indexer_logits_fp8_refusal(const float* logits, c
                                                           int num_batch, int num_seq_q, int num_head, int block_size,
                                                           int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes,
                                                           int64_t logits_row_stride) {
-  return logits_check(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
-                      max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride)
+  return hpc::mla_indexer_logits_check(MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, 0), logits, q, weights, k_cache, block_ids,
+                                       num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride)
       .why;
 }
 
@@ -493,69 +440,39 @@ extern "C" int hpc_mla_indexer_logits_fp8_async(float* logits, const void* q, co
                                                 int num_head, int block_size, int max_blocks, int num_blocks,
                                                 int64_t k_cache_block_stride_bytes, int64_t logits_row_stride,
                                                 int new_kv_included, hipStream_t stream) {
-  const MlaIndexerCheck c = logits_check(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
-                                         block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride);
-  if (c.code != HPC_OK) return c.code;
-  if (num_batch == 0) return HPC_OK;  // nothing to launch
-  return launch_logits(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
-                       max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride, new_kv_included, stream);
+  return launch_logits(MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, new_kv_included), logits, q, weights, k_cache, block_ids,
+                       num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride, stream);
 }
 
 extern "C" const char* hpc_mla_indexer_topk_refusal(const int* indices, const float* logits, const int* num_seq_kvcache,
                                                     int num_batch, int num_seq_q, int64_t num_cols, int topk,
                                                     int64_t logits_row_stride) {
-  return topk_check(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride).why;
+  return hpc::mla_indexer_topk_check(MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, 0), indices, logits, num_cols, topk,
+                                     logits_row_stride)
+      .why;
 }
 
 extern "C" int hpc_mla_indexer_topk_async(int* indices, const float* logits, const int* num_seq_kvcache, int num_batch,
                                           int num_seq_q, int64_t num_cols, int topk, int64_t logits_row_stride, int new_kv_included,
                                           hipStream_t stream) {
-  const MlaIndexerCheck c = topk_check(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride);
-  if (c.code != HPC_OK) return c.code;
-  if (num_batch == 0) return HPC_OK;  // nothing to launch
-  return launch_topk(indices, logits, num_seq_kvcache, num_batch, num_seq_q, num_cols, topk, logits_row_stride, new_kv_included,
-                     stream);
+  return launch_topk(MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, new_kv_included), indices, logits, num_cols, topk,
+                     logits_row_stride, stream);
 }
 
-// ---- the top-k of a ragged chunk: the same kernel with the row rule as the source of n_r --------------------------------------
-namespace {
-MlaIndexerCheck topk_prefill_check(const int* indices, const float* logits, const int* num_seqlen_per_req, const int* q_index,
-                                   int num_rows, int num_req, int row_begin, int64_t num_cols, int topk, int64_t logits_row_stride) {
-  using namespace hpc;
-  if (num_rows < 0 || num_req < 0 || row_begin < 0) return {HPC_ERR_INVALID, "num_rows, num_req and row_begin must not be negative"};
-  if (num_cols < 0) return {HPC_ERR_INVALID, "the logits' column count must not be negative"};
-  if (topk < 1 || topk > kIdxMaxTopk) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
-  if (num_cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "logits reach beyond 2^30 columns"};
-  if (static_cast<int64_t>(row_begin) + num_rows > INT32_MAX || num_req == INT32_MAX)
-    return {HPC_ERR_UNSUPPORTED, "row_begin + num_rows and num_req + 1 must fit int32"};
-  // a row that sees no more than topk tokens reads no logit, so a call over zero columns needs no logits at all
-  const bool work = num_rows > 0 && num_req > 0;
-  if (work && (!indices || !num_seqlen_per_req || !q_index || (!logits && num_cols > 0)))
-    return {HPC_ERR_INVALID, "indices, logits, num_seqlen_per_req and q_index must not be null"};
-  if (misaligned(indices, 4) || misaligned(logits, 4)) return {HPC_ERR_UNSUPPORTED, "indices and logits must be 4-byte aligned"};
-  if (logits_row_stride < num_cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least the column count"};
-  if (logits_row_stride > kSpan / 4 / INT32_MAX) return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
-  return {HPC_OK, nullptr};
-}
-}  // namespace
-
+// the top-k of a ragged chunk: the same check, launcher and kernel with the row rule as the source of what a row sees
 extern "C" const char* hpc_mla_indexer_topk_prefill_refusal(const int* indices, const float* logits, const int* num_seqlen_per_req,
                                                             const int* q_index, int num_rows, int num_req, int row_begin,
                                                             int64_t num_cols, int topk, int64_t logits_row_stride) {
-  return topk_prefill_check(indices, logits, num_seqlen_per_req, q_index, num_rows, num_req, row_begin, num_cols, topk,
-                            logits_row_stride)
+  return hpc::mla_indexer_topk_check(MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, row_begin), indices, logits,
+                                     num_cols, topk, logits_row_stride)
       .why;
 }
 
 extern "C" int hpc_mla_indexer_topk_prefill_async(int* indices, const float* logits, const int* num_seqlen_per_req,
                                                   const int* q_index, int num_rows, int num_req, int row_begin, int64_t num_cols,
                                                   int topk, int64_t logits_row_stride, hipStream_t stream) {
-  const MlaIndexerCheck c = topk_prefill_check(indices, logits, num_seqlen_per_req, q_index, num_rows, num_req, row_begin, num_cols,
-                                               topk, logits_row_stride);
-  if (c.code != HPC_OK) return c.code;
-  if (num_rows == 0 || num_req == 0) return HPC_OK;  // nothing to launch, as the writers of the cache
-  return launch_topk(indices, logits, num_seqlen_per_req, num_rows, 1, num_cols, topk, logits_row_stride, 1, stream, q_index,
-                     num_req, row_begin);
+  return launch_topk(MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, row_begin), indices, logits, num_cols, topk,
+                     logits_row_stride, stream);
 }
 
 extern "C" const char* hpc_mla_indexer_topk_fp8_refusal(const int* indices, const void* q, const float* weights,
@@ -563,27 +480,28 @@ extern "C" const char* hpc_mla_indexer_topk_fp8_refusal(const int* indices, cons
                                                         int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
                                                         int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
                                                         const void* workspace, int64_t workspace_bytes) {
-  return fused_check(indices, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
-                     max_blocks, num_blocks, k_cache_block_stride_bytes, topk, workspace, workspace_bytes)
+  return hpc::mla_indexer_fused_check(MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, 0), indices, q, weights, k_cache, block_ids,
+                                      num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, topk, 0, workspace,
+                                      workspace_bytes)
       .why;
 }
 
+// logits then top-k through the scratch, whose layout is mla_indexer_scratch()'s
 extern "C" int hpc_mla_indexer_topk_fp8_async(int* indices, const void* q, const float* weights, const void* k_cache,
                                               const int* block_ids, const int* num_seq_kvcache, int num_batch, int num_seq_q,
                                               int num_head, int block_size, int max_blocks, int num_blocks,
                                               int64_t k_cache_block_stride_bytes, int topk, int new_kv_included, void* workspace,
                                               int64_t workspace_bytes, hipStream_t stream) {
-  const MlaIndexerCheck c = fused_check(indices, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head,
-                                        block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, topk, workspace,
-                                        workspace_bytes);
+  const MlaRows rows = MlaRows::step(num_seq_kvcache, num_batch, num_seq_q, new_kv_included);
+  const MlaIndexerCheck c =
+      hpc::mla_indexer_fused_check(rows, indices, q, weights, k_cache, block_ids, num_head, block_size, max_blocks, num_blocks,
+                                   k_cache_block_stride_bytes, topk, 0, workspace, workspace_bytes);
   if (c.code != HPC_OK) return c.code;
-  if (num_batch == 0) return HPC_OK;  // nothing to launch
-  const hpc::MlaIndexerScratch ws =
-      hpc::mla_indexer_scratch(static_cast<int64_t>(num_batch) * num_seq_q, static_cast<int64_t>(max_blocks) * block_size);
+  if (!rows.work()) return HPC_OK;  // nothing to launch
+  const hpc::MlaIndexerScratch ws = hpc::mla_indexer_scratch(rows.rows(), static_cast<int64_t>(max_blocks) * block_size);
   float* logits = static_cast<float*>(workspace);
-  const int rc = launch_logits(logits, q, weights, k_cache, block_ids, num_seq_kvcache, num_batch, num_seq_q, num_head, block_size,
-                               max_blocks, num_blocks, k_cache_block_stride_bytes, ws.row_stride, new_kv_included, stream);
+  const int rc = launch_logits(rows, logits, q, weights, k_cache, block_ids, num_head, block_size, max_blocks, num_blocks,
+                               k_cache_block_stride_bytes, ws.row_stride, stream);
   if (rc != HPC_OK) return rc;
-  return launch_topk(indices, logits, num_seq_kvcache, num_batch, num_seq_q, ws.row_stride, topk, ws.row_stride, new_kv_included,
-                     stream);
+  return launch_topk(rows, indices, logits, ws.row_stride, topk, ws.row_stride, stream);
 }

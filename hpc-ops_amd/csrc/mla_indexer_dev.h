@@ -2,8 +2,8 @@
 // once: the request and position of a row, the cache cell of a token with its guards, the 16-lane abs-max, the 128-column
 // quantiser on a vector held as 8 columns per lane, and the store of a token's 128 + 4 bytes.  Internal, device only.
 // Behind them what the READERS share (mla_indexer.hip: logits_kernel, topk_kernel; mla_indexer_prefill.hip: logits_prefill_kernel;
-// attention_decode_mla.hip: the sparse form over a ragged chunk): the operand roles, the key block and the head sum of a logit,
-// and the ragged row rule as what a row sees.
+// attention_decode_mla.hip: the token-sparse form): the operand roles, the key block and the head sum of a logit, and the two
+// row rules as what a row sees - row_sees for a ragged chunk, step_sees for a decode step.
 #pragma once
 #include "act_quant.h"
 #include "hpc_common.h"
@@ -140,6 +140,15 @@ __device__ __forceinline__ RowSees row_sees(const int* q_index, const int* seqle
   const RowAt at = locate_row(q_index, seqlen, num_req, row);
   return {at.req, at.live ? clamp_len(at.pos + 1, cols) : 0};
 }
+
+// The decode-step row rule of the readers: what row (b, s) of a step of sq rows per request sees.  step_len is the request's
+// length including the new tokens, L = lens[b] + (new_kv_included ? 0 : sq); row s sees the L - sq + s + 1 first of them, never
+// beyond the page table's reach (so a position below vis has a page-table entry).  Two functions, so that a kernel with several
+// rows of a request forms L once.
+__device__ __forceinline__ long step_len(int len_b, int sq, int new_kv_included) {
+  return static_cast<long>(len_b) + (new_kv_included ? 0 : sq);
+}
+__device__ __forceinline__ int step_sees(long len, int sq, int s, int cols) { return clamp_len(len - sq + s + 1, cols); }
 
 }  // namespace mla_indexer
 }  // namespace hpc

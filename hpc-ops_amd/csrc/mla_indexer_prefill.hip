@@ -201,62 +201,10 @@ __global__ __launch_bounds__(kPrefillThreads) void logits_prefill_kernel(const P
 }  // namespace mla_indexer
 }  // namespace hpc
 
-namespace {
+// ---- C-ABI: the host rules of these entries are mla_indexer_route.h's, the ones of a decode step's with a chunk's rows --------------
 using hpc::MlaIndexerCheck;
+using hpc::MlaRows;
 
-int current_cu_count() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess ? hpc_get_cu_count(dev) : 0;
-}
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-constexpr int64_t kSpan = int64_t{1} << 60;  // bytes: page id x block stride stays below 2^61
-
-// ---- the host rules: the refusal code and its reason in words, no device call ----------------------------------------------------
-MlaIndexerCheck logits_check(const float* logits, const void* q, const float* weights, const void* k_cache, const int* block_ids,
-                             const int* num_seqlen_per_req, const int* q_index, int num_rows, int num_req, int row_begin,
-                             int num_head, int block_size, int max_blocks, int num_blocks, int64_t block_stride,
-                             int64_t logits_row_stride) {
-  using namespace hpc;
-  const MlaIndexerPrefillRoute r = mla_indexer_prefill_route(num_rows, num_req, num_head, block_size, max_blocks, 0, true, 0, 256);
-  if (r.code != HPC_OK) return {r.code, r.why};
-  if (num_blocks < 0 || row_begin < 0) return {HPC_ERR_INVALID, "num_blocks and row_begin must not be negative"};
-  if (static_cast<int64_t>(row_begin) + num_rows + kIdxPrefillTile > INT32_MAX)
-    return {HPC_ERR_UNSUPPORTED, "row_begin + num_rows beyond int32"};
-  const MlaIndexerCheck cache = mla_indexer_cache_check(reinterpret_cast<uintptr_t>(k_cache), block_size, block_stride);
-  if (cache.code != HPC_OK) return cache;
-  const bool work = num_rows > 0 && num_req > 0;
-  if (work && (!logits || !q || !weights || !k_cache || !block_ids || !num_seqlen_per_req || !q_index))
-    return {HPC_ERR_INVALID, "logits, q, weights, k_cache, block_ids, num_seqlen_per_req and q_index must not be null"};
-  if (work && max_blocks == 0) return {HPC_ERR_INVALID, "block_ids has no columns"};
-  if (misaligned(q, 16) || misaligned(weights, 16) || misaligned(logits, 4))
-    return {HPC_ERR_UNSUPPORTED, "q and weights must be 16-byte aligned, logits 4-byte"};
-  if (logits_row_stride < r.cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least max_blocks * block_size"};
-  if (logits_row_stride > kSpan / 4 / INT32_MAX || (num_blocks > 0 && block_stride > kSpan / num_blocks))
-    return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
-  return {HPC_OK, nullptr};
-}
-
-MlaIndexerCheck fused_check(const int* indices, const void* q, const float* weights, const void* k_cache, const int* block_ids,
-                            const int* num_seqlen_per_req, const int* q_index, int num_rows, int num_req, int num_head,
-                            int block_size, int max_blocks, int num_blocks, int64_t block_stride, int topk, int scratch_rows,
-                            const void* workspace, int64_t workspace_bytes) {
-  using namespace hpc;
-  const MlaIndexerPrefillRoute r =
-      mla_indexer_prefill_route(num_rows, num_req, num_head, block_size, max_blocks, topk, false, scratch_rows, 256);
-  if (r.code != HPC_OK) return {r.code, r.why};
-  const bool work = num_rows > 0 && num_req > 0;
-  if (work && !indices) return {HPC_ERR_INVALID, "indices must not be null"};
-  if (misaligned(indices, 4)) return {HPC_ERR_UNSUPPORTED, "indices must be 4-byte aligned"};
-  // the scratch stands in for the logits; without work neither is looked at
-  const float* ws = work ? static_cast<const float*>(workspace) : nullptr;
-  if (work && (!workspace || workspace_bytes < r.scratch.bytes))
-    return {HPC_ERR_INVALID, "the workspace is missing or smaller than hpc_mla_indexer_prefill_plan's workspace_bytes"};
-  return logits_check(ws, q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, num_rows, num_req, 0, num_head, block_size,
-                      max_blocks, num_blocks, block_stride, r.scratch.row_stride);
-}
-}  // namespace
-
-// ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
 extern "C" int hpc_mla_indexer_prefill_plan(int num_rows, int num_req, int num_head, int block_size, int max_blocks, int topk,
                                             int scratch_rows, int num_cu, int* tile, int* grid, int* chunk, int* slab_rows,
                                             int* slabs, int64_t* logits_row_stride, int64_t* workspace_bytes) {
@@ -266,7 +214,7 @@ extern "C" int hpc_mla_indexer_prefill_plan(int num_rows, int num_req, int num_h
                                                                  logits_only, scratch_rows, num_cu > 0 ? num_cu : 256);
   if (r.code == HPC_OK && num_cu <= 0 && num_rows > 0 && num_req > 0)
     r = hpc::mla_indexer_prefill_route(num_rows, num_req, num_head, block_size, max_blocks, topk, logits_only, scratch_rows,
-                                       current_cu_count());
+                                       hpc::current_cu_count());
   *tile = r.tile, *grid = r.grid, *chunk = r.chunk, *slab_rows = r.slab_rows, *slabs = r.slabs;
   *logits_row_stride = r.scratch.row_stride, *workspace_bytes = r.scratch.bytes;
   return r.code;
@@ -278,8 +226,9 @@ extern "C" const char* hpc_mla_indexer_logits_prefill_fp8_refusal(const float* l
                                                                   int num_req, int row_begin, int num_head, int block_size,
                                                                   int max_blocks, int num_blocks, int64_t k_cache_block_stride_bytes,
                                                                   int64_t logits_row_stride) {
-  return logits_check(logits, q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, num_rows, num_req, row_begin, num_head,
-                      block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, logits_row_stride)
+  return hpc::mla_indexer_logits_check(MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, row_begin), logits, q, weights,
+                                       k_cache, block_ids, num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes,
+                                       logits_row_stride)
       .why;
 }
 
@@ -290,11 +239,11 @@ extern "C" int hpc_mla_indexer_logits_prefill_fp8_async(float* logits, const voi
                                                         int64_t logits_row_stride, hipStream_t stream) {
   using namespace hpc;
   using namespace hpc::mla_indexer;
-  const MlaIndexerCheck c = logits_check(logits, q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, num_rows, num_req,
-                                         row_begin, num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes,
-                                         logits_row_stride);
+  const MlaRows rows = MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, row_begin);
+  const MlaIndexerCheck c = mla_indexer_logits_check(rows, logits, q, weights, k_cache, block_ids, num_head, block_size, max_blocks,
+                                                     num_blocks, k_cache_block_stride_bytes, logits_row_stride);
   if (c.code != HPC_OK) return c.code;
-  if (num_rows == 0 || num_req == 0) return HPC_OK;  // nothing to launch
+  if (!rows.work()) return HPC_OK;  // nothing to launch
   const MlaIndexerPrefillRoute r =
       mla_indexer_prefill_route(num_rows, num_req, num_head, block_size, max_blocks, 0, true, 0, current_cu_count());
   if (r.code != HPC_OK) return r.code;
@@ -332,8 +281,9 @@ extern "C" const char* hpc_mla_indexer_topk_prefill_fp8_refusal(const int* indic
                                                                 int num_req, int num_head, int block_size, int max_blocks,
                                                                 int num_blocks, int64_t k_cache_block_stride_bytes, int topk,
                                                                 int scratch_rows, const void* workspace, int64_t workspace_bytes) {
-  return fused_check(indices, q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, num_rows, num_req, num_head, block_size,
-                     max_blocks, num_blocks, k_cache_block_stride_bytes, topk, scratch_rows, workspace, workspace_bytes)
+  return hpc::mla_indexer_fused_check(MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, 0), indices, q, weights, k_cache,
+                                      block_ids, num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, topk,
+                                      scratch_rows, workspace, workspace_bytes)
       .why;
 }
 
@@ -346,11 +296,12 @@ extern "C" int hpc_mla_indexer_topk_prefill_fp8_async(int* indices, const void* 
                                                       int num_blocks, int64_t k_cache_block_stride_bytes, int topk, int scratch_rows,
                                                       void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   using namespace hpc;
-  const MlaIndexerCheck c = fused_check(indices, q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, num_rows, num_req,
-                                        num_head, block_size, max_blocks, num_blocks, k_cache_block_stride_bytes, topk, scratch_rows,
-                                        workspace, workspace_bytes);
+  const MlaRows rows = MlaRows::chunk(num_seqlen_per_req, q_index, num_rows, num_req, 0);
+  const MlaIndexerCheck c = mla_indexer_fused_check(rows, indices, q, weights, k_cache, block_ids, num_head, block_size, max_blocks,
+                                                    num_blocks, k_cache_block_stride_bytes, topk, scratch_rows, workspace,
+                                                    workspace_bytes);
   if (c.code != HPC_OK) return c.code;
-  if (num_rows == 0 || num_req == 0) return HPC_OK;  // nothing to launch
+  if (!rows.work()) return HPC_OK;  // nothing to launch
   const MlaIndexerPrefillRoute r =
       mla_indexer_prefill_route(num_rows, num_req, num_head, block_size, max_blocks, topk, false, scratch_rows, 256);
   float* logits = static_cast<float*>(workspace);

@@ -1,9 +1,17 @@
-// The DSA lightning indexer (mla_indexer.hip), stated once: the paged index-key cache, the host rule for a cache a launcher
-// accepts, the one route of the logits / top-k ops - the grid, the chunking of the context, the scratch of the fused call and
-// every refusal with its reason in words -, the one route of the same ops over a ragged prefill chunk (mla_indexer_prefill.hip:
-// row tile, chunk, grid, slab, scratch, refusals) and the one host rule of the front end (mla_indexer_prep.hip) at the end.
-// Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip, mla_indexer_prefill.hip and mla_indexer_prep.hip, hpc_mla_indexer_plan
-// and the torch shim (torch_mla_indexer.cpp) all read it.
+// The DSA lightning indexer, stated once.  In this order:
+//   the cache    the paged index-key cache and the host rule for a cache a launcher accepts (mla_indexer_cache_check);
+//   the rows     MlaRows, where the rows of a reader's call come from - a decode step (num_seq_kvcache, mtp, new_kv_included) or
+//                a ragged prefill chunk (num_seqlen_per_req, q_index, row_begin) - with the refusals, the row count and the
+//                "is there work" of either.  The logits / top-k launchers and the token-sparse MLA attention
+//                (attention_decode_mla.hip) all take it;
+//   the routes   mla_indexer_route() of a decode step (mla_indexer.hip: grid, chunking of the context, scratch of the fused
+//                call) and mla_indexer_prefill_route() of a chunk (mla_indexer_prefill.hip: row tile, chunk, grid, slab,
+//                scratch).  What both refuse of a shape is mla_indexer_shape(), how both cut the columns mla_indexer_chunk();
+//   the checks   mla_indexer_logits_check, _topk_check and _fused_check: every refusal of the six reader entries with its reason
+//                in words, one function per op for both forms, given the rows and the form's route;
+//   the front end  the one host rule of mla_indexer_prep.hip, at the end.
+// Internal header, plain C++17, no HIP header: the launchers of mla_indexer.hip, mla_indexer_prefill.hip and
+// mla_indexer_prep.hip, the plan entries and the torch shim (torch_mla_indexer.cpp) all read it.
 //
 // The index-key cache.  Every token of every request has ONE index key of 128 columns, shared by all index heads: 128
 // float8_e4m3fn codes and one float32 scale, column d = fp32(code[d]) * scale, for any finite non-negative scale.  The cache is
@@ -14,6 +22,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "byte_span.h"
 #include "hpc_status.h"
 #include "mla_cache.h"
 
@@ -57,6 +66,69 @@ struct MlaIndexerScratch {
 };
 static inline MlaIndexerScratch mla_indexer_scratch(int64_t rows, int64_t cols) { return {cols, rows * cols * 4}; }
 
+// ---- the rows of a call ------------------------------------------------------------------------------------------------------
+// A decode step: num_batch requests of num_seq_q rows each, row r is (b, s) = (r / num_seq_q, r % num_seq_q), lens is
+// num_seq_kvcache [num_batch].  A ragged chunk: num_rows rows that the writers' row rule (mla_indexer_dev.h::locate_row) places
+// in num_req requests, lens is num_seqlen_per_req [num_req], q_index [num_req + 1], and row r of the call is row row_begin + r of
+// the chunk.  What a row sees is the device's (mla_indexer_dev.h: step_sees, row_sees).  The pointers are held as given and
+// never dereferenced on the host.
+struct MlaRows {
+  bool ragged;
+  const int* lens;
+  const int* q_index;                         // a chunk's; null for a step
+  int num_batch, num_seq_q, new_kv_included;  // a step's; a chunk holds (0, 1, 1): what the shared kernels are told
+  int num_rows, num_req, row_begin;           // a chunk's; zeros for a step
+
+  static MlaRows step(const int* lens, int num_batch, int num_seq_q, int new_kv_included) {
+    return {false, lens, nullptr, num_batch, num_seq_q, new_kv_included, 0, 0, 0};
+  }
+  static MlaRows chunk(const int* lens, const int* q_index, int num_rows, int num_req, int row_begin) {
+    return {true, lens, q_index, 0, 1, 1, num_rows, num_req, row_begin};
+  }
+  int64_t rows() const { return ragged ? num_rows : static_cast<int64_t>(num_batch) * num_seq_q; }
+  bool work() const { return ragged ? num_rows > 0 && num_req > 0 : num_batch > 0; }  // without it nothing is launched
+  bool tables() const { return lens && (!ragged || q_index); }                        // what a call with work reads
+  // the refusals: the counts that make no sense, then what the kernels' int32 arithmetic does not hold.  pad: the rows past
+  // its last that a chunk's logits call counts (its row tile)
+  MlaIndexerCheck negative() const {
+    if (ragged && (num_rows < 0 || num_req < 0 || row_begin < 0))
+      return {HPC_ERR_INVALID, "num_rows, num_req and row_begin must not be negative"};
+    if (!ragged && num_batch < 0) return {HPC_ERR_INVALID, "num_batch must not be negative"};
+    if (!ragged && num_seq_q <= 0) return {HPC_ERR_INVALID, "num_seq_q must be positive"};
+    return {HPC_OK, nullptr};
+  }
+  MlaIndexerCheck limits(int pad = 0) const {
+    if (!ragged && num_seq_q > kIdxMaxSeqQ) return {HPC_ERR_UNSUPPORTED, "mtp must be 0 .. 3"};
+    if (!ragged && rows() > INT32_MAX) return {HPC_ERR_UNSUPPORTED, "num_batch * num_seq_q beyond int32"};
+    if (ragged && (static_cast<int64_t>(row_begin) + num_rows + pad > INT32_MAX || num_req == INT32_MAX))
+      return {HPC_ERR_UNSUPPORTED, "row_begin + num_rows and num_req + 1 must fit int32"};
+    return {HPC_OK, nullptr};
+  }
+};
+
+// ---- what the two routes share -------------------------------------------------------------------------------------------------
+// The shape refusals: head count, page size, list length (logits_only: not looked at) and columns; head_blocks and cols are set
+// on the way
+static inline MlaIndexerCheck mla_indexer_shape(int num_head, int block_size, int max_blocks, int topk, bool logits_only,
+                                                int* head_blocks, int64_t* cols) {
+  if (num_head != 16 && num_head != 32 && num_head != 64) return {HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64"};
+  if (mla_page_shift(block_size) < 0) return {HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128"};
+  if (!logits_only && (topk < 1 || topk > kIdxMaxTopk)) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
+  *head_blocks = num_head / 16;
+  *cols = static_cast<int64_t>(max_blocks) * block_size;
+  if (*cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "block_ids reaches beyond 2^30 tokens"};
+  return {HPC_OK, nullptr};
+}
+// The chunk rule: the columns one logits workgroup owns are 512, doubled up to 8192 while `units` (requests of a step, row tiles
+// of a chunk's launch) times the chunks of a row are beyond 16 workgroups per CU - a host value: nothing here or on the device
+// depends on the lengths of the requests for it.  cu_count <= 0: 256.
+static inline int mla_indexer_chunk(int64_t units, int64_t cols, int cu_count) {
+  const int cus = cu_count > 0 ? cu_count : 256;
+  int chunk = kIdxMinChunk;
+  while (chunk < kIdxMaxChunk && units * ((cols + chunk - 1) / chunk) > 16ll * cus) chunk *= 2;
+  return chunk;
+}
+
 struct MlaIndexerRoute {
   int code;          // HPC_OK or the refusal; the rest is set either way (zeros where it has no meaning)
   const char* why;   // the refusal in words (null when accepted)
@@ -69,9 +141,8 @@ struct MlaIndexerRoute {
   MlaIndexerScratch scratch;  // of the fused call
 };
 
-// logits_only: the list length has no part in the call and topk is not looked at; otherwise 1 .. 65536.  The chunk: 512 tokens, doubled while
-// the grid is beyond 16 workgroups per CU, up to 8192 - a host value: nothing here or on the device depends on the lengths of
-// the requests for it.  cu_count <= 0: 256.
+// logits_only: the list length has no part in the call and topk is not looked at; otherwise 1 .. 65536.  The chunk is
+// mla_indexer_chunk()'s with the requests as units.
 static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, int num_head, int block_size, int max_blocks,
                                                 int topk, bool logits_only, int cu_count) {
   MlaIndexerRoute r{};
@@ -80,25 +151,16 @@ static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, in
     r.why = why;
     return r;
   };
-  if (num_batch < 0) return refuse(HPC_ERR_INVALID, "num_batch must not be negative");
-  if (num_seq_q <= 0) return refuse(HPC_ERR_INVALID, "num_seq_q must be positive");
-  if (max_blocks < 0) return refuse(HPC_ERR_INVALID, "max_blocks must not be negative");
-  if (num_seq_q > kIdxMaxSeqQ) return refuse(HPC_ERR_UNSUPPORTED, "mtp must be 0 .. 3");
-  if (num_head != 16 && num_head != 32 && num_head != 64) return refuse(HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64");
-  if (mla_page_shift(block_size) < 0) return refuse(HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128");
-  if (!logits_only && (topk < 1 || topk > kIdxMaxTopk)) return refuse(HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536");
-  r.head_blocks = num_head / 16;
-  r.cols = static_cast<int64_t>(max_blocks) * block_size;
-  if (r.cols > kIdxMaxCols) return refuse(HPC_ERR_UNSUPPORTED, "block_ids reaches beyond 2^30 tokens");
-  const int64_t rows = static_cast<int64_t>(num_batch) * num_seq_q;
-  if (rows > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "num_batch * num_seq_q beyond int32");
-  r.topk_grid = static_cast<int>(rows);
-  r.scratch = mla_indexer_scratch(rows, r.cols);
-  const int cus = cu_count > 0 ? cu_count : 256;
-  int64_t chunk = kIdxMinChunk;
-  while (chunk < kIdxMaxChunk && num_batch * ((r.cols + chunk - 1) / chunk) > 16ll * cus) chunk *= 2;
-  r.chunk = static_cast<int>(chunk);
-  r.chunks = static_cast<int>((r.cols + chunk - 1) / chunk);
+  const MlaRows rows = MlaRows::step(nullptr, num_batch, num_seq_q, 1);
+  MlaIndexerCheck c = rows.negative();
+  if (c.code == HPC_OK && max_blocks < 0) c = {HPC_ERR_INVALID, "max_blocks must not be negative"};
+  if (c.code == HPC_OK) c = rows.limits();
+  if (c.code == HPC_OK) c = mla_indexer_shape(num_head, block_size, max_blocks, topk, logits_only, &r.head_blocks, &r.cols);
+  if (c.code != HPC_OK) return refuse(c.code, c.why);
+  r.topk_grid = static_cast<int>(rows.rows());
+  r.scratch = mla_indexer_scratch(rows.rows(), r.cols);
+  r.chunk = mla_indexer_chunk(num_batch, r.cols, cu_count);
+  r.chunks = static_cast<int>((r.cols + r.chunk - 1) / r.chunk);
   const int64_t grid = static_cast<int64_t>(num_batch) * r.chunks;
   if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
   r.grid = static_cast<int>(grid);
@@ -110,8 +172,7 @@ static inline MlaIndexerRoute mla_indexer_route(int num_batch, int num_seq_q, in
 // key-stationary: a workgroup stages a tile of kIdxPrefillTile q rows (codes and weights) in LDS once and runs all of them
 // against every 64-key step of its chunk of columns, so a key tile is loaded once per row tile.  Tiles are cut from the row
 // index of the call, not per request, which makes the grid a host value: ceil(rows / tile) * chunks; the chunking of the columns
-// is the decode route's - 512, doubled up to 8192 while the grid is beyond 16 workgroups per CU - with the tile count in the
-// place of the request count.
+// is mla_indexer_chunk()'s with the row tiles of a launch as units.
 // The fused call runs logits then top-k over slabs of rows through one float32 scratch [slab_rows, cols]; the slab is the
 // caller's (scratch_rows > 0) or, with 0, what fits kIdxPrefillScratchBytes.  That budget is a resource cap, not a tuned number:
 // 256 MiB holds the logits of a 2048-row slab over a 32k-token table, so that the scratch does not grow with the chunk while a
@@ -153,16 +214,14 @@ static inline MlaIndexerPrefillRoute mla_indexer_prefill_route(int num_rows, int
     r.why = why;
     return r;
   };
-  if (num_rows < 0 || num_req < 0) return refuse(HPC_ERR_INVALID, "num_rows and num_req must not be negative");
-  if (max_blocks < 0) return refuse(HPC_ERR_INVALID, "max_blocks must not be negative");
-  if (!logits_only && scratch_rows < 0) return refuse(HPC_ERR_INVALID, "scratch_rows must be 0 (the library chooses) or a row count");
-  if (num_head != 16 && num_head != 32 && num_head != 64) return refuse(HPC_ERR_UNSUPPORTED, "the index head count must be 16, 32 or 64");
-  if (mla_page_shift(block_size) < 0) return refuse(HPC_ERR_UNSUPPORTED, "block_size must be 16, 32, 64 or 128");
-  if (!logits_only && (topk < 1 || topk > kIdxMaxTopk)) return refuse(HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536");
-  if (num_req == 0x7fffffff) return refuse(HPC_ERR_UNSUPPORTED, "num_req + 1 beyond int32");
-  r.head_blocks = num_head / 16;
-  r.cols = static_cast<int64_t>(max_blocks) * block_size;
-  if (r.cols > kIdxMaxCols) return refuse(HPC_ERR_UNSUPPORTED, "block_ids reaches beyond 2^30 tokens");
+  const MlaRows rows = MlaRows::chunk(nullptr, nullptr, num_rows, num_req, 0);
+  MlaIndexerCheck c = rows.negative();
+  if (c.code == HPC_OK && max_blocks < 0) c = {HPC_ERR_INVALID, "max_blocks must not be negative"};
+  if (c.code == HPC_OK && !logits_only && scratch_rows < 0)
+    c = {HPC_ERR_INVALID, "scratch_rows must be 0 (the library chooses) or a row count"};
+  if (c.code == HPC_OK) c = rows.limits();
+  if (c.code == HPC_OK) c = mla_indexer_shape(num_head, block_size, max_blocks, topk, logits_only, &r.head_blocks, &r.cols);
+  if (c.code != HPC_OK) return refuse(c.code, c.why);
   r.tile = kIdxPrefillTile;
   r.tiles = static_cast<int>((static_cast<int64_t>(num_rows) + r.tile - 1) / r.tile);
   r.topk_grid = num_rows;
@@ -178,16 +237,90 @@ static inline MlaIndexerPrefillRoute mla_indexer_prefill_route(int num_rows, int
   r.slab_rows = static_cast<int>(slab);
   r.slabs = slab > 0 ? static_cast<int>((num_rows + slab - 1) / slab) : 0;
   r.scratch = mla_indexer_scratch(logits_only ? 0 : slab, r.cols);
-  const int cus = cu_count > 0 ? cu_count : 256;
-  const int64_t call_tiles = (slab + r.tile - 1) / r.tile;
-  int64_t chunk = kIdxMinChunk;
-  while (chunk < kIdxMaxChunk && call_tiles * ((r.cols + chunk - 1) / chunk) > 16ll * cus) chunk *= 2;
-  r.chunk = static_cast<int>(chunk);
-  r.chunks = static_cast<int>((r.cols + chunk - 1) / chunk);
+  r.chunk = mla_indexer_chunk((slab + r.tile - 1) / r.tile, r.cols, cu_count);
+  r.chunks = static_cast<int>((r.cols + r.chunk - 1) / r.chunk);
   const int64_t grid = static_cast<int64_t>(r.tiles) * r.chunks;
   if (grid > 0x7fffffffll) return refuse(HPC_ERR_UNSUPPORTED, "the logits grid is beyond int32");
   r.grid = num_req > 0 ? static_cast<int>(grid) : 0;
   return r;
+}
+
+// ---- the host rules of the six reader entries, one function per op for both forms: the refusal code and its reason in words, no
+// device call.  Each takes the rows of the call and, through them, the form's route. -------------------------------------------
+struct MlaIndexerRouted {  // what a check takes from either route
+  int code;
+  const char* why;
+  int64_t cols;
+  MlaIndexerScratch scratch;
+};
+static inline MlaIndexerRouted mla_indexer_routed(const MlaRows& rows, int num_head, int block_size, int max_blocks, int topk,
+                                                  bool logits_only, int scratch_rows) {
+  if (rows.ragged) {
+    const MlaIndexerPrefillRoute r = mla_indexer_prefill_route(rows.num_rows, rows.num_req, num_head, block_size, max_blocks, topk,
+                                                               logits_only, scratch_rows, 256);
+    return {r.code, r.why, r.cols, r.scratch};
+  }
+  const MlaIndexerRoute r = mla_indexer_route(rows.num_batch, rows.num_seq_q, num_head, block_size, max_blocks, topk, logits_only, 256);
+  return {r.code, r.why, r.cols, r.scratch};
+}
+
+static inline MlaIndexerCheck mla_indexer_logits_check(const MlaRows& rows, const float* logits, const void* q, const float* weights,
+                                                       const void* k_cache, const int* block_ids, int num_head, int block_size,
+                                                       int max_blocks, int num_blocks, int64_t block_stride,
+                                                       int64_t logits_row_stride) {
+  const MlaIndexerRouted r = mla_indexer_routed(rows, num_head, block_size, max_blocks, 0, true, 0);
+  if (r.code != HPC_OK) return {r.code, r.why};
+  if (num_blocks < 0) return {HPC_ERR_INVALID, "num_blocks must not be negative"};
+  if (rows.row_begin < 0) return {HPC_ERR_INVALID, "row_begin must not be negative"};
+  const MlaIndexerCheck fits = rows.limits(kIdxPrefillTile);
+  if (fits.code != HPC_OK) return fits;
+  const MlaIndexerCheck cache = mla_indexer_cache_check(reinterpret_cast<uintptr_t>(k_cache), block_size, block_stride);
+  if (cache.code != HPC_OK) return cache;
+  if (rows.work() && (!logits || !q || !weights || !k_cache || !block_ids || !rows.tables()))
+    return {HPC_ERR_INVALID, "logits, q, weights, k_cache, block_ids and the rows' tables (the lengths, a chunk's q_index) must not be null"};
+  if (rows.work() && max_blocks == 0) return {HPC_ERR_INVALID, "block_ids has no columns"};
+  if (misaligned(q, 16) || misaligned(weights, 16) || misaligned(logits, 4))
+    return {HPC_ERR_UNSUPPORTED, "q and weights must be 16-byte aligned, logits 4-byte"};
+  if (logits_row_stride < r.cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least max_blocks * block_size"};
+  if (logits_row_stride > kMaxSpan / 4 / INT32_MAX || (num_blocks > 0 && block_stride > kMaxSpan / num_blocks))
+    return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+
+static inline MlaIndexerCheck mla_indexer_topk_check(const MlaRows& rows, const int* indices, const float* logits, int64_t num_cols,
+                                                     int topk, int64_t logits_row_stride) {
+  MlaIndexerCheck c = rows.negative();
+  if (c.code == HPC_OK && num_cols < 0) c = {HPC_ERR_INVALID, "the logits' column count must not be negative"};
+  if (c.code == HPC_OK) c = rows.limits();
+  if (c.code != HPC_OK) return c;
+  if (topk < 1 || topk > kIdxMaxTopk) return {HPC_ERR_UNSUPPORTED, "topk must be 1 .. 65536"};
+  if (num_cols > kIdxMaxCols) return {HPC_ERR_UNSUPPORTED, "logits reach beyond 2^30 columns"};
+  // a row that sees no more than topk tokens reads no logit, so a call over zero columns needs no logits at all
+  if (rows.work() && (!indices || !rows.tables() || (!logits && num_cols > 0)))
+    return {HPC_ERR_INVALID, "indices, logits and the rows' tables (the lengths, a chunk's q_index) must not be null"};
+  if (misaligned(indices, 4) || misaligned(logits, 4)) return {HPC_ERR_UNSUPPORTED, "indices and logits must be 4-byte aligned"};
+  if (logits_row_stride < num_cols) return {HPC_ERR_UNSUPPORTED, "logits row stride must be at least the column count"};
+  if (logits_row_stride > kMaxSpan / 4 / INT32_MAX) return {HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes"};
+  return {HPC_OK, nullptr};
+}
+
+// The fused call: the scratch stands in for the logits (without work neither is looked at), then the two checks above.  A
+// chunk's list is looked at before its scratch, a step's behind the logits' rules: a call with two faults keeps its code.
+static inline MlaIndexerCheck mla_indexer_fused_check(const MlaRows& rows, const int* indices, const void* q, const float* weights,
+                                                      const void* k_cache, const int* block_ids, int num_head, int block_size,
+                                                      int max_blocks, int num_blocks, int64_t block_stride, int topk,
+                                                      int scratch_rows, const void* workspace, int64_t workspace_bytes) {
+  const MlaIndexerRouted r = mla_indexer_routed(rows, num_head, block_size, max_blocks, topk, false, scratch_rows);
+  if (r.code != HPC_OK) return {r.code, r.why};
+  if (rows.ragged && rows.work() && !indices) return {HPC_ERR_INVALID, "indices must not be null"};
+  if (rows.ragged && misaligned(indices, 4)) return {HPC_ERR_UNSUPPORTED, "indices must be 4-byte aligned"};
+  const float* ws = rows.work() ? static_cast<const float*>(workspace) : nullptr;
+  if (rows.work() && (!workspace || workspace_bytes < r.scratch.bytes))
+    return {HPC_ERR_INVALID, "the workspace is missing or smaller than the workspace_bytes of the form's plan entry"};
+  const MlaIndexerCheck c = mla_indexer_logits_check(rows, ws, q, weights, k_cache, block_ids, num_head, block_size, max_blocks,
+                                                     num_blocks, block_stride, r.scratch.row_stride);
+  if (c.code != HPC_OK) return c;
+  return mla_indexer_topk_check(rows, indices, ws, r.cols, topk, r.scratch.row_stride);
 }
 
 // ---- the front end (mla_indexer_prep.hip): LayerNorm + RoPE + rotation + quantisation of the index key and the index queries ----
@@ -231,7 +364,6 @@ static inline MlaIndexerPrepRoute mla_indexer_prep_route(const MlaIndexerPrepCal
     r.why = why;
     return r;
   };
-  constexpr int64_t span = int64_t{1} << 60;  // bytes: page id x block stride and row x row stride stay below 2^61
   if (c.num_rows < 0 || c.num_req < 0 || c.max_blocks < 0 || c.num_blocks < 0 || c.max_pos < 0)
     return refuse(HPC_ERR_INVALID, "num_rows, num_req, max_blocks, num_blocks and max_pos must not be negative");
   if (!c.k_cache && !c.out_k) return refuse(HPC_ERR_INVALID, "the key has no destination: one of k_cache and out_k must be given");
@@ -272,8 +404,8 @@ static inline MlaIndexerPrepRoute mla_indexer_prep_route(const MlaIndexerPrepCal
   r.vectors = static_cast<int64_t>(c.num_rows) * (with_q ? 1 + c.num_head : 1);
   if (r.vectors > 0x7fffffffll - kIdxPrepVectors || c.num_req == 0x7fffffff)
     return refuse(HPC_ERR_UNSUPPORTED, "num_rows * (1 + num_head) vectors do not fit int32");
-  if (c.k_row_stride > span / 2 / 0x7fffffffll || (with_q && c.q_row_stride > span / 2 / 0x7fffffffll) ||
-      (c.k_cache && c.num_blocks > 0 && c.block_stride > span / c.num_blocks))
+  if (c.k_row_stride > kMaxSpan / 2 / 0x7fffffffll || (with_q && c.q_row_stride > kMaxSpan / 2 / 0x7fffffffll) ||
+      (c.k_cache && c.num_blocks > 0 && c.block_stride > kMaxSpan / c.num_blocks))
     return refuse(HPC_ERR_UNSUPPORTED, "strides whose offsets would leave 2^60 bytes");
   r.grid = work ? static_cast<int>((r.vectors + kIdxPrepVectors - 1) / kIdxPrepVectors) : 0;
   return r;

@@ -31,6 +31,19 @@ inline const char* err_text(int code) {
 }
 #define HPC_LAUNCH_CHECK(rc, what) TORCH_CHECK((rc) == 0, what, " launch failed! (", ::hpc_torch::err_text(rc), ")")
 
+// An op whose C entry has a `_refusal` twin: the refusal in words first, then - with work - the launch.  The launcher's
+// arguments are the refusal's plus `tail` (a stream, or flags and a stream), so the list is stated once and the call that was
+// checked is the call that is launched.
+template <class Refusal, class Launch, class... Args, class... Tail>
+void checked_launch(const char* op, Refusal refusal, Launch launch, bool work, const std::tuple<Args...>& args,
+                    const std::tuple<Tail...>& tail) {
+  const char* why = std::apply(refusal, args);
+  TORCH_CHECK(why == nullptr, op, ": ", why);
+  if (!work) return;  // nothing to launch
+  const int rc = std::apply(launch, std::tuple_cat(args, tail));
+  HPC_LAUNCH_CHECK(rc, op);
+}
+
 inline void* ptr(const at::Tensor& t) { return t.data_ptr(); }
 inline void* ptr(const c10::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
 

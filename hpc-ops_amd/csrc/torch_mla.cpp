@@ -1,18 +1,22 @@
-// C++ host side of the MLA decode attention over the paged latent KV cache (csrc/attention_decode_mla.hip):
-// attention_decode_mla_bf16.  Ours only (no reference op; pinned to the PyTorch statement tests/mla_ref.py), so under its own
-// namespace: torch.ops.hpc_mla.* (hpc:: holds the reference's surface).  With `output` (and `output_lse` where an lse is wanted)
-// given nothing is allocated per call beyond the cached scratch and the call captures into a hipGraph.  Nothing here reads the
-// values of num_seq_kvcache.  Below it rope_norm_store_kv, the op that writes that cache and the RoPE columns of q
-// (csrc/mla_store.hip).  Each has its twin over the FP8 latent cache (csrc/mla_fp8_format.h: a uint8 tensor of 656-byte rows,
-// strides in bytes): attention_decode_mla_fp8 and rope_norm_store_kv_fp8 - one body each, the cache's kind (csrc/mla_cache.h:
-// row width, stride unit and the one host rule for a valid cache, which check_cache prints) and dtype being the only
-// difference.  Behind them the prompt side: attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip,
-// the non-absorbed 192 / 128 form with an lse output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the
-// kv_b projection of a context pass, gather_ckv / gather_ckv_fp8 (csrc/mla_gather.hip).  attention_decode_mla_sparse_{bf16,fp8} are the decode
-// attention over a list of token positions per q row (the same kernel source, its kSparse form, and here the same body as the
-// dense ops: decode_mla<kFp8>, the list null or given), and attention_prefill_mla_sparse_{bf16,fp8} that kernel over a ragged
-// prefill chunk (the writers' row rule instead of mtp).  Either side of the decode
-// attention the two absorb matmuls, absorb_q and unabsorb_o (csrc/mla_absorb.hip).  No kernels here.
+// C++ host side of the MLA ops over the paged latent KV cache, under their own namespace torch.ops.hpc_mla.* (hpc:: holds the
+// reference's surface).  Ours only (no reference op; pinned to PyTorch statements under tests/).  Where each rule lives:
+//   the cache      check_cache prints csrc/mla_cache.h's one host rule for a valid cache (row width, stride unit, alignment).  Every
+//                  op over a cache is a template on kFp8, registered once per kind (bf16 elements; FP8: csrc/mla_fp8_format.h's
+//                  656-byte rows in a uint8 tensor, strides in bytes): the kind and its dtype are the only difference.
+//   the attention  decode_mla<kFp8> is the one body of attention_decode_mla_{bf16,fp8} (csrc/attention_decode_mla.hip, pinned to
+//                  tests/mla_ref.py), of attention_decode_mla_sparse_{bf16,fp8} (the kernel's kSparse form: a list of token
+//                  positions per q row, `indices` null or given) and of attention_prefill_mla_sparse_{bf16,fp8} (that form over
+//                  a ragged prefill chunk: MlaRowsOf says whether the rows are a decode step's or a chunk's, the writers' row
+//                  rule instead of mtp).  The registered functions only build the rows from their schema's arguments.  Route,
+//                  split count and scratch size are the plan entries'; nothing here reads the values of a length or a list.
+//   the writer     rope_norm_store_kv{,_fp8} (csrc/mla_store.hip), which writes that cache and the RoPE columns of q.
+//   the prompt     attention_prefill_mla_bf16 (csrc/attention_prefill_mla.hip, the non-absorbed 192 / 128 form with an lse
+//                  output), merge_attn_states (csrc/merge_attn_states.hip) and, between the cache and the kv_b projection of a
+//                  context pass, gather_ckv{,_fp8} (csrc/mla_gather.hip).
+//   the absorbs    absorb_q and unabsorb_o (csrc/mla_absorb.hip) either side of the decode attention: their route's refusal in
+//                  words and the launch take one argument list (checked_launch, torch_common.h).
+// With `output` (and `output_lse` where an lse is wanted) given nothing is allocated per call beyond the cached scratch and the
+// calls capture into a hipGraph.  No kernels here.
 #include <limits>
 
 #include "byte_span.h"
@@ -89,52 +93,62 @@ void check_table(const at::Tensor& t, const char* name, const at::Tensor& like, 
               t.sizes());
 }
 
-// ---- attention_decode_mla_{bf16,fp8} and attention_decode_mla_sparse_{bf16,fp8}: one body, `indices` null for the dense ops -----
-// sparse: each q row attends to the tokens its list names (tests/mla_sparse_ref.py); the list's checks stand beside the dense
-// ones.  Nothing here reads the values of num_seq_kvcache, block_ids or indices.  With `output` (and `output_lse` where an lse
-// is wanted) given nothing is allocated per call beyond the cached scratch.
+// ---- attention_decode_mla_{bf16,fp8}, attention_decode_mla_sparse_{bf16,fp8} and attention_prefill_mla_sparse_{bf16,fp8}: one
+// body.  `indices` null for the dense ops; sparse: each q row attends to the tokens its list names (tests/mla_sparse_ref.py), the
+// list's checks stand beside the dense ones.  The rows are a decode step's (num_seq_kvcache, mtp, new_kv_included) or, the
+// prefill ops, a ragged chunk's (num_seqlen_per_req, q_index: the writers' row rule as the source of a row's request and of what
+// it sees, tests/mla_indexer_prefill_ref.py), routed as num_rows requests of one q row.  Nothing here reads the values of the
+// lengths, q_index, block_ids or indices.  With `output` (and `output_lse` where an lse is wanted) given nothing is allocated per
+// call beyond the cached scratch.
+struct MlaRowsOf {
+  const at::Tensor& lens;     // num_seq_kvcache, or a chunk's num_seqlen_per_req
+  const at::Tensor* q_index;  // a chunk's; null: a decode step
+  int64_t mtp;
+  bool new_kv_included;
+};
 template <bool kFp8>
 std::tuple<at::Tensor, at::Tensor> decode_mla(const at::Tensor& q, const at::Tensor& ckv_cache, const at::Tensor& block_ids,
-                                              const at::Tensor& num_seq_kvcache, const at::Tensor* indices, double softmax_scale,
-                                              int64_t mtp, bool new_kv_included, const c10::optional<at::Tensor>& output,
-                                              const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
-  const bool sparse = indices != nullptr;
-  const char* op = sparse ? (kFp8 ? "attention_decode_mla_sparse_fp8" : "attention_decode_mla_sparse_bf16")
-                          : (kFp8 ? "attention_decode_mla_fp8" : "attention_decode_mla_bf16");
+                                              const MlaRowsOf& rows, const at::Tensor* indices, double softmax_scale,
+                                              const c10::optional<at::Tensor>& output, const c10::optional<at::Tensor>& output_lse,
+                                              bool return_lse, int64_t splits) {
+  const bool sparse = indices != nullptr, ragged = rows.q_index != nullptr;
+  const char* op = ragged   ? (kFp8 ? "attention_prefill_mla_sparse_fp8" : "attention_prefill_mla_sparse_bf16")
+                   : sparse ? (kFp8 ? "attention_decode_mla_sparse_fp8" : "attention_decode_mla_sparse_bf16")
+                            : (kFp8 ? "attention_decode_mla_fp8" : "attention_decode_mla_bf16");
+  const char* rows_word = ragged ? "rows" : "num_batch * (mtp + 1)";
   cuda_contig(q, "q");
-  cuda_contig(block_ids, "block_ids");
-  cuda_contig(num_seq_kvcache, "num_seq_kvcache");
-  TORCH_CHECK(ckv_cache.is_cuda(), "ckv_cache tensor must be cuda");
-  TORCH_CHECK(ckv_cache.device() == q.device() && block_ids.device() == q.device() && num_seq_kvcache.device() == q.device(),
-              "ckv_cache, block_ids and num_seq_kvcache must be on q's device");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
-  TORCH_CHECK(block_ids.scalar_type() == at::kInt, "block_ids dtype must be int32");
-  TORCH_CHECK(num_seq_kvcache.scalar_type() == at::kInt, "num_seq_kvcache dtype must be int32");
-  TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
-  const int64_t sq = mtp + 1;
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [num_batch * num_seq_q, num_head, 576]");
-  TORCH_CHECK(block_ids.dim() == 2, "block_ids must be [num_batch, max_blocks]");
-  TORCH_CHECK(num_seq_kvcache.dim() == 1, "num_seq_kvcache must be [num_batch]");
-  const int64_t b = num_seq_kvcache.size(0), h = q.size(1);
-  TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
-  TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [", rows_word, ", num_head, 576]");
+  const int64_t t = q.size(0), h = q.size(1);
+  TORCH_CHECK(ckv_cache.is_cuda() && ckv_cache.device() == q.device(), "ckv_cache must be a cuda tensor on q's device");
+  check_table(rows.lens, ragged ? "num_seqlen_per_req" : "num_seq_kvcache", q, at::kInt, {-1});
+  const int64_t units = rows.lens.size(0);  // requests: the rows of block_ids
+  if (ragged) {
+    check_table(*rows.q_index, "q_index", q, at::kInt, {units + 1});
+  } else {
+    TORCH_CHECK(rows.mtp >= 0 && rows.mtp <= 3, "mtp must be 0 .. 3, got ", rows.mtp);
+    TORCH_CHECK(t == units * (rows.mtp + 1), "q must have num_batch * (mtp + 1) = ", units * (rows.mtp + 1), " rows, got ", t);
+  }
+  check_table(block_ids, "block_ids", q, at::kInt, {units, -1});
   TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
   int64_t topk = 0;
   if (sparse) {
-    check_table(*indices, "indices", q, at::kInt, {b * sq, -1});
+    check_table(*indices, "indices", q, at::kInt, {t, -1});
     topk = indices->size(1);
-    TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [num_batch * (mtp + 1), topk] with 1 <= topk <= 65536, got topk = ", topk);
+    TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [", rows_word, ", topk] with 1 <= topk <= 65536, got topk = ", topk);
   }
   check_cache(ckv_cache, kCache<kFp8>);
   const int64_t page = ckv_cache.size(1);
   TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
-  TORCH_CHECK(!sparse || ckv_cache.size(0) <= INT32_MAX, "sizes beyond int32");
+  TORCH_CHECK((!sparse || ckv_cache.size(0) <= INT32_MAX) && (!ragged || (t <= INT32_MAX && units < INT32_MAX)), "sizes beyond int32");
   TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
-  at::Tensor out = out_or_new(output, q, {b * sq, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
+  at::Tensor out = out_or_new(output, q, {t, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
   const bool want_lse = return_lse || output_lse.has_value();
-  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {b * sq, h}, at::kFloat, "output_lse", kOnInputDevice)
+  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {t, h}, at::kFloat, "output_lse", kOnInputDevice)
                             : at::empty({0}, q.options().dtype(at::kFloat));
 
+  // the route's units: the requests of a step, the rows of a chunk
+  const int64_t b = ragged ? t : units, sq = ragged ? 1 : rows.mtp + 1;
   int s = 0, max_splits = 0;
   int64_t ws_bytes = 0;
   const int wanted = i32(std::min<int64_t>(splits, INT32_MAX)), cus = b > 0 ? hpc_get_cu_count(q.device().index()) : 256;
@@ -146,24 +160,31 @@ std::tuple<at::Tensor, at::Tensor> decode_mla(const at::Tensor& q, const at::Ten
               " may be cut into");
   HPC_LAUNCH_CHECK(rc_plan, op);
   if (b == 0) return {out, lse};
+  if (ragged && units == 0) {  // every row is a row of no request: the empty row
+    out.zero_();
+    if (want_lse) lse.fill_(-std::numeric_limits<float>::infinity());
+    return {out, lse};
+  }
   TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
   at::Tensor ws;
   if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: an unwritten piece is never read
+  const auto ip = [](const at::Tensor& x) { return static_cast<const int*>(x.data_ptr()); };
   float* lse_ptr = want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr;
-  const int* bid_ptr = static_cast<const int*>(block_ids.data_ptr());
-  const int* len_ptr = static_cast<const int*>(num_seq_kvcache.data_ptr());
   void* ws_ptr = s > 1 ? ws.data_ptr() : nullptr;
   const float scale = static_cast<float>(softmax_scale);
+  const int nki = rows.new_kv_included ? 1 : 0, cols = i32(block_ids.size(1)), num_blocks = i32(ckv_cache.size(0));
+  const int64_t bs = ckv_cache.stride(0), ts = ckv_cache.stride(1);
   // sparse: the launcher is given the effective count - cutting the list into that many pieces gives the same piece length again
   const int rc =
-      sparse ? (kFp8 ? hpc_attention_decode_mla_sparse_fp8_async : hpc_attention_decode_mla_sparse_bf16_async)(
-                   ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), bid_ptr, len_ptr, static_cast<const int*>(indices->data_ptr()), i32(b),
-                   i32(sq), i32(h), i32(topk), i32(page), i32(block_ids.size(1)), i32(ckv_cache.size(0)), ckv_cache.stride(0),
-                   ckv_cache.stride(1), scale, new_kv_included ? 1 : 0, s, ws_ptr, ws_bytes, stream_of(q))
-             : (kFp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
-                   ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), bid_ptr, len_ptr, i32(b), i32(sq), i32(h), i32(page),
-                   i32(block_ids.size(1)), ckv_cache.stride(0), ckv_cache.stride(1), scale, new_kv_included ? 1 : 0, s, ws_ptr,
-                   ws_bytes, stream_of(q));
+      ragged   ? (kFp8 ? hpc_attention_prefill_mla_sparse_fp8_async : hpc_attention_prefill_mla_sparse_bf16_async)(
+                     ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), ip(block_ids), ip(rows.lens), ip(*rows.q_index), ip(*indices), i32(t),
+                     i32(units), i32(h), i32(topk), i32(page), cols, num_blocks, bs, ts, scale, s, ws_ptr, ws_bytes, stream_of(q))
+      : sparse ? (kFp8 ? hpc_attention_decode_mla_sparse_fp8_async : hpc_attention_decode_mla_sparse_bf16_async)(
+                     ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), ip(block_ids), ip(rows.lens), ip(*indices), i32(b), i32(sq), i32(h),
+                     i32(topk), i32(page), cols, num_blocks, bs, ts, scale, nki, s, ws_ptr, ws_bytes, stream_of(q))
+               : (kFp8 ? hpc_attention_decode_mla_fp8_async : hpc_attention_decode_mla_bf16_async)(
+                     ptr(out), lse_ptr, ptr(q), ptr(ckv_cache), ip(block_ids), ip(rows.lens), i32(b), i32(sq), i32(h), i32(page), cols,
+                     bs, ts, scale, nki, s, ws_ptr, ws_bytes, stream_of(q));
   HPC_LAUNCH_CHECK(rc, op);
   return {out, lse};
 }
@@ -173,8 +194,8 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla(const at::Tensor& q, con
                                                         const at::Tensor& num_seq_kvcache, double softmax_scale, int64_t mtp,
                                                         bool new_kv_included, const c10::optional<at::Tensor>& output,
                                                         const c10::optional<at::Tensor>& output_lse, bool return_lse, int64_t splits) {
-  return decode_mla<kFp8>(q, ckv_cache, block_ids, num_seq_kvcache, nullptr, softmax_scale, mtp, new_kv_included, output, output_lse,
-                          return_lse, splits);
+  return decode_mla<kFp8>(q, ckv_cache, block_ids, {num_seq_kvcache, nullptr, mtp, new_kv_included}, nullptr, softmax_scale, output,
+                          output_lse, return_lse, splits);
 }
 
 template <bool kFp8>
@@ -184,14 +205,11 @@ std::tuple<at::Tensor, at::Tensor> attention_decode_mla_sparse(const at::Tensor&
                                                                bool new_kv_included, const c10::optional<at::Tensor>& output,
                                                                const c10::optional<at::Tensor>& output_lse, bool return_lse,
                                                                int64_t splits) {
-  return decode_mla<kFp8>(q, ckv_cache, block_ids, num_seq_kvcache, &indices, softmax_scale, mtp, new_kv_included, output,
+  return decode_mla<kFp8>(q, ckv_cache, block_ids, {num_seq_kvcache, nullptr, mtp, new_kv_included}, &indices, softmax_scale, output,
                           output_lse, return_lse, splits);
 }
 
-// ---- attention_prefill_mla_sparse_{bf16,fp8}: the token-sparse attention over a ragged prefill chunk ---------------------------
-// The decode op's kernel, route and scratch with the writers' row rule (num_seqlen_per_req, q_index) as the source of a row's
-// request and of what it sees (tests/mla_indexer_prefill_ref.py: the sparse statement on the expanded form).  Nothing here reads
-// the values of num_seqlen_per_req, q_index, block_ids or indices.
+// the token-sparse attention over a ragged prefill chunk: the decode op's body, kernel, route and scratch with a chunk's rows
 template <bool kFp8>
 std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_sparse(const at::Tensor& q, const at::Tensor& ckv_cache,
                                                                 const at::Tensor& block_ids, const at::Tensor& num_seqlen_per_req,
@@ -199,53 +217,8 @@ std::tuple<at::Tensor, at::Tensor> attention_prefill_mla_sparse(const at::Tensor
                                                                 double softmax_scale, const c10::optional<at::Tensor>& output,
                                                                 const c10::optional<at::Tensor>& output_lse, bool return_lse,
                                                                 int64_t splits) {
-  const char* op = kFp8 ? "attention_prefill_mla_sparse_fp8" : "attention_prefill_mla_sparse_bf16";
-  cuda_contig(q, "q");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q dtype must be bfloat16");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kMlaRow, "q must be [rows, num_head, 576]");
-  const int64_t t = q.size(0), h = q.size(1);
-  TORCH_CHECK(ckv_cache.is_cuda() && ckv_cache.device() == q.device(), "ckv_cache must be a cuda tensor on q's device");
-  check_table(num_seqlen_per_req, "num_seqlen_per_req", q, at::kInt, {-1});
-  const int64_t req = num_seqlen_per_req.size(0);
-  check_table(q_index, "q_index", q, at::kInt, {req + 1});
-  check_table(block_ids, "block_ids", q, at::kInt, {req, -1});
-  TORCH_CHECK(h % 16 == 0 && h >= 16 && h <= 128, "num_head must be a multiple of 16, 16 .. 128, got ", h);
-  check_table(indices, "indices", q, at::kInt, {t, -1});
-  const int64_t topk = indices.size(1);
-  TORCH_CHECK(topk >= 1 && topk <= 65536, "indices must be [rows, topk] with 1 <= topk <= 65536, got topk = ", topk);
-  check_cache(ckv_cache, kCache<kFp8>);
-  const int64_t page = ckv_cache.size(1);
-  TORCH_CHECK(block_ids.size(1) * page <= (int64_t{1} << 30), "block_ids reaches beyond 2^30 tokens");
-  TORCH_CHECK(ckv_cache.size(0) <= INT32_MAX && t <= INT32_MAX && req < INT32_MAX, "sizes beyond int32");
-  TORCH_CHECK(splits >= 0, "splits must be 0 (the library chooses) or a count, got ", splits);
-  at::Tensor out = out_or_new(output, q, {t, h, hpc::kMlaLatent}, at::kBFloat16, "output", kOnInputDevice);
-  const bool want_lse = return_lse || output_lse.has_value();
-  at::Tensor lse = want_lse ? out_or_new(output_lse, q, {t, h}, at::kFloat, "output_lse", kOnInputDevice)
-                            : at::empty({0}, q.options().dtype(at::kFloat));
-  int s = 0, max_splits = 0;
-  int64_t ws_bytes = 0;
-  const int wanted = i32(std::min<int64_t>(splits, INT32_MAX)), cus = t > 0 ? hpc_get_cu_count(q.device().index()) : 256;
-  const int rc_plan =
-      hpc_attention_decode_mla_sparse_plan(i32(t), 1, i32(h), i32(topk), wanted, cus, &s, &max_splits, &ws_bytes, nullptr, nullptr);
-  TORCH_CHECK(splits <= max_splits, "splits = ", splits, " is beyond the ", max_splits, " pieces a list may be cut into");
-  HPC_LAUNCH_CHECK(rc_plan, op);
-  if (t == 0) return {out, lse};
-  if (req == 0) {  // every row is a row of no request: the empty row
-    out.zero_();
-    if (want_lse) lse.fill_(-std::numeric_limits<float>::infinity());
-    return {out, lse};
-  }
-  TORCH_CHECK(block_ids.size(1) > 0, "block_ids has no columns");
-  at::Tensor ws;
-  if (s > 1) ws = cached_scratch(kScratchMla, q, ws_bytes, 0);  // never zeroed: every launched piece writes all of its rows
-  const auto ip = [](const at::Tensor& x) { return static_cast<const int*>(x.data_ptr()); };
-  const int rc = (kFp8 ? hpc_attention_prefill_mla_sparse_fp8_async : hpc_attention_prefill_mla_sparse_bf16_async)(
-      ptr(out), want_lse ? static_cast<float*>(lse.data_ptr()) : nullptr, ptr(q), ptr(ckv_cache), ip(block_ids), ip(num_seqlen_per_req),
-      ip(q_index), ip(indices), i32(t), i32(req), i32(h), i32(topk), i32(page), i32(block_ids.size(1)), i32(ckv_cache.size(0)),
-      ckv_cache.stride(0), ckv_cache.stride(1), static_cast<float>(softmax_scale), s, s > 1 ? ws.data_ptr() : nullptr, ws_bytes,
-      stream_of(q));
-  HPC_LAUNCH_CHECK(rc, op);
-  return {out, lse};
+  return decode_mla<kFp8>(q, ckv_cache, block_ids, {num_seqlen_per_req, &q_index, 0, true}, &indices, softmax_scale, output, output_lse,
+                          return_lse, splits);
 }
 
 // ---- rope_norm_store_kv: the writer of that cache (csrc/mla_store.hip), pinned to tests/mla_store_ref.py --------------------
@@ -454,13 +427,10 @@ at::Tensor absorb_q(const at::Tensor& q_nope, const at::Tensor& w_uk, const c10:
   } else {
     out = at::empty({t, h, hpc::kMlaLatent}, q_nope.options());
   }
-  const char* why = hpc_mla_absorb_q_refusal(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1),
-                                             w_uk.stride(0), w_uk.stride(1), out.stride(0), out.stride(1));
-  TORCH_CHECK(why == nullptr, "mla_absorb_q: ", why);
-  if (t == 0) return out;  // nothing to launch
-  const int rc = hpc_mla_absorb_q_async(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1),
-                                        w_uk.stride(0), w_uk.stride(1), out.stride(0), out.stride(1), stream_of(q_nope));
-  HPC_LAUNCH_CHECK(rc, "mla_absorb_q");
+  checked_launch("mla_absorb_q", hpc_mla_absorb_q_refusal, hpc_mla_absorb_q_async, t > 0,
+                 std::make_tuple(ptr(out), ptr(q_nope), ptr(w_uk), t, i32(h), q_nope.stride(0), q_nope.stride(1), w_uk.stride(0),
+                                 w_uk.stride(1), out.stride(0), out.stride(1)),
+                 std::make_tuple(stream_of(q_nope)));
   return out;
 }
 
@@ -493,13 +463,10 @@ std::tuple<at::Tensor, at::Tensor> unabsorb_o(const at::Tensor& o_lat, const at:
   // a [1, N] or [0, N] tensor carries any row stride: the route is told the contiguous one
   const int64_t out_rs = t > 1 ? out.stride(0) : h * kNope;
   float* sp = quant ? static_cast<float*>(scale.data_ptr()) : nullptr;
-  const char* why = hpc_mla_unabsorb_o_refusal(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1),
-                                               w_uv.stride(0), w_uv.stride(1), out_rs, quant ? 1 : 0);
-  TORCH_CHECK(why == nullptr, "mla_unabsorb_o: ", why);
-  if (t == 0) return {out, scale};  // nothing to launch
-  const int rc = hpc_mla_unabsorb_o_async(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1),
-                                          w_uv.stride(0), w_uv.stride(1), out_rs, quant ? 1 : 0, stream_of(o_lat));
-  HPC_LAUNCH_CHECK(rc, "mla_unabsorb_o");
+  checked_launch("mla_unabsorb_o", hpc_mla_unabsorb_o_refusal, hpc_mla_unabsorb_o_async, t > 0,
+                 std::make_tuple(ptr(out), sp, ptr(o_lat), ptr(w_uv), t, i32(h), o_lat.stride(0), o_lat.stride(1), w_uv.stride(0),
+                                 w_uv.stride(1), out_rs, quant ? 1 : 0),
+                 std::make_tuple(stream_of(o_lat)));
   return {out, scale};
 }
 

@@ -1,12 +1,16 @@
-// C++ host side of the DSA lightning indexer (csrc/mla_indexer.hip): mla_indexer_store_k_fp8, mla_indexer_logits_fp8,
-// mla_indexer_topk and the fused mla_indexer_topk_fp8, and of its front end mla_indexer_prep_fp8 (csrc/mla_indexer_prep.hip), under torch.ops.hpc_mla.* beside the MLA ops they serve.  Ours only;
-// pinned to the PyTorch statements tests/mla_indexer_ref.py and tests/mla_indexer_prep_ref.py.  dtype, device and shape are
-// checked here; the cache's rule, the
-// limits, strides and alignment are the launchers' (csrc/mla_indexer_route.h) and come back in their words through
-// hpc_mla_indexer_*_refusal.  Nothing here reads the values of a length, a page table or a logit; with `output` given nothing is
-// allocated per call beyond the cached scratch of the fused op and the calls capture into a hipGraph.  Behind them the same three
-// over a ragged prefill chunk (csrc/mla_indexer_prefill.hip): mla_indexer_logits_prefill_fp8, mla_indexer_topk_prefill and the
-// fused mla_indexer_topk_prefill_fp8 over row slabs.  No kernels here.
+// C++ host side of the DSA lightning indexer, under torch.ops.hpc_mla.* beside the MLA ops it serves.  Ours only; pinned to the
+// PyTorch statements tests/mla_indexer_ref.py, tests/mla_indexer_prefill_ref.py and tests/mla_indexer_prep_ref.py.
+//   the writer     mla_indexer_store_k_fp8 (csrc/mla_indexer.hip) and the front end mla_indexer_prep_fp8 (csrc/mla_indexer_prep.hip);
+//   the readers    logits, top-k and the fused top-k, each ONE body (logits_body, topk_body, fused_body) for a decode step
+//                  (mla_indexer_logits_fp8, mla_indexer_topk, mla_indexer_topk_fp8; csrc/mla_indexer.hip) and for a ragged prefill
+//                  chunk (mla_indexer_logits_prefill_fp8, mla_indexer_topk_prefill, mla_indexer_topk_prefill_fp8 over row slabs;
+//                  csrc/mla_indexer_prefill.hip).  Where the rows of a call come from - its tensor checks, message words and C
+//                  arguments - is `Rows`; the eight registered functions only build one from their schema's arguments.
+// dtype, device and shape are checked here; the cache's rule, the limits, strides and alignment are the launchers'
+// (csrc/mla_indexer_route.h) and come back in their words through hpc_mla_indexer_*_refusal: checked_launch (torch_common.h)
+// hands one argument list to the refusal and to the launcher.  Nothing here reads the values of a length, a page table or a
+// logit; with `output` given nothing is allocated per call beyond the cached scratch of the fused ops and the calls capture into
+// a hipGraph.  No kernels here.
 #include "mla_indexer_route.h"
 #include "torch_common.h"
 
@@ -35,28 +39,64 @@ int64_t check_cache(const at::Tensor& c, const at::Tensor& like) {
 // a [0, N] or [1, N] tensor carries any block stride: the launcher is told the contiguous one
 int64_t block_stride(const at::Tensor& c) { return c.size(0) > 1 ? c.stride(0) : c.size(1); }
 
-struct Dims {
-  int64_t b, sq, h, page, max_blocks;
+const int* ip(const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); }
+const float* fp(const at::Tensor& t) { return static_cast<const float*>(t.data_ptr()); }
+const void* cp(const at::Tensor& t) { return t.data_ptr(); }
+
+// The rows of a reader's call as the shim sees them (the launchers' MlaRows, csrc/mla_indexer_route.h): a decode step
+// (num_seq_kvcache, mtp, new_kv_included) or a ragged prefill chunk (num_seqlen_per_req, q_index, row_begin), with the tensor
+// checks, the message words and the C arguments of its form
+struct Rows {
+  const at::Tensor& lens;
+  const at::Tensor* q_index;  // null: a decode step
+  int64_t mtp, row_begin;
+  bool new_kv_included;
+
+  bool ragged() const { return q_index != nullptr; }
+  int64_t units() const { return lens.size(0); }  // requests: the rows of block_ids
+  const char* rows_word() const { return ragged() ? "rows" : "num_batch * (mtp + 1)"; }
+  const char* units_word() const { return ragged() ? "num_req" : "num_batch"; }
+  bool work(int64_t rows) const { return units() > 0 && (!ragged() || rows > 0); }
+  // the tables, on `like`'s device, and the `rows` that `what` (q or logits) has
+  void check(const at::Tensor& like, const char* what, int64_t rows) const {
+    if (ragged()) {
+      check_table(lens, "num_seqlen_per_req", like, 1);
+      check_table(*q_index, "q_index", like, 1);
+      TORCH_CHECK(q_index->size(0) == units() + 1, "q_index must be [num_req + 1] = [", units() + 1, "]");
+      TORCH_CHECK(row_begin >= 0 && row_begin <= INT32_MAX, "row_begin must be a row of the chunk, got ", row_begin);
+      TORCH_CHECK(rows <= INT32_MAX && units() < INT32_MAX, "sizes beyond int32");
+    } else {
+      TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
+      check_table(lens, "num_seq_kvcache", like, 1);
+      TORCH_CHECK(rows == units() * (mtp + 1), what, " must have num_batch * (mtp + 1) = ", units() * (mtp + 1), " rows, got ", rows);
+      TORCH_CHECK(units() <= INT32_MAX, "sizes beyond int32");
+    }
+  }
+  // where the C entries of the two forms take their rows from (a chunk's row_begin follows where an entry has one)
+  auto step_args() const { return std::make_tuple(ip(lens), i32(units()), i32(mtp + 1)); }
+  auto chunk_args(int64_t rows) const { return std::make_tuple(ip(lens), ip(*q_index), i32(rows), i32(units())); }
 };
-// q, weights, k_cache, block_ids and num_seq_kvcache of the two ops that read the cache
+
+struct Dims {
+  int64_t rows, h, page, max_blocks;
+};
+// q, weights, k_cache, block_ids and the rows of the ops that read the cache
 Dims check_reader(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                  const at::Tensor& num_seq_kvcache, int64_t mtp) {
+                  const Rows& rows) {
   TORCH_CHECK(q.is_cuda(), "q tensor must be cuda");
   TORCH_CHECK(q.scalar_type() == kF8, "q dtype must be float8_e4m3fn");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kIdxDim && q.is_contiguous(), "q must be a contiguous [num_batch * (mtp + 1), num_head, 128]");
-  TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
-  const int64_t sq = mtp + 1, h = q.size(1);
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kIdxDim && q.is_contiguous(), "q must be a contiguous [", rows.rows_word(),
+              ", num_head, 128]");
+  const int64_t n = q.size(0), h = q.size(1);
   check_on(weights, "weights", q, at::kFloat, "float32");
-  TORCH_CHECK(weights.dim() == 2 && weights.size(0) == q.size(0) && weights.size(1) == h && weights.is_contiguous(),
-              "weights must be a contiguous [num_batch * (mtp + 1), num_head] = [", q.size(0), ", ", h, "]");
+  TORCH_CHECK(weights.dim() == 2 && weights.size(0) == n && weights.size(1) == h && weights.is_contiguous(),
+              "weights must be a contiguous [", rows.rows_word(), ", num_head] = [", n, ", ", h, "]");
+  rows.check(q, "q", n);
   check_table(block_ids, "block_ids", q, 2);
-  check_table(num_seq_kvcache, "num_seq_kvcache", q, 1);
-  const int64_t b = num_seq_kvcache.size(0);
-  TORCH_CHECK(q.size(0) == b * sq, "q must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", q.size(0));
-  TORCH_CHECK(block_ids.size(0) == b, "block_ids must have num_batch = ", b, " rows");
+  TORCH_CHECK(block_ids.size(0) == rows.units(), "block_ids must have ", rows.units_word(), " = ", rows.units(), " rows");
   const int64_t page = check_cache(k_cache, q);
-  TORCH_CHECK(b <= INT32_MAX && h <= INT32_MAX && block_ids.size(1) <= INT32_MAX, "sizes beyond int32");
-  return {b, sq, h, page, block_ids.size(1)};
+  TORCH_CHECK(h <= INT32_MAX && block_ids.size(1) <= INT32_MAX, "sizes beyond int32");
+  return {n, h, page, block_ids.size(1)};
 }
 
 // ---- mla_indexer_store_k_fp8 ------------------------------------------------------------------------------------------------------
@@ -75,194 +115,129 @@ void store_k_fp8(const at::Tensor& k_cache, const at::Tensor& k, const at::Tenso
   const int64_t page = check_cache(k_cache, k);
   TORCH_CHECK(rows <= INT32_MAX && num_req < INT32_MAX && block_ids.size(1) <= INT32_MAX, "sizes beyond int32");
   const int64_t k_rs = rows > 1 ? k.stride(0) : hpc::kIdxDim;
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_store_k_fp8_refusal(ptr(k_cache), ptr(k), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
-                                                        i32(rows), i32(num_req), i32(page), i32(block_ids.size(1)),
-                                                        i32(k_cache.size(0)), block_stride(k_cache), k_rs);
-  TORCH_CHECK(why == nullptr, "mla_indexer_store_k_fp8: ", why);
-  if (rows == 0 || num_req == 0) return;  // nothing to launch
-  const int rc = hpc_mla_indexer_store_k_fp8_async(ptr(k_cache), ptr(k), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
-                                                   i32(rows), i32(num_req), i32(page), i32(block_ids.size(1)),
-                                                   i32(k_cache.size(0)), block_stride(k_cache), k_rs, stream_of(k));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_store_k_fp8");
+  checked_launch("mla_indexer_store_k_fp8", hpc_mla_indexer_store_k_fp8_refusal, hpc_mla_indexer_store_k_fp8_async,
+                 rows > 0 && num_req > 0,
+                 std::make_tuple(ptr(k_cache), cp(k), ip(num_seqlen_per_req), ip(q_index), ip(block_ids), i32(rows), i32(num_req),
+                                 i32(page), i32(block_ids.size(1)), i32(k_cache.size(0)), block_stride(k_cache), k_rs),
+                 std::make_tuple(stream_of(k)));
 }
 
-// ---- mla_indexer_logits_fp8 -------------------------------------------------------------------------------------------------------
-at::Tensor logits_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                      const at::Tensor& num_seq_kvcache, int64_t mtp, bool new_kv_included, const c10::optional<at::Tensor>& output) {
-  const Dims d = check_reader(q, weights, k_cache, block_ids, num_seq_kvcache, mtp);
-  const int64_t cols = d.max_blocks * d.page;
-  at::Tensor out = out_or_new(output, q, {d.b * d.sq, cols}, at::kFloat, "output", kOnInputDevice);
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_logits_fp8_refusal(static_cast<const float*>(out.data_ptr()), ptr(q),
-                                                       static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-                                                       ip(num_seq_kvcache), i32(d.b), i32(d.sq), i32(d.h), i32(d.page),
-                                                       i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), cols);
-  TORCH_CHECK(why == nullptr, "mla_indexer_logits_fp8: ", why);
-  if (d.b == 0) return out;  // nothing to launch
-  const int rc = hpc_mla_indexer_logits_fp8_async(static_cast<float*>(out.data_ptr()), ptr(q),
-                                                  static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-                                                  ip(num_seq_kvcache), i32(d.b), i32(d.sq), i32(d.h), i32(d.page), i32(d.max_blocks),
-                                                  i32(k_cache.size(0)), block_stride(k_cache), cols, new_kv_included ? 1 : 0,
-                                                  stream_of(q));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_logits_fp8");
-  return out;
-}
-
-// ---- mla_indexer_topk -------------------------------------------------------------------------------------------------------------
-at::Tensor select_topk(const at::Tensor& logits, const at::Tensor& num_seq_kvcache, int64_t topk, int64_t mtp, bool new_kv_included,
-                const c10::optional<at::Tensor>& output) {
-  TORCH_CHECK(logits.is_cuda(), "logits tensor must be cuda");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32");
-  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1), "logits must be [num_batch * (mtp + 1), columns] with a contiguous last dim");
-  TORCH_CHECK(mtp >= 0 && mtp <= 3, "mtp must be 0 .. 3, got ", mtp);
-  const int64_t sq = mtp + 1;
-  check_table(num_seq_kvcache, "num_seq_kvcache", logits, 1);
-  const int64_t b = num_seq_kvcache.size(0), cols = logits.size(1);
-  TORCH_CHECK(logits.size(0) == b * sq, "logits must have num_batch * (mtp + 1) = ", b * sq, " rows, got ", logits.size(0));
-  TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
-  TORCH_CHECK(b <= INT32_MAX, "sizes beyond int32");
-  at::Tensor out = out_or_new(output, logits, {b * sq, topk}, at::kInt, "output", kOnInputDevice);
-  const int64_t rs = logits.size(0) > 1 ? logits.stride(0) : cols;
-  const char* why = hpc_mla_indexer_topk_refusal(static_cast<const int*>(out.data_ptr()), static_cast<const float*>(logits.data_ptr()),
-                                                 static_cast<const int*>(num_seq_kvcache.data_ptr()), i32(b), i32(sq), cols,
-                                                 i32(topk), rs);
-  TORCH_CHECK(why == nullptr, "mla_indexer_topk: ", why);
-  if (b == 0) return out;  // nothing to launch
-  const int rc = hpc_mla_indexer_topk_async(static_cast<int*>(out.data_ptr()), static_cast<const float*>(logits.data_ptr()),
-                                            static_cast<const int*>(num_seq_kvcache.data_ptr()), i32(b), i32(sq), cols, i32(topk),
-                                            rs, new_kv_included ? 1 : 0, stream_of(logits));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk");
-  return out;
-}
-
-// ---- mla_indexer_topk_fp8: the two back to back through the cached scratch, whose layout is mla_indexer_scratch()'s ---------------
-at::Tensor topk_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                    const at::Tensor& num_seq_kvcache, int64_t topk, int64_t mtp, bool new_kv_included,
-                    const c10::optional<at::Tensor>& output) {
-  const Dims d = check_reader(q, weights, k_cache, block_ids, num_seq_kvcache, mtp);
-  TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
-  at::Tensor out = out_or_new(output, q, {d.b * d.sq, topk}, at::kInt, "output", kOnInputDevice);
-  const hpc::MlaIndexerScratch need = hpc::mla_indexer_scratch(d.b * d.sq, d.max_blocks * d.page);
-  at::Tensor ws;
-  if (d.b > 0) ws = cached_scratch(kScratchMlaIndexer, q, std::max<int64_t>(need.bytes, 16), 0);  // never zeroed
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_topk_fp8_refusal(static_cast<const int*>(out.data_ptr()), ptr(q),
-                                                     static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-                                                     ip(num_seq_kvcache), i32(d.b), i32(d.sq), i32(d.h), i32(d.page),
-                                                     i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), i32(topk),
-                                                     d.b > 0 ? ws.data_ptr() : nullptr, d.b > 0 ? ws.numel() : 0);
-  TORCH_CHECK(why == nullptr, "mla_indexer_topk_fp8: ", why);
-  if (d.b == 0) return out;  // nothing to launch
-  const int rc = hpc_mla_indexer_topk_fp8_async(static_cast<int*>(out.data_ptr()), ptr(q),
-                                                static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-                                                ip(num_seq_kvcache), i32(d.b), i32(d.sq), i32(d.h), i32(d.page), i32(d.max_blocks),
-                                                i32(k_cache.size(0)), block_stride(k_cache), i32(topk), new_kv_included ? 1 : 0,
-                                                ws.data_ptr(), ws.numel(), stream_of(q));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk_fp8");
-  return out;
-}
-
-// ---- the same three over a ragged prefill chunk (csrc/mla_indexer_prefill.hip), pinned to tests/mla_indexer_prefill_ref.py --------
-struct ChunkDims {
-  int64_t rows, req, h, page, max_blocks;
-};
-void check_row_rule(const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, const at::Tensor& like, int64_t row_begin) {
-  check_table(num_seqlen_per_req, "num_seqlen_per_req", like, 1);
-  check_table(q_index, "q_index", like, 1);
-  TORCH_CHECK(q_index.size(0) == num_seqlen_per_req.size(0) + 1, "q_index must be [num_req + 1] = [", num_seqlen_per_req.size(0) + 1, "]");
-  TORCH_CHECK(row_begin >= 0 && row_begin <= INT32_MAX, "row_begin must be a row of the chunk, got ", row_begin);
-}
-ChunkDims check_chunk_reader(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                             const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t row_begin) {
-  TORCH_CHECK(q.is_cuda(), "q tensor must be cuda");
-  TORCH_CHECK(q.scalar_type() == kF8, "q dtype must be float8_e4m3fn");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hpc::kIdxDim && q.is_contiguous(), "q must be a contiguous [rows, num_head, 128]");
-  const int64_t rows = q.size(0), h = q.size(1);
-  check_on(weights, "weights", q, at::kFloat, "float32");
-  TORCH_CHECK(weights.dim() == 2 && weights.size(0) == rows && weights.size(1) == h && weights.is_contiguous(),
-              "weights must be a contiguous [rows, num_head] = [", rows, ", ", h, "]");
-  check_row_rule(num_seqlen_per_req, q_index, q, row_begin);
-  const int64_t req = num_seqlen_per_req.size(0);
-  check_table(block_ids, "block_ids", q, 2);
-  TORCH_CHECK(block_ids.size(0) == req, "block_ids must have num_req = ", req, " rows");
-  const int64_t page = check_cache(k_cache, q);
-  TORCH_CHECK(rows <= INT32_MAX && req < INT32_MAX && h <= INT32_MAX && block_ids.size(1) <= INT32_MAX, "sizes beyond int32");
-  return {rows, req, h, page, block_ids.size(1)};
-}
-
-at::Tensor logits_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                              const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t row_begin,
-                              const c10::optional<at::Tensor>& output) {
-  const ChunkDims d = check_chunk_reader(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, row_begin);
+// ---- the three readers, one body each for a decode step (mla_indexer_logits_fp8, mla_indexer_topk, mla_indexer_topk_fp8;
+// csrc/mla_indexer.hip, pinned to tests/mla_indexer_ref.py) and a ragged prefill chunk (the _prefill ops;
+// csrc/mla_indexer_prefill.hip, pinned to tests/mla_indexer_prefill_ref.py) -----------------------------------------------------------
+at::Tensor logits_body(const char* op, const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache,
+                       const at::Tensor& block_ids, const Rows& rows, const c10::optional<at::Tensor>& output) {
+  const Dims d = check_reader(q, weights, k_cache, block_ids, rows);
   const int64_t cols = d.max_blocks * d.page;
   at::Tensor out = out_or_new(output, q, {d.rows, cols}, at::kFloat, "output", kOnInputDevice);
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_logits_prefill_fp8_refusal(
-      static_cast<const float*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(row_begin), i32(d.h), i32(d.page), i32(d.max_blocks),
-      i32(k_cache.size(0)), block_stride(k_cache), cols);
-  TORCH_CHECK(why == nullptr, "mla_indexer_logits_prefill_fp8: ", why);
-  if (d.rows == 0 || d.req == 0) return out;  // nothing to launch
-  const int rc = hpc_mla_indexer_logits_prefill_fp8_async(
-      static_cast<float*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(row_begin), i32(d.h), i32(d.page), i32(d.max_blocks),
-      i32(k_cache.size(0)), block_stride(k_cache), cols, stream_of(q));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_logits_prefill_fp8");
+  const auto head = std::make_tuple(static_cast<float*>(out.data_ptr()), cp(q), fp(weights), cp(k_cache), ip(block_ids));
+  const auto tail = std::make_tuple(i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), cols);
+  if (rows.ragged())
+    checked_launch(op, hpc_mla_indexer_logits_prefill_fp8_refusal, hpc_mla_indexer_logits_prefill_fp8_async, rows.work(d.rows),
+                   std::tuple_cat(head, rows.chunk_args(d.rows), std::make_tuple(i32(rows.row_begin)), tail),
+                   std::make_tuple(stream_of(q)));
+  else
+    checked_launch(op, hpc_mla_indexer_logits_fp8_refusal, hpc_mla_indexer_logits_fp8_async, rows.work(d.rows),
+                   std::tuple_cat(head, rows.step_args(), tail), std::make_tuple(rows.new_kv_included ? 1 : 0, stream_of(q)));
   return out;
 }
 
-at::Tensor topk_prefill(const at::Tensor& logits, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk,
-                        int64_t row_begin, const c10::optional<at::Tensor>& output) {
+at::Tensor topk_body(const char* op, const at::Tensor& logits, const Rows& rows, int64_t topk, const c10::optional<at::Tensor>& output) {
   TORCH_CHECK(logits.is_cuda(), "logits tensor must be cuda");
   TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits dtype must be float32");
-  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1), "logits must be [rows, columns] with a contiguous last dim");
-  check_row_rule(num_seqlen_per_req, q_index, logits, row_begin);
-  const int64_t rows = logits.size(0), cols = logits.size(1), req = num_seqlen_per_req.size(0);
+  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1), "logits must be [", rows.rows_word(),
+              ", columns] with a contiguous last dim");
+  const int64_t n = logits.size(0), cols = logits.size(1);
+  rows.check(logits, "logits", n);
   TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
-  TORCH_CHECK(rows <= INT32_MAX && req < INT32_MAX, "sizes beyond int32");
-  at::Tensor out = out_or_new(output, logits, {rows, topk}, at::kInt, "output", kOnInputDevice);
-  const int64_t rs = rows > 1 ? logits.stride(0) : cols;
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_topk_prefill_refusal(ip(out), static_cast<const float*>(logits.data_ptr()), ip(num_seqlen_per_req),
-                                                         ip(q_index), i32(rows), i32(req), i32(row_begin), cols, i32(topk), rs);
-  TORCH_CHECK(why == nullptr, "mla_indexer_topk_prefill: ", why);
-  if (rows == 0) return out;  // nothing to launch
-  if (req == 0) return out.fill_(-1);  // every row is a row of no request
-  const int rc = hpc_mla_indexer_topk_prefill_async(static_cast<int*>(out.data_ptr()), static_cast<const float*>(logits.data_ptr()),
-                                                    ip(num_seqlen_per_req), ip(q_index), i32(rows), i32(req), i32(row_begin), cols,
-                                                    i32(topk), rs, stream_of(logits));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk_prefill");
+  at::Tensor out = out_or_new(output, logits, {n, topk}, at::kInt, "output", kOnInputDevice);
+  const auto head = std::make_tuple(static_cast<int*>(out.data_ptr()), fp(logits));
+  const auto tail = std::make_tuple(cols, i32(topk), n > 1 ? logits.stride(0) : cols);
+  if (rows.ragged())
+    checked_launch(op, hpc_mla_indexer_topk_prefill_refusal, hpc_mla_indexer_topk_prefill_async, rows.work(n),
+                   std::tuple_cat(head, rows.chunk_args(n), std::make_tuple(i32(rows.row_begin)), tail),
+                   std::make_tuple(stream_of(logits)));
+  else
+    checked_launch(op, hpc_mla_indexer_topk_refusal, hpc_mla_indexer_topk_async, rows.work(n),
+                   std::tuple_cat(head, rows.step_args(), tail), std::make_tuple(rows.new_kv_included ? 1 : 0, stream_of(logits)));
+  if (rows.ragged() && n > 0 && rows.units() == 0) out.fill_(-1);  // every row is a row of no request
   return out;
 }
 
-// the two over row slabs through the cached scratch, whose layout and slab are mla_indexer_prefill_route()'s
-at::Tensor topk_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
-                            const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk, int64_t scratch_rows,
-                            const c10::optional<at::Tensor>& output) {
-  const ChunkDims d = check_chunk_reader(q, weights, k_cache, block_ids, num_seqlen_per_req, q_index, 0);
+// the two back to back through the cached scratch: a step's in one piece, laid out by mla_indexer_scratch(); a chunk's over row
+// slabs, slab and layout being mla_indexer_prefill_route()'s (scratch_rows is a chunk's alone)
+at::Tensor fused_body(const char* op, const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache,
+                      const at::Tensor& block_ids, const Rows& rows, int64_t topk, int64_t scratch_rows,
+                      const c10::optional<at::Tensor>& output) {
+  const Dims d = check_reader(q, weights, k_cache, block_ids, rows);
   TORCH_CHECK(topk >= 1 && topk <= hpc::kIdxMaxTopk, "topk must be 1 .. 65536, got ", topk);
   TORCH_CHECK(scratch_rows >= 0 && scratch_rows <= INT32_MAX, "scratch_rows must be 0 (the library chooses) or a row count, got ", scratch_rows);
   at::Tensor out = out_or_new(output, q, {d.rows, topk}, at::kInt, "output", kOnInputDevice);
-  const bool work = d.rows > 0 && d.req > 0;
-  const hpc::MlaIndexerPrefillRoute r = hpc::mla_indexer_prefill_route(i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks),
-                                                                       i32(topk), false, i32(scratch_rows), 256);
+  const bool work = rows.work(d.rows);
+  int64_t need = hpc::mla_indexer_scratch(d.rows, d.max_blocks * d.page).bytes;
+  if (rows.ragged()) {
+    const hpc::MlaIndexerPrefillRoute r = hpc::mla_indexer_prefill_route(i32(d.rows), i32(rows.units()), i32(d.h), i32(d.page),
+                                                                         i32(d.max_blocks), i32(topk), false, i32(scratch_rows), 256);
+    need = r.code == HPC_OK ? r.scratch.bytes : -1;  // a refused call gets no scratch; the refusal below says why
+  }
   at::Tensor ws;
-  if (work && r.code == HPC_OK) ws = cached_scratch(kScratchMlaIndexerPrefill, q, std::max<int64_t>(r.scratch.bytes, 16), 0);  // never zeroed
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const char* why = hpc_mla_indexer_topk_prefill_fp8_refusal(
-      ip(out), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids), ip(num_seqlen_per_req), ip(q_index),
-      i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), i32(topk),
-      i32(scratch_rows), ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? ws.numel() : 0);
-  TORCH_CHECK(why == nullptr, "mla_indexer_topk_prefill_fp8: ", why);
-  if (d.rows == 0) return out;  // nothing to launch
-  if (d.req == 0) return out.fill_(-1);  // every row is a row of no request
-  const int rc = hpc_mla_indexer_topk_prefill_fp8_async(
-      static_cast<int*>(out.data_ptr()), ptr(q), static_cast<const float*>(weights.data_ptr()), ptr(k_cache), ip(block_ids),
-      ip(num_seqlen_per_req), ip(q_index), i32(d.rows), i32(d.req), i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)),
-      block_stride(k_cache), i32(topk), i32(scratch_rows), ws.data_ptr(), ws.numel(), stream_of(q));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_topk_prefill_fp8");
+  if (work && need >= 0)
+    ws = cached_scratch(rows.ragged() ? kScratchMlaIndexerPrefill : kScratchMlaIndexer, q, std::max<int64_t>(need, 16), 0);  // never zeroed
+  void* ws_ptr = ws.defined() ? ws.data_ptr() : nullptr;
+  const int64_t ws_bytes = ws.defined() ? ws.numel() : 0;
+  int* op_out = static_cast<int*>(out.data_ptr());
+  const auto head = std::make_tuple(op_out, cp(q), fp(weights), cp(k_cache), ip(block_ids));
+  const auto shape = std::make_tuple(i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)), block_stride(k_cache), i32(topk));
+  if (rows.ragged()) {
+    checked_launch(op, hpc_mla_indexer_topk_prefill_fp8_refusal, hpc_mla_indexer_topk_prefill_fp8_async, work,
+                   std::tuple_cat(head, rows.chunk_args(d.rows), shape, std::make_tuple(i32(scratch_rows), ws_ptr, ws_bytes)),
+                   std::make_tuple(stream_of(q)));
+    if (d.rows > 0 && rows.units() == 0) out.fill_(-1);  // every row is a row of no request
+    return out;
+  }
+  // a step's launcher takes new_kv_included in the middle of its list: written out
+  const char* why =
+      std::apply(hpc_mla_indexer_topk_fp8_refusal, std::tuple_cat(head, rows.step_args(), shape, std::make_tuple(ws_ptr, ws_bytes)));
+  TORCH_CHECK(why == nullptr, op, ": ", why);
+  if (!work) return out;  // nothing to launch
+  const int rc = hpc_mla_indexer_topk_fp8_async(op_out, cp(q), fp(weights), cp(k_cache), ip(block_ids), ip(rows.lens), i32(rows.units()),
+                                                i32(rows.mtp + 1), i32(d.h), i32(d.page), i32(d.max_blocks), i32(k_cache.size(0)),
+                                                block_stride(k_cache), i32(topk), rows.new_kv_included ? 1 : 0, ws_ptr, ws_bytes,
+                                                stream_of(q));
+  HPC_LAUNCH_CHECK(rc, op);
   return out;
+}
+
+// the eight registered functions: the schema's arguments as the rows of a step or of a chunk
+at::Tensor logits_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                      const at::Tensor& num_seq_kvcache, int64_t mtp, bool new_kv_included, const c10::optional<at::Tensor>& output) {
+  return logits_body("mla_indexer_logits_fp8", q, weights, k_cache, block_ids, {num_seq_kvcache, nullptr, mtp, 0, new_kv_included}, output);
+}
+at::Tensor select_topk(const at::Tensor& logits, const at::Tensor& num_seq_kvcache, int64_t topk, int64_t mtp, bool new_kv_included,
+                       const c10::optional<at::Tensor>& output) {
+  return topk_body("mla_indexer_topk", logits, {num_seq_kvcache, nullptr, mtp, 0, new_kv_included}, topk, output);
+}
+at::Tensor topk_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                    const at::Tensor& num_seq_kvcache, int64_t topk, int64_t mtp, bool new_kv_included,
+                    const c10::optional<at::Tensor>& output) {
+  return fused_body("mla_indexer_topk_fp8", q, weights, k_cache, block_ids, {num_seq_kvcache, nullptr, mtp, 0, new_kv_included}, topk, 0,
+                    output);
+}
+at::Tensor logits_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                              const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t row_begin,
+                              const c10::optional<at::Tensor>& output) {
+  return logits_body("mla_indexer_logits_prefill_fp8", q, weights, k_cache, block_ids, {num_seqlen_per_req, &q_index, 0, row_begin, true},
+                     output);
+}
+at::Tensor topk_prefill(const at::Tensor& logits, const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk,
+                        int64_t row_begin, const c10::optional<at::Tensor>& output) {
+  return topk_body("mla_indexer_topk_prefill", logits, {num_seqlen_per_req, &q_index, 0, row_begin, true}, topk, output);
+}
+at::Tensor topk_prefill_fp8(const at::Tensor& q, const at::Tensor& weights, const at::Tensor& k_cache, const at::Tensor& block_ids,
+                            const at::Tensor& num_seqlen_per_req, const at::Tensor& q_index, int64_t topk, int64_t scratch_rows,
+                            const c10::optional<at::Tensor>& output) {
+  return fused_body("mla_indexer_topk_prefill_fp8", q, weights, k_cache, block_ids, {num_seqlen_per_req, &q_index, 0, 0, true}, topk,
+                    scratch_rows, output);
 }
 
 // ---- mla_indexer_prep_fp8: the front end (csrc/mla_indexer_prep.hip), pinned to tests/mla_indexer_prep_ref.py -------------------------
@@ -327,25 +302,16 @@ std::tuple<at::Tensor, at::Tensor> prep_fp8(const c10::optional<at::Tensor>& k_c
     if (out_q_rot.has_value()) qrot = out_or_new(out_q_rot, k, {rows, h, hpc::kIdxDim}, at::kBFloat16, "out_q_rot", kOnInputDevice);
   }
   const int64_t k_rs = rows > 1 ? k.stride(0) : hpc::kIdxDim;
-  const auto ip = [](const at::Tensor& t) { return static_cast<const int*>(t.data_ptr()); };
-  const auto fp = [](const at::Tensor& t) { return static_cast<const float*>(t.data_ptr()); };
   const auto vp = [](const at::Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; };
   // float32(softmax_scale * Hi ** -0.5), formed in double as the caller's Python would
   const float ss = with_q ? static_cast<float>(*softmax_scale * hpc::mla_indexer_prep_head_factor(i32(h))) : 0.f;
-  const char* why = hpc_mla_indexer_prep_fp8_refusal(
-      ptr(k_cache), vp(ok), with_q ? q8.data_ptr() : nullptr, with_q ? static_cast<float*>(w.data_ptr()) : nullptr, vp(qrot), ptr(k),
-      ptr(q), ptr(head_weights), fp(k_norm_weight), fp(k_norm_bias), fp(cos_sin), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
-      i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)), i32(num_blocks), i32(cos_sin.size(0)), bs, k_rs, q_rs, q_hs,
-      hw_bf16 ? 1 : 0, ss, static_cast<float>(eps), static_cast<float>(rotate_scale));
-  TORCH_CHECK(why == nullptr, "mla_indexer_prep_fp8: ", why);
-  if (rows == 0 || num_req == 0) return {q8, w};  // nothing to launch
-  const int rc = hpc_mla_indexer_prep_fp8_async(
-      ptr(k_cache), vp(ok), with_q ? q8.data_ptr() : nullptr, with_q ? static_cast<float*>(w.data_ptr()) : nullptr, vp(qrot), ptr(k),
-      ptr(q), ptr(head_weights), fp(k_norm_weight), fp(k_norm_bias), fp(cos_sin), ip(num_seqlen_per_req), ip(q_index), ip(block_ids),
-      i32(rows), i32(num_req), i32(h), i32(page), i32(block_ids.size(1)), i32(num_blocks), i32(cos_sin.size(0)), bs, k_rs, q_rs, q_hs,
-      hw_bf16 ? 1 : 0, ss, static_cast<float>(eps), static_cast<float>(rotate_scale), interleaved ? 1 : 0, pow2_scale ? 1 : 0,
-      stream_of(k));
-  HPC_LAUNCH_CHECK(rc, "mla_indexer_prep_fp8");
+  checked_launch(
+      "mla_indexer_prep_fp8", hpc_mla_indexer_prep_fp8_refusal, hpc_mla_indexer_prep_fp8_async, rows > 0 && num_req > 0,
+      std::make_tuple(ptr(k_cache), vp(ok), with_q ? q8.data_ptr() : nullptr, with_q ? static_cast<float*>(w.data_ptr()) : nullptr,
+                      vp(qrot), cp(k), ptr(q), ptr(head_weights), fp(k_norm_weight), fp(k_norm_bias), fp(cos_sin), ip(num_seqlen_per_req), ip(q_index), ip(block_ids), i32(rows), i32(num_req), i32(h),
+                      i32(page), i32(block_ids.size(1)), i32(num_blocks), i32(cos_sin.size(0)), bs, k_rs, q_rs, q_hs, hw_bf16 ? 1 : 0, ss,
+                      static_cast<float>(eps), static_cast<float>(rotate_scale)),
+      std::make_tuple(interleaved ? 1 : 0, pow2_scale ? 1 : 0, stream_of(k)));
   return {q8, w};
 }
 

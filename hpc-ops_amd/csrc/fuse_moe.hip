@@ -692,6 +692,8 @@ namespace {
 struct MoeScales {
   bool blockwise;  // x_scale [token][hidden / 128] and 128 x 128 weight scale blocks (rows padded to *_pad4 floats), activation
                    // quantised per 128 columns; else one scale per expert on each GEMM and act_mul_scale[0] on the activation
+  bool mxfp4;      // (with blockwise) the weights are MXFP4 with e8m0 scales per 32 k, both GEMMs hpc_group_gemm_mxfp4_async:
+                   // x_scale and the activation between them as in the blockwise pipeline, *_pad4 unused
   const void *x_scale, *gate_up, *down, *act_mul;
   int gate_up_pad4, down_pad4, use_bf16_mul;
 };
@@ -712,7 +714,12 @@ int fuse_moe(void* y_ptr, void* workspace, const void* x_ptr, const void* gate_u
   // gate_up: rows come straight from x through row_index, blockwise scales from x_scale[token][kb].  Where ggemm_route() puts
   // the activation (+ quantisation) into the GEMM's epilogue the bf16 gate-up matrix is never written; else it runs here.
   int fused = 0;
-  rc = s.blockwise
+  rc = s.mxfp4
+           ? hpc_group_gemm_mxfp4_async(ws + w.gate_up_out, x_ptr, static_cast<const float*>(s.x_scale), gate_up_weight_ptr, s.gate_up,
+                                        reinterpret_cast<const int*>(ws + w.seqlens), reinterpret_cast<const int*>(ws + w.cu_seqlens),
+                                        reinterpret_cast<const int*>(ws + w.row_index), num_expert, m, num_tokens, intermediate_size2,
+                                        hidden_size, stream)
+       : s.blockwise
            ? hpc_group_gemm_blockwise_fp8_act(ws + w.gate_up_out, ws + w.down_in, ws + w.down_in_scale, x_ptr, gate_up_weight_ptr,
                                               ws + w.seqlens, ws + w.cu_seqlens, s.x_scale, s.gate_up, ws + w.row_index, nullptr,
                                               num_expert, m, intermediate_size2, hidden_size, s.gate_up_pad4, 16,
@@ -729,7 +736,12 @@ int fuse_moe(void* y_ptr, void* workspace, const void* x_ptr, const void* gate_u
                      : hpc_act_mul_and_quant_async(ws + w.down_in, ws + w.gate_up_out, s.act_mul, num_rows, m, inter,
                                                    s.use_bf16_mul, stream);
   if (rc) return rc;
-  rc = s.blockwise
+  rc = s.mxfp4
+           ? hpc_group_gemm_mxfp4_async(ws + w.down_out, ws + w.down_in, reinterpret_cast<const float*>(ws + w.down_in_scale),
+                                        down_weight_ptr, s.down, reinterpret_cast<const int*>(ws + w.seqlens),
+                                        reinterpret_cast<const int*>(ws + w.cu_seqlens), nullptr, num_expert, m, m, hidden_size, inter,
+                                        stream)
+       : s.blockwise
            ? hpc_group_gemm_blockwise_fp8_async(ws + w.down_out, ws + w.down_in, down_weight_ptr, ws + w.seqlens, ws + w.cu_seqlens,
                                                 ws + w.down_in_scale, s.down, nullptr, nullptr, num_expert, m, hidden_size, inter,
                                                 s.down_pad4, 16, inter / 128, 1, ws + w.cu_tiles, stream)
@@ -755,7 +767,30 @@ extern "C" int hpc_fuse_moe_blockwise_async(
   if ((hidden_size & 127) || (intermediate_size2 & 255) || num_topk > 128) return HPC_ERR_UNSUPPORTED;
   if (num_tokens <= 0) return HPC_OK;
   (void)num_expert_total;
-  const MoeScales s{true, x_scale_ptr, gate_up_weight_scale_ptr, down_weight_scale_ptr, nullptr, gate_up_ws_pad4, down_ws_pad4, 0};
+  const MoeScales s{true, false, x_scale_ptr, gate_up_weight_scale_ptr, down_weight_scale_ptr, nullptr, gate_up_ws_pad4, down_ws_pad4, 0};
+  return fuse_moe(y_ptr, workspace, x_ptr, gate_up_weight_ptr, down_weight_ptr, s, topk_ids_ptr, topk_scale_ptr, shared_output_ptr,
+                  num_tokens, hidden_size, intermediate_size2, intermediate_size2, num_topk, num_expert, rank_ep, stream);
+}
+
+// MXFP4 expert weights (e2m1 codes, e8m0 scales per 32 k), e4m3 activations with 128-block scales: the blockwise pipeline and its
+// workspace layout with hpc_group_gemm_mxfp4_async in both GEMM places; the activation between them is the blockwise one, unchanged.
+extern "C" int64_t hpc_fuse_moe_mxfp4_workspace_bytes(int num_tokens, int num_topk, int hidden_size, int intermediate_size2,
+                                                      int num_expert) {
+  return hpc_fuse_moe_blockwise_workspace_bytes(num_tokens, num_topk, hidden_size, intermediate_size2, num_expert);
+}
+
+extern "C" int hpc_fuse_moe_mxfp4_async(void* y_ptr, void* workspace, const void* x_ptr, const void* x_scale_ptr,
+                                        const void* gate_up_weight_ptr, const void* gate_up_weight_scale_ptr,
+                                        const void* down_weight_ptr, const void* down_weight_scale_ptr, const void* topk_ids_ptr,
+                                        const void* topk_scale_ptr, const void* shared_output_ptr, int num_tokens, int hidden_size,
+                                        int intermediate_size2, int num_topk, int num_expert, int rank_ep, hipStream_t stream) {
+  if (!y_ptr || !workspace || !x_ptr || !x_scale_ptr || !gate_up_weight_ptr || !gate_up_weight_scale_ptr || !down_weight_ptr ||
+      !down_weight_scale_ptr || !topk_ids_ptr || !topk_scale_ptr)
+    return HPC_ERR_INVALID;
+  if (hidden_size <= 0 || intermediate_size2 <= 0 || num_topk <= 0 || num_expert <= 0) return HPC_ERR_INVALID;
+  if ((hidden_size & 127) || (intermediate_size2 & 255) || num_topk > 128) return HPC_ERR_UNSUPPORTED;
+  if (num_tokens <= 0) return HPC_OK;
+  const MoeScales s{true, true, x_scale_ptr, gate_up_weight_scale_ptr, down_weight_scale_ptr, nullptr, 0, 0, 0};
   return fuse_moe(y_ptr, workspace, x_ptr, gate_up_weight_ptr, down_weight_ptr, s, topk_ids_ptr, topk_scale_ptr, shared_output_ptr,
                   num_tokens, hidden_size, intermediate_size2, intermediate_size2, num_topk, num_expert, rank_ep, stream);
 }
@@ -774,7 +809,7 @@ extern "C" int hpc_fuse_moe_pertensor_async(
     return HPC_ERR_INVALID;
   if ((hidden_size & 63) || (intermediate_size2 & 127) || num_topk > 128) return HPC_ERR_UNSUPPORTED;
   if (num_tokens <= 0) return HPC_OK;
-  const MoeScales s{false, nullptr, gate_up_scale_ptr, down_scale_ptr, act_and_mul_scale_ptr, 0, 0, use_bf16_mul};
+  const MoeScales s{false, false, nullptr, gate_up_scale_ptr, down_scale_ptr, act_and_mul_scale_ptr, 0, 0, use_bf16_mul};
   return fuse_moe(y_ptr, workspace, x_ptr, gate_up_weight_ptr, down_weight_ptr, s, topk_ids_ptr, topk_scale_ptr, shared_output_ptr,
                   num_tokens, hidden_size, intermediate_size2, (intermediate_size2 + 255) / 256 * 256, num_topk, num_expert, rank_ep,
                   stream);

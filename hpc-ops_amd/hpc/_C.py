@@ -73,6 +73,10 @@ _sig("hpc_act_mul_and_blockwise_quant_async", I, P, P, P, P, I, I, L, L, P, P)
 _sig("hpc_moe_reduce_async", I, P, P, P, P, P, I, I, I, P)
 _sig("hpc_fuse_moe_blockwise_workspace_bytes", L, I, I, I, I, I)
 _sig("hpc_fuse_moe_blockwise_async", I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P)
+_sig("hpc_group_gemm_mxfp4_plan", I, I, I, I, I, I, IP, IP, IP)
+_sig("hpc_group_gemm_mxfp4_async", I, P, P, P, P, P, P, P, P, I, I, I, I, I, P)
+_sig("hpc_fuse_moe_mxfp4_workspace_bytes", L, I, I, I, I, I)
+_sig("hpc_fuse_moe_mxfp4_async", I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P)
 
 _sig("hpc_group_gemm_pertensor_fp8_async", I, P, P, P, P, P, P, P, I, I, I, I, I, P, P)
 _sig("hpc_act_mul_and_quant_async", I, P, P, P, P, I, I, I, P)

@@ -255,6 +255,36 @@ int hpc_fuse_moe_blockwise_async(void* y_ptr, void* workspace, const void* x_ptr
                                  int gate_up_ws_pad4, int down_ws_pad4, int rank_ep,
                                  hpc_stream_t stream);
 
+/* ---- MXFP4 weights x e4m3 activations (W4A8), decode steps (ours: no reference counterpart; csrc/group_gemm_mxfp4.hip) ----
+ * The statement is tests/mxfp4_ref.py.  For the seqlens[g] output rows r starting at cu_seqlens[g], with row(r) = row_index[r] when
+ * row_index is given (gather-free MoE: the token) and r otherwise:
+ *   P[r, n, kb] = sum over the 128 k of block kb of x[row(r), k] * e2m1(weight[g, n, k]) * 2^(weight_scale[g, n, k / 32] - 127)
+ *   tot = fmaf(P[r, n, kb], x_scale[row(r), kb], tot), kb ascending, fp32;   y[r, n] = bf16_rne(tot)
+ * x e4m3 [x_rows, k] and x_scale f32 [x_rows, k / 128], both row-major (the pair hpc_blockwise_fp8_quant_async writes); weight
+ * uint8 [G, n, k / 2] in checkpoint layout, two e2m1 codes per byte, even k in the low nibble; weight_scale uint8 [G, n, k / 32],
+ * e8m0 (byte 255, NaN, is unspecified); y bf16 [m, n].  k % 128 == 0, n % 64 == 0, n * k / 2 and x_rows * k <= 0xfffffff0,
+ * num_group <= 65535 (HPC_ERR_UNSUPPORTED otherwise, as for a pointer that is not 16-byte aligned); null pointers, sizes below
+ * zero, num_group, n or k of zero and x_rows < m without a row_index are HPC_ERR_INVALID.  m == 0 launches nothing; an empty
+ * group costs nothing but its workgroups' first load.  A pass over a group's weights serves 16 / 32 / 48 rows, chosen from
+ * m / num_group (<= 10 / <= 22 / more); longer groups take several passes - correct at any length, meant for decode steps.
+ * hpc_group_gemm_mxfp4_plan gives the rows per pass and the grid of such a call (0 where nothing is launched; any out pointer may
+ * be NULL) and returns what the call would for these shapes.  Every check is made on the host before any device call. */
+int hpc_group_gemm_mxfp4_plan(int num_group, int m, int x_rows, int n, int k, int* tokens_per_pass, int* grid_x, int* grid_y);
+int hpc_group_gemm_mxfp4_async(void* y, const void* x, const float* x_scale, const void* weight, const void* weight_scale,
+                               const int* seqlens, const int* cu_seqlens, const int* row_index /* may be NULL */, int num_group,
+                               int m, int x_rows, int n, int k, hpc_stream_t stream);
+/* The fused MoE on MXFP4 expert weights: hpc_fuse_moe_blockwise_async's pipeline and workspace layout with the GEMM above in both
+ * places - count/slot -> gate-up GEMM (rows through row_index, scales by token) -> hpc_act_mul_and_blockwise_quant_async (e4m3 +
+ * f32 128-block scales: what the second GEMM takes) -> down GEMM -> reduce.  gate_up_weight uint8 [E, 2I, H / 2] with scales
+ * [E, 2I, H / 32], down_weight uint8 [E, H, I / 2] with scales [E, H, I / 32]; hidden % 128 == 0, intermediate_size2 % 256 == 0,
+ * num_topk <= 128.  No host sync. */
+int64_t hpc_fuse_moe_mxfp4_workspace_bytes(int num_tokens, int num_topk, int hidden_size, int intermediate_size2, int num_expert);
+int hpc_fuse_moe_mxfp4_async(void* y_ptr, void* workspace, const void* x_ptr, const void* x_scale_ptr,
+                             const void* gate_up_weight_ptr, const void* gate_up_weight_scale_ptr, const void* down_weight_ptr,
+                             const void* down_weight_scale_ptr, const void* topk_ids_ptr, const void* topk_scale_ptr,
+                             const void* shared_output_ptr, int num_tokens, int hidden_size, int intermediate_size2, int num_topk,
+                             int num_expert, int rank_ep, hpc_stream_t stream);
+
 /* Per-tensor FP8 MoE pieces (reference src/fuse_moe/fuse_moe.h:15-40 fuse_moe_async, src/group_gemm/
  * group_gemm.h group_gemm_fp8_async, src/activation/activation.h act_mul_and_quant_async /
  * scaled_fp8_quant_async, cp.async pipeline src/fuse_moe/cp_async/fuse_moe.cu:16-63):

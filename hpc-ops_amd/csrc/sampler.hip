@@ -22,6 +22,8 @@
 // Draft-token verification of a speculative step (hpc_speculative_verify_async) is the fast path's segment pass plus the
 // segment's softmax statistics, and a one-wave accept scan per request.  Both passes score a token with score_composite,
 // so speculative_verify returns bit for bit the token the fast path returns for the same row, noise and draft.
+// The log-probability, rank and top-N of a row's token (hpc_token_logprobs_async) are the verification's segment pass
+// without the noise plus a count of larger composites, and the top-k selection above on torch_topk_key composites.
 // Ordered keys, (key, index) composites and the 64-bit wave operations: ordered_key.h.
 #include "ordered_key.h"
 #include "../../include/hpc_amd.h"
@@ -572,6 +574,242 @@ __global__ __launch_bounds__(64) void verify_final_kernel(const VerifyArgs v) {
   if (lane == 0) v.num_accepted[b] = jr;
 }
 
+// ---- log-probability, rank and top-N of a given token per row (ours: no reference counterpart) ------------------------
+// The third reader of the logits a step ends in, after the sampler and the verification: row r has a token t_r (what one
+// of them emitted, or a prompt token), and the answer is y[t] - logsumexp(y) with y = x / T (x when T == 0), the token's
+// 1-based rank in the order of the RAW logits, and the first num_top entries of that order with their log-probabilities.
+// The order is torch_topk_key's (-0.0 == +0.0, ties to the smaller id) as 52-bit composites, so a rank is a count of
+// larger composites and the top list is the sampler's threshold / compaction / select_kth selection.  Phase 1 (grid S x
+// rows) is verify_segment_kernel's pass - every load issued first, the same y, the same statistics - plus the count and,
+// with num_top > 0, the segment's candidates; phase 2 (one workgroup per row) folds, selects, sorts and writes.  A row
+// whose token is outside [0, V) is dead: neither phase reads its logits.
+struct LogprobStat {  // one per (row, segment)
+  float m, sum;       // max of y, sum exp(y - m)
+  int above, pad;     // elements of the segment whose composite is larger than the token's
+};
+struct LogprobArgs {
+  Args a;             // logits, dtype, row_stride, B = rows, V, S, seg, t_arr / t_val
+  const void* tok;    // [rows] int32 or int64
+  int tok_bytes;
+  int rows_per_temp;  // row r uses t_arr[r / rows_per_temp]
+  int row0;           // first row of this launch pair (a grid's y extent is 65535)
+  int K;              // num_top
+  float* lp;          // [rows]
+  int* rank;          // [rows]
+  int* top_ids;       // [rows][K]
+  float* top_lp;      // [rows][K]
+  LogprobStat* stat;  // [rows][S]
+  uint64_t* cand;     // [rows][S][K] composites
+};
+
+// the row's token, -1 when the row is dead
+__device__ __forceinline__ int logprob_token(const LogprobArgs& g, int r) {
+  const int64_t t = g.tok_bytes == 8 ? static_cast<const int64_t*>(g.tok)[r] : static_cast<const int*>(g.tok)[r];
+  return (t < 0 || t >= g.a.V) ? -1 : static_cast<int>(t);
+}
+__device__ __forceinline__ float logprob_temp(const LogprobArgs& g, int r) {
+  return g.a.t_arr ? g.a.t_arr[r / g.rows_per_temp] : g.a.t_val;
+}
+// The one expression behind token_logprobs and top_logprobs: the element's value decoded from its order key (so -0.0 has
+// become +0.0 for both), scaled as phase 1 scaled it, minus the row's maximum first - |y - m| <= |result|, so the
+// subtraction costs one rounding of the result and not one of m + log(sum) - then minus log(sum).
+__device__ __forceinline__ float logprob_value(uint32_t key, float temp, float m, float log_sum) {
+  const float x = ieee_key_value(key);
+  const float y = temp > 0.f ? x / temp : x;
+  return (y - m) - log_sum;
+}
+
+template <bool kTop>
+__global__ __launch_bounds__(kThreads) void logprobs_segment_kernel(const LogprobArgs g) {
+  __shared__ uint64_t s_list[kTop ? kSegMax : 1];
+  __shared__ unsigned s_hist[256];
+  __shared__ int s_misc[6];
+  __shared__ float s_m[4], s_s[4];
+  __shared__ int s_c[4];
+  const Args& a = g.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x, r = g.row0 + blockIdx.y;
+  const int tok = logprob_token(g, r);
+  if (tok < 0) return;  // block-uniform
+  const float temp = logprob_temp(g, r);
+  const bool greedy = !(temp > 0.f);
+  const uint64_t ctok = comp_of(torch_topk_key(load_logit(a, r, tok)), static_cast<uint32_t>(tok));
+  const int i0 = s * a.seg, i1 = min(a.V, i0 + a.seg);
+
+  // as verify_segment_kernel: all loads first; out-of-range slots read the segment's last element and are set to -inf
+  float xs[kElems];
+  const int last = i1 - 1;
+  if (i0 >= i1) {
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = 0.f;
+  } else if (a.dtype == 0) {
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = load_logit(a, r, min(i0 + e * kThreads + tid, last));
+  } else {
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) xs[e] = load_logit(a, r, min(i0 + e * kThreads + tid, last));
+  }
+  uint32_t key[kTop ? kElems : 1];
+  uint32_t best = 0;
+  float m = kNegInf;
+  int above = 0;
+#pragma unroll
+  for (int e = 0; e < kElems; ++e) {
+    const int i = i0 + e * kThreads + tid;
+    const bool in = i < i1;
+    const uint32_t k = in ? torch_topk_key(xs[e]) : 0u;
+    above += in && comp_of(k, static_cast<uint32_t>(i)) > ctok;
+    if (kTop) {
+      key[e] = k;
+      best = max(best, k);
+    }
+    const float y = greedy ? xs[e] : xs[e] / temp;
+    xs[e] = in ? y : kNegInf;
+    m = fmaxf(m, xs[e]);
+  }
+  float sum = 0.f;
+  {
+    const float sub = m == kNegInf ? 0.f : m;
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) sum += __expf(xs[e] - sub);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    above += __shfl_xor(above, o, 64);
+    stat_merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
+  }
+  if (lane == 0) {
+    s_m[wave] = m;
+    s_s[wave] = sum;
+    s_c[wave] = above;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) {
+      stat_merge(m, sum, s_m[w], s_s[w]);
+      above += s_c[w];
+    }
+    LogprobStat* st = g.stat + static_cast<long>(r) * a.S + s;
+    st->m = m;
+    st->sum = sum;
+    st->above = above;
+  }
+  if constexpr (kTop) {
+    // the segment's top K composites, as sampler_segment_kernel selects them
+    const int K = g.K;
+    const int n = max(i1 - i0, 0);
+    uint32_t bound = 0;
+    if (n > K) {
+      s_list[tid] = comp_of(best, tid);
+      __syncthreads();
+      bound = static_cast<uint32_t>(select_kth(s_list, kThreads, K, s_hist, s_misc) >> kIdxBits);
+    }
+    if (tid == 0) s_misc[2] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kElems; ++e) {
+      if (key[e] && key[e] >= bound) {
+        const int pos = atomicAdd(&s_misc[2], 1);
+        s_list[pos] = comp_of(key[e], i0 + e * kThreads + tid);
+      }
+    }
+    __syncthreads();
+    const int cnt = s_misc[2];
+    uint64_t thr = 0;
+    if (cnt > K) thr = select_kth(s_list, cnt, K, s_hist, s_misc);
+    if (tid == 0) s_misc[3] = 0;
+    __syncthreads();
+    uint64_t* out = g.cand + (static_cast<long>(r) * a.S + s) * K;
+    for (int i = tid; i < cnt; i += kThreads) {
+      const uint64_t c = s_list[i];
+      if (c >= thr) out[atomicAdd(&s_misc[3], 1)] = c;
+    }
+    __syncthreads();
+    // fewer than K elements: pad with distinct composites below every real one (key part 0)
+    for (int i = min(cnt, K) + tid; i < K; i += kThreads) out[i] = static_cast<uint64_t>(s * K + i);
+  }
+}
+
+// kTop: 256 threads select the K winners out of S * K, then wave 0 sorts them; otherwise one wave.
+template <bool kTop>
+__global__ __launch_bounds__(kTop ? kThreads : 64) void logprobs_final_kernel(const LogprobArgs g) {
+  constexpr int kListMax = (1 << kIdxBits) / kSegMax * 32;  // S <= 128 segments of K <= 32 candidates
+  __shared__ uint64_t s_list[kTop ? kListMax : 1];
+  __shared__ uint64_t s_sel[64];
+  __shared__ unsigned s_hist[256];
+  __shared__ int s_misc[6];
+  const Args& a = g.a;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = g.row0 + blockIdx.x;
+  const int K = g.K;
+  const int tok = logprob_token(g, r);
+  if (tok < 0) {  // block-uniform
+    if (tid == 0) {
+      g.lp[r] = 0.f;
+      g.rank[r] = 0;
+    }
+    for (int i = tid; i < K; i += blockDim.x) {
+      g.top_ids[static_cast<long>(r) * K + i] = -1;
+      g.top_lp[static_cast<long>(r) * K + i] = 0.f;
+    }
+    return;
+  }
+  uint64_t c = 0;
+  if (kTop) {
+    const int n = a.S * K;  // > K: S >= 16
+    const uint64_t* cand = g.cand + static_cast<long>(r) * n;
+    for (int i = tid; i < n; i += kThreads) s_list[i] = cand[i];
+    if (tid < 64) s_sel[tid] = 0;
+    if (tid == 0) s_misc[2] = 0;
+    __syncthreads();
+    const uint64_t thr = select_kth(s_list, n, K, s_hist, s_misc);
+    for (int i = tid; i < n; i += kThreads) {
+      const uint64_t v = s_list[i];
+      if (v >= thr) s_sel[atomicAdd(&s_misc[2], 1)] = v;
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    // bitonic sort (descending) of one composite per lane, as sampler_final_kernel's
+    c = s_sel[lane];
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        const uint64_t o = shfl_xor_u64(c, j);
+        const bool up = (lane & k) != 0;
+        const bool lower = (lane & j) == 0;
+        const bool take_max = (lower != up);
+        c = take_max ? (c > o ? c : o) : (c < o ? c : o);
+      }
+  }
+  float m = kNegInf, sum = 0.f;
+  int above = 0;
+  for (int s = lane; s < a.S; s += 64) {
+    const LogprobStat st = g.stat[static_cast<long>(r) * a.S + s];
+    stat_merge(m, sum, st.m, st.sum);
+    above += st.above;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    above += __shfl_xor(above, o, 64);
+    stat_merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
+  }
+  // lane 0's fold for every lane: the token's value and its slot of the top list must see the same bits
+  m = __shfl(m, 0, 64);
+  const float log_sum = logf(__shfl(sum, 0, 64));
+  const float temp = logprob_temp(g, r);
+  if (lane == 0) {
+    g.lp[r] = logprob_value(torch_topk_key(load_logit(a, r, tok)), temp, m, log_sum);
+    g.rank[r] = above + 1;
+  }
+  if (kTop && lane < K) {
+    const uint32_t key = static_cast<uint32_t>(c >> kIdxBits);
+    const bool real = key != 0;  // num_top <= V: always
+    g.top_ids[static_cast<long>(r) * K + lane] = real ? static_cast<int>(kIdxMask - (c & kIdxMask)) : -1;
+    g.top_lp[static_cast<long>(r) * K + lane] = real ? logprob_value(key, temp, m, log_sum) : 0.f;
+  }
+}
+
 // launch counter: the same seed gives fresh noise on every launch (reference sampler_rng.cuh:41-52)
 std::atomic<uint64_t> g_launch_offset{0};
 inline uint64_t next_offset() { return g_launch_offset.fetch_add(128, std::memory_order_relaxed); }
@@ -726,5 +964,67 @@ extern "C" int hpc_speculative_verify_async(void* output_token_ids, void* num_ac
   HPC_CHECK_LAUNCH();
   verify_final_kernel<<<batch_size, 64, 0, stream>>>(v);
   HPC_CHECK_LAUNCH();
+  return HPC_OK;
+}
+
+// workspace: segment statistics [rows][S] of 16 bytes + candidates [rows][S][num_top] u64
+extern "C" int64_t hpc_token_logprobs_workspace_bytes(int rows, int num_top, int vocab_size) {
+  if (rows < 0 || num_top < 0 || vocab_size <= 0) return 0;
+  const int64_t slots = static_cast<int64_t>(rows) * hpc::sampler::segments_of(vocab_size);
+  return slots * static_cast<int64_t>(sizeof(hpc::sampler::LogprobStat)) + slots * num_top * 8;
+}
+
+// semantics: include/hpc_amd.h.  Every check runs before the rows == 0 return, so none can reach a launch.
+extern "C" int hpc_token_logprobs_async(void* token_logprobs, void* token_ranks, void* top_ids, void* top_logprobs, void* workspace,
+                                        const void* logits, int logits_dtype, int64_t logits_row_stride, const void* token_ids,
+                                        int token_id_bytes, const void* temperature, int temperature_count, float temperature_val,
+                                        int rows, int num_top, int vocab_size, hipStream_t stream) {
+  using namespace hpc::sampler;
+  if (!token_logprobs || !token_ranks || !workspace || !logits || !token_ids) return HPC_ERR_INVALID;
+  if (rows < 0 || num_top < 0 || vocab_size <= 0) return HPC_ERR_INVALID;
+  if (num_top > 0 && (!top_ids || !top_logprobs)) return HPC_ERR_INVALID;
+  if (logits_dtype != 0 && logits_dtype != 1) return HPC_ERR_INVALID;
+  if (logits_row_stride < vocab_size) return HPC_ERR_INVALID;
+  if (token_id_bytes != 4 && token_id_bytes != 8) return HPC_ERR_INVALID;
+  if (temperature ? (temperature_count < 1 || rows % temperature_count != 0) : !(temperature_val >= 0.f)) return HPC_ERR_INVALID;
+  if ((vocab_size & 7) || vocab_size >= (1 << kIdxBits)) return HPC_ERR_UNSUPPORTED;
+  if (num_top > 32 || num_top > vocab_size) return HPC_ERR_UNSUPPORTED;
+  if (rows == 0) return HPC_OK;
+  LogprobArgs g{};
+  Args& a = g.a;  // fill_common's fields without its noise offset: this op draws nothing
+  a.logits = logits;
+  a.dtype = logits_dtype;
+  a.row_stride = logits_row_stride;
+  a.B = rows;
+  a.V = vocab_size;
+  a.S = segments_of(vocab_size);
+  a.seg = (vocab_size + a.S - 1) / a.S;
+  a.t_arr = static_cast<const float*>(temperature);
+  a.t_val = temperature_val;
+  g.tok = token_ids;
+  g.tok_bytes = token_id_bytes;
+  g.rows_per_temp = temperature ? rows / temperature_count : 1;
+  g.K = num_top;
+  g.lp = static_cast<float*>(token_logprobs);
+  g.rank = static_cast<int*>(token_ranks);
+  g.top_ids = static_cast<int*>(top_ids);
+  g.top_lp = static_cast<float*>(top_logprobs);
+  g.stat = static_cast<LogprobStat*>(workspace);
+  g.cand = reinterpret_cast<uint64_t*>(g.stat + static_cast<int64_t>(rows) * a.S);
+  // rows sit on the grid's y axis: one launch pair per 65535 rows
+  for (int row0 = 0; row0 < rows; row0 += 65535) {
+    const int n = rows - row0 < 65535 ? rows - row0 : 65535;
+    g.row0 = row0;
+    if (num_top > 0) {
+      logprobs_segment_kernel<true><<<dim3(a.S, n), kThreads, 0, stream>>>(g);
+      HPC_CHECK_LAUNCH();
+      logprobs_final_kernel<true><<<n, kThreads, 0, stream>>>(g);
+    } else {
+      logprobs_segment_kernel<false><<<dim3(a.S, n), kThreads, 0, stream>>>(g);
+      HPC_CHECK_LAUNCH();
+      logprobs_final_kernel<false><<<n, 64, 0, stream>>>(g);
+    }
+    HPC_CHECK_LAUNCH();
+  }
   return HPC_OK;
 }

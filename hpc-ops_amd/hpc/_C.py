@@ -153,6 +153,8 @@ _sig("hpc_fused_sampler_async", I, P, P, P, I, P, L, P, P, F, P, F, I, P, I, I, 
 _sig("hpc_fused_sampler_temperature_async", I, P, P, P, I, L, P, F, P, P, I, I, ctypes.c_uint64, P)
 _sig("hpc_speculative_verify_workspace_bytes", L, I, I, I)
 _sig("hpc_speculative_verify_async", I, P, P, P, P, I, L, P, P, F, P, P, I, I, I, ctypes.c_uint64, P)
+_sig("hpc_token_logprobs_workspace_bytes", L, I, I, I)
+_sig("hpc_token_logprobs_async", I, P, P, P, P, P, P, I, L, P, I, P, I, F, I, I, I, P)
 PP = ctypes.POINTER(c_void_p)
 _sig("hpc_comm_create", I, I, I, I, c_char_p)
 _sig("hpc_comm_destroy", I, I)

@@ -158,3 +158,57 @@ def _speculative_verify_fake(logits, draft_token_ids, temperature, temperature_v
     b, k = draft_token_ids.shape
     return (torch.empty((b, k + 1), dtype=torch.int32, device=logits.device),
             torch.empty((b,), dtype=torch.int32, device=logits.device))
+
+
+def token_logprobs(
+    logits: Tensor,
+    token_ids: Tensor,
+    temperature: Union[Tensor, float] = 1.0,
+    num_top: int = 0,
+    token_logprobs: Optional[Tensor] = None,
+    token_ranks: Optional[Tensor] = None,
+    top_ids: Optional[Tensor] = None,
+    top_logprobs: Optional[Tensor] = None,
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The log-probability of the token each logits row emitted, its rank, and the row's ``num_top`` most likely tokens
+    with their log-probabilities, in one pass over the logits: the ``logprobs`` / ``top_logprobs`` of a completion API,
+    the per-token logprobs of an RL rollout, ``prompt_logprobs`` over a prefill chunk.  It reads the logits
+    fused_sampler or speculative_verify has just read and takes what they return as it is.  No reference counterpart
+    (torch.ops.hpc_logprobs.token_logprobs); semantics = PyTorch (tests/token_logprobs_ref.py).
+
+    logits [R, V] float32 / bfloat16 (inner stride 1, row stride >= V, V % 8 == 0, V < 2^20, never written).  token_ids
+    int32 or int64, contiguous, R elements in any shape: [R], the [R, 1] fused_sampler returns, the [B, K + 1]
+    speculative_verify returns for logits [B * (K + 1), V]; there is no cast and no host sync.  An entry < 0 or >= V marks
+    a dead row (the -1 entries of a speculative step): its logits are not read and its outputs are 0.0, 0, -1 ..., 0.0 ....
+    temperature: scalar >= 0, or a float32 tensor of C elements with R % C == 0, row r using entry r // (R / C) - C == R
+    is a value per row, C == B the per-request tensor speculative_verify takes.  With x = logits[r].float():
+        T > 0:  y = x / T (an fp32 division, speculative_verify's expression)
+        T == 0: y = x, the raw distribution of a greedy request          (negative or NaN T: unspecified)
+    Per row r with token t:
+        token_logprobs[r] = y[t] - logsumexp(y)                                                    float32 [R]
+        token_ranks[r]    = 1 + #{i : x[i] > x[t] or (x[i] == x[t] and i < t)}                     int32 [R]
+        top_ids[r], top_logprobs[r] = the first num_top ids of that order, y[id] - logsumexp(y)    int32 / float32 [R, num_top]
+    The order is that of the raw logits as floats - -0.0 == +0.0, ties to the smaller id: torch.sort(x, descending=True,
+    stable=True) - so neither rank nor ids depend on the temperature.  Wherever rank <= num_top, top_ids[r, rank - 1] == t
+    and top_logprobs[r, rank - 1] is bit-identical to token_logprobs[r].  0 <= num_top <= 32, num_top <= V; num_top == 0
+    returns [R, 0] tensors and selects nothing.
+
+    -inf logits (a masked vocabulary) are ordinary inputs: they add nothing to the sum and rank last, and a token whose
+    logit is -inf has logprob -inf.  A row with a NaN, a +inf or a maximum of -inf is unspecified.
+
+    token_logprobs, token_ranks, top_ids and top_logprobs, when given, are written and returned as the same objects.
+    R == 0 returns empty tensors without a launch; any R is accepted (one launch pair per 65535 rows).  There is no host
+    sync, and scratch comes from the caching allocator, so the call can be captured in a hipGraph.
+    Returns (token_logprobs, token_ranks, top_ids, top_logprobs)."""
+    temp_tensor, temp_scalar = (temperature, 0.0) if isinstance(temperature, Tensor) else (None, float(temperature))
+    given = (token_logprobs, token_ranks, top_ids, top_logprobs)
+    outs = torch.ops.hpc_logprobs.token_logprobs(logits, token_ids, temp_tensor, temp_scalar, int(num_top), *given)
+    return tuple(o if g is None else g for o, g in zip(outs, given))
+
+
+@torch.library.register_fake("hpc_logprobs::token_logprobs")
+def _token_logprobs_fake(logits, token_ids, temperature, temperature_val, num_top, token_logprobs=None, token_ranks=None,
+                         top_ids=None, top_logprobs=None):
+    r, dev = logits.shape[0], logits.device
+    return (torch.empty((r,), dtype=torch.float32, device=dev), torch.empty((r,), dtype=torch.int32, device=dev),
+            torch.empty((r, num_top), dtype=torch.int32, device=dev), torch.empty((r, num_top), dtype=torch.float32, device=dev))

@@ -1028,6 +1028,37 @@ int hpc_speculative_verify_async(void* output_token_ids, void* num_accepted, voi
                                  const void* gumbel_noise, int batch_size, int num_draft, int vocab_size,
                                  uint64_t rng_seed, hpc_stream_t stream);
 
+/* ---- log-probability, rank and top-N of a given token per logits row (ours: no reference counterpart) ----
+ * What a completion API's logprobs / top_logprobs, an RL rollout and prompt_logprobs need of the logits a step ends in,
+ * in one pass.  logits [rows, V] as for the sampler above (dtype 0 fp32 / 1 bf16, inner stride 1, row stride >= V in
+ * elements, V % 8 == 0, V < 2^20, never written).  token_ids [rows] of token_id_bytes = 4 (int32) or 8 (int64): the
+ * token a sampler or the verification emitted for that row, or a prompt token.  An entry < 0 or >= V marks a dead row
+ * (the -1 entries of a speculative step): its logits are not read, its outputs are 0.0, 0, -1 ..., 0.0 ....
+ * temperature f32 [temperature_count] or NULL (then temperature_val >= 0): row r uses entry
+ * r / (rows / temperature_count), so a count of rows is a value per row and a count of batch_size the per-request tensor
+ * hpc_speculative_verify_async takes.  With x the fp32 row: y = x / T (an fp32 division) when T > 0, y = x when T == 0;
+ * negative or NaN T is unspecified.
+ *   token_logprobs f32 [rows]           y[t] - logsumexp(y)
+ *   token_ranks    i32 [rows]           1 + #{i : x[i] > x[t] or (x[i] == x[t] and i < t)}: the order of the raw logits
+ *                                       as floats, -0.0 == +0.0, ties to the smaller id (a stable descending sort); it
+ *                                       does not depend on T
+ *   top_ids        i32 [rows, num_top]  the first num_top ids of that order
+ *   top_logprobs   f32 [rows, num_top]  y[id] - logsumexp(y) of those ids
+ * Where rank <= num_top, top_ids[r][rank - 1] is the token and top_logprobs[r][rank - 1] has the bits of
+ * token_logprobs[r].  -inf logits are ordinary (they add nothing and rank last; such a token has logprob -inf); a row
+ * with a NaN, a +inf or a maximum of -inf is unspecified.  0 <= num_top <= 32, num_top <= V; top_ids and top_logprobs
+ * may be NULL when num_top == 0.  workspace: hpc_token_logprobs_workspace_bytes.  Any number of rows: one launch pair
+ * per 65535.  Every check runs on the host before the rows == 0 return and before any launch: HPC_ERR_INVALID for null
+ * pointers, negative sizes, a dtype other than 0 / 1, a row stride below V, token_id_bytes other than 4 / 8, a
+ * temperature_count < 1 or one that does not divide rows, a negative temperature_val without a tensor;
+ * HPC_ERR_UNSUPPORTED for V % 8 != 0, V >= 2^20, num_top > 32 and num_top > V. */
+int64_t hpc_token_logprobs_workspace_bytes(int rows, int num_top, int vocab_size);
+int hpc_token_logprobs_async(void* token_logprobs, void* token_ranks, void* top_ids, void* top_logprobs, void* workspace,
+                             const void* logits, int logits_dtype, int64_t logits_row_stride, const void* token_ids,
+                             int token_id_bytes /* 4 or 8 */, const void* temperature /* may be NULL */,
+                             int temperature_count, float temperature_val, int rows, int num_top, int vocab_size,
+                             hpc_stream_t stream);
+
 /* ---- communicator: socket rendezvous + symmetric device buffers (HIP IPC over xGMI) ---------------
  * reference: src/communicator/{communicator,channel,listener,connector,protocol}.cc (rank-0 star over
  *            an abstract unix socket "unix://name" / bare name, or "tcp://ip:port"),
